@@ -9,7 +9,10 @@ dim=512, 8 codebooks of 256 entries, 5 refinement passes (BASELINE.json metric).
 One "step" is one Quantizer.encode() of the per-GPU batch (65,536 synthetic Gaussian
 vectors already resident in HBM; uint8 codes written to HBM).  With N GPUs every rank
 encodes its own shard -- no collective on the data path (weak scaling).  Rank 0 prints
-ONE JSON line.  `roofline` is for the dominant kernel: its launch time from HIP events on the
+ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`, ...); --dump-outputs DIR also writes the codes of the last timed step
+(rank 0's batch) as DIR/codes.npy in float32.  Everything below is measured only under --full.
+`roofline` is for the dominant kernel: its launch time from HIP events on the
 launch stream (mcq_profile_encode), its counters (L1 <- L2 requests, HBM-side bytes) read live by
 rocprofv3 --pmc child runs of this command (--no-pmc-check: from the committed passes); a table
 kernel is priced against what binds it, the L2 -> L1 path (`bound`: "l2"); `cpu_baseline` times the torch-CPU restatement of the
@@ -463,6 +466,12 @@ def main():
     ap.add_argument("--dim", type=int, default=512)
     ap.add_argument("--num-codebooks", type=int, default=8)
     ap.add_argument("--refine-iters", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: parity against the oracle and the reference "
+                         "fixture, per-kernel times and roofline, decode, the other configs, the secondary figures, the trainer "
+                         "legs and the CPU baseline (the --no-* options below trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the codes of the last timed step (rank 0's batch) as DIR/codes.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event pass (for PMC runs)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for a dry run)")
@@ -481,6 +490,8 @@ def main():
     ap.add_argument("--shard-vectors", type=int, default=1 << 20,
                     help="vectors per GPU of the config-C shard leg under --gpus N > 1 (BASELINE config C: 8M over 8 GPUs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # The ONE line of this command goes to the process's real stdout; everything else that writes to file descriptor 1 -- RCCL prints
     # a version banner there, from C, when its first communicator comes up, and it lands AFTER the line when the buffers are flushed at
@@ -561,11 +572,14 @@ def main():
         per_rank_dt = [float(e.item()) for e in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "codes.npy"), codes.cpu().numpy().astype(np.float32))
 
     # ---- BASELINE config C under --gpus N > 1: the 8M-vector encode sharded over the GPUs, 1,048,576 vectors per GPU, no collective on
     # the data path; every rank times its own shard between barriers, value = all shards / the slowest rank
     shard = None
-    if dist is not None and not args.no_secondary:
+    if dist is not None and args.full and not args.no_secondary:
         shard = {}
         try:
             Bs = args.shard_vectors
@@ -602,7 +616,7 @@ def main():
     # a per-GPU batch of 4,096 frames, with the gradient all-reduce in two overlapped parts and as one collective
     dp = None
     dp_failed = False
-    if dist is not None and not args.no_secondary:
+    if dist is not None and args.full and not args.no_secondary:
         dp = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(), "iterations_per_phase": args.dp_iters}
         try:      # (a failure here must not take the headline line with it)
             for tag, per_gpu in (("config_e_global_batch_4096", max(4096 // world, 64)), ("config_e_per_gpu_batch_4096", 4096)):
@@ -633,6 +647,28 @@ def main():
             dist.destroy_process_group()
         if dp_failed:
             sys.exit(3)
+        return
+
+    value = world * B * args.steps / dt
+    out = {
+        "metric": "vectors encoded/sec at dim=512, 8 codebooks; uint8 codes bit-exact vs ref",
+        "value": round(value, 1), "unit": "vectors/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32 (products: exact 30-bit fixed point on the i8 MFMA)", "data": "synthetic",
+        "config": {"workload": f"Quantizer.encode, dim={D}, bytes_per_frame={N}, codebook_size={K}, "
+                               f"refine_indexes_iters={iters}, batch={B} fp32 Gaussian vectors per GPU "
+                               f"(BASELINE.json configs[1]), seeded synthetic codebooks",
+                   "global_batch": world * B, "parallelism": f"batch-sharded x{world}, no collective"},
+        "ranks": {"rccl_ranks": world, "backend": (dist.get_backend() if dist is not None else "none (one process)"),
+                  "launcher": os.environ.get("TORCHELASTIC_RUN_ID") and "torch.distributed.run" or "plain python",
+                  "per_rank_vectors_per_s": [round(B * args.steps / t_, 1) for t_ in per_rank_dt],
+                  "note": "value = all ranks' vectors / the slowest rank's time (barrier + synchronize on both sides)"},
+    }
+    if not args.full:
+        emit(out)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
         return
 
     # ---- parity (outside the timed region): sampled rows vs the CPU oracle, fixture rows vs the reference
@@ -694,7 +730,6 @@ def main():
         _lines = sum((_pmc.get(n_, {}).get("l2_read_request_bytes") or 0) for n_ in _pass_names)
         if _lines > 0:
             line_floor_ms = round((LIMB_PRODUCTS * exec_fpv * B / (PEAK_I8_MFMA_TOPS * 1e12) + iters * _lines / (PEAK_L2_GBPS * 1e9)) * 1e3, 3)
-    value = world * B * args.steps / dt
     if roofline is not None:
         roofline["whole_encode"] = {"ms_per_step": round(dt / args.steps * 1e3, 3), "executed_floor_ms": executed_floor_ms,
                                     "frac_of_floor": round(executed_floor_ms / (dt / args.steps * 1e3), 4),
@@ -703,19 +738,7 @@ def main():
                                     "note": "the whole encode against what THIS algorithm costs at the chip's peaks (products at the dense i8 "
                                             "peak + the table passes' useful bytes at the L2 peak), and against the same with the table passes "
                                             "priced by the 128-byte lines they move: see whole_encode"}
-    out = {
-        "metric": "vectors encoded/sec at dim=512, 8 codebooks; uint8 codes bit-exact vs ref",
-        "value": round(value, 1), "unit": "vectors/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32 (products: exact 30-bit fixed point on the i8 MFMA)", "data": "synthetic",
-        "config": {"workload": f"Quantizer.encode, dim={D}, bytes_per_frame={N}, codebook_size={K}, "
-                               f"refine_indexes_iters={iters}, batch={B} fp32 Gaussian vectors per GPU "
-                               f"(BASELINE.json configs[1]), seeded synthetic codebooks",
-                   "global_batch": world * B, "parallelism": f"batch-sharded x{world}, no collective"},
-        "ranks": {"rccl_ranks": world, "backend": (dist.get_backend() if dist is not None else "none (one process)"),
-                  "launcher": os.environ.get("TORCHELASTIC_RUN_ID") and "torch.distributed.run" or "plain python",
-                  "per_rank_vectors_per_s": [round(B * args.steps / t_, 1) for t_ in per_rank_dt],
-                  "note": "value = all ranks' vectors / the slowest rank's time (barrier + synchronize on both sides)"},
+    out.update({
         "parity": parity,
         "whole_encode": {"kernels_sum_ms": kernels_sum_ms,
                          "executed_floor_ms": executed_floor_ms, "frac_of_floor": round(executed_floor_ms / (dt / args.steps * 1e3), 4),
@@ -737,7 +760,7 @@ def main():
                                  "Gram matrix, so this fraction can exceed 1"},
         "roofline": roofline,
         "kernels": kernels,
-    }
+    })
     if dp is not None:
         out["dp_trainer"] = dp
     if shard is not None:

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -72,3 +75,28 @@ def test_committed_counters_need_the_exact_shape():
     assert bench.pmc_committed("stage0_tables", 256, 4, 256, 4096, 5) == (None, None)
     pm, _ = bench.pmc_committed("stage0_tables", 1024, 16, 256, 65536, 5)
     assert pm is not None
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_codes_of_its_last_step(tmp_path):
+    """a plain run prints the headline alone; --dump-outputs writes the codes its timed encode returned, which are the oracle's
+    codes of the same seeded batch (bench.py's state, rank 0's generator on cuda:0)"""
+    import torch
+    from oracle.oracle import OracleQuantizer
+    from quantization_amd import synthetic as gen
+    B, D, N, K = 4096, 512, 8, 256
+    r = _run(["--steps", "3", "--warmup", "1", "--batch-per-gpu", str(B), "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert got["steps"] == 3 and got["ms_per_step"] > 0 and got["value"] > 0
+    assert "parity" not in got and "kernels" not in got and "cpu_baseline" not in got
+    codes = np.load(os.path.join(str(tmp_path), "codes.npy"))
+    assert codes.dtype == np.float32 and codes.shape == (B, N)
+    st = gen.synthetic_state(103, D, K, N)
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(0)
+    x = torch.randn(B, D, generator=g, device="cuda:0", dtype=torch.float32).cpu().numpy()
+    o = OracleQuantizer(st["centers"], float(st["centers_scale"]), st["to_logits.weight"], st["to_logits.bias"],
+                        float(st["logits_scale"]))
+    rows = np.random.RandomState(1).choice(B, 512, replace=False)
+    assert np.array_equal(codes[rows], o.encode(x[rows], 5).astype(np.float32))

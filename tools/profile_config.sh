@@ -8,7 +8,7 @@ TAG=$1; DIM=$2; NCB=$3
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-ARGS="--dim $DIM --num-codebooks $NCB --no-cpu-baseline --no-secondary --no-pmc-check"
+ARGS="--full --dim $DIM --num-codebooks $NCB --no-cpu-baseline --no-secondary --no-pmc-check"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python $R/bench.py --steps 5 --warmup 2 $ARGS > $O/bench_under_rocprof.json 2> $O/kt.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/dec -- python $R/tools/exp_decode_shape.py $DIM $NCB 65536 > $O/dec.log 2>&1
 for pass in "tcp TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum" "fetch FETCH_SIZE" "write WRITE_SIZE" "sq SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU"; do
