@@ -123,12 +123,17 @@ int mcq_encode(const float *x, long B, const void *prepared, float lscale_exp, i
                int refine_iters, uint8_t *out_u8, int64_t *out_i64, void *workspace,
                size_t workspace_bytes, void *stream);
 
-/* mcq_encode with options.  MCQ_ENCODE_SKIP_FIXED_POINTS: _refine_indexes is a deterministic map
- * of (x, indexes), so a vector whose indexes a pass leaves unchanged is already final; with this
- * flag such vectors leave the active list and later passes only process the rest.  The codes are
- * identical to mcq_encode's for every input; the cost becomes data dependent (off by default, and
- * never used for the headline benchmark figure).                                                */
+/* mcq_encode with options.  Fixed-point skipping is ON by default (mcq_encode, mcq_encode_ex,
+ * mcq_refine_indexes): _refine_indexes is a deterministic map of (x, indexes), so a vector whose
+ * indexes a pass leaves unchanged is already final; such vectors leave the active list, their codes
+ * go straight to the caller's output, and later passes only process the rest.  The codes are
+ * identical to those of running every pass, for every input; the cost becomes data dependent
+ * (lower on trained states, where most vectors converge after two or three passes).
+ * MCQ_ENCODE_ALL_PASSES: run every pass on every vector (the cost of a batch where nothing
+ * converges; what mcq_profile_encode and the trainer entry mcq_logits_refine_codes time).
+ * MCQ_ENCODE_SKIP_FIXED_POINTS: accepted, no effect (the default it once opted into).            */
 #define MCQ_ENCODE_SKIP_FIXED_POINTS 1u
+#define MCQ_ENCODE_ALL_PASSES 8u
 #define MCQ_ENCODE_LSCALE_FROM_PREPARED 2u /* lscale_exp argument ignored: see mcq_prepare_dev */
 /* x points to IEEE fp16 [B][D] (the reference's data helper yields fp16 frames that callers widen,
  * quantization/quantization.py:798): rows widen to fp32 in the kernels' load path.  Every fp16 value

@@ -24,6 +24,7 @@ SYMBOLS = (
 )
 
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
+MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
 _lib = None
 
 

@@ -9,6 +9,7 @@
 #include "mcq_train_kernels.h"
 
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 using namespace mcq;
@@ -75,7 +76,7 @@ Prepared prepared_view(const void *p, int N, int K, int D) {
 // CT: how a codebook entry is held (mcq_tf_kernels.h: one byte up to 256 entries per codebook, two above)
 template <typename CT>
 struct WorkspaceT {
-    CT *idx, *idxB, *idxC, *final_idx;        // B, C, final: fixed-point skipping only
+    CT *idx, *idxB, *idxC, *final_idx;        // B, C: fixed-point skipping only; final_idx: spare (the workspace size is ABI)
     int *map[2], *cnt;
     float *E, *R, *xx, *XC;                   // per vector: |x_err|^2, |x_err - old_n|^2, |x|^2, x.C products
     float *gterms;                            // per vector: the N*N Gram entries G[o_m][o_m2] of the current indexes
@@ -146,6 +147,8 @@ WorkspaceT<CT> carve(void *ws, long Bc, int N, int K, int D) {
     w.tf.ent = nullptr;
     w.tf.out_i64 = nullptr;
     w.tf.out_u8 = nullptr;
+    w.tf.out_pack = 1;
+    w.tf.map = nullptr;
     w.tf.erG = w.tf.erXC = w.tf.erxx = nullptr;
     w.tf.erE = w.tf.erR = nullptr;
     w.tf.erK = 0;
@@ -294,12 +297,23 @@ int launch_logits(const int8_t *xf, const int *xe, long B, const Prepared &P, in
 }
 
 // ---------------------------------------------------------------- the refinement pass
+// Grid of a pass kernel: the full grid, or at most `cap` workgroups (a multiple of 8) that stride over the virtual workgroups of
+// the active vectors (capped: later passes of fixed-point skipping, where most workgroups of the full grid would find no vector
+// and still cost their dispatch, about 0.2 ns each)
+constexpr unsigned kCapStage0 = 32768, kCapWave = 65536;     // workgroups of four waves / of one wave
+inline unsigned pass_grid(unsigned full, bool capped, unsigned cap) { return (capped && full > cap) ? cap : full; }
+
 template <int K>
 int launch_tf_stage0_k(int N, const float *G, const float *XC, const tf_code_of<K> *idx, const float *R, const float *Q, long B,
-                       int keep, tf_code_of<K> *ent, float *S, tf_code_of<K> *fin, const int *nact, const int *map, hipStream_t st) {
-    const dim3 grid((unsigned)(((B + 3) / 4) * N)), block(256);
-#define MCQ_S0_CASE(NN) \
-    case NN: hipLaunchKernelGGL((k_tf_stage0<K, NN>), grid, block, 0, st, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map); break;
+                       int keep, tf_code_of<K> *ent, float *S, tf_code_of<K> *fin, const int *nact, const int *map, hipStream_t st,
+                       bool capped) {
+    const unsigned vgrid = (unsigned)(((B + 3) / 4) * N);
+    const dim3 grid(pass_grid(vgrid, capped, kCapStage0)), block(256);
+#define MCQ_S0_CASE(NN)                                                                                                            \
+    case NN:                                                                                                                       \
+        if (capped) hipLaunchKernelGGL((k_tf_stage0<K, NN, true>), grid, block, 0, st, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, vgrid); \
+        else hipLaunchKernelGGL((k_tf_stage0<K, NN, false>), grid, block, 0, st, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, vgrid);      \
+        break;
     switch (N) {
         MCQ_S0_CASE(1) MCQ_S0_CASE(2) MCQ_S0_CASE(4) MCQ_S0_CASE(8) MCQ_S0_CASE(16) MCQ_S0_CASE(32) MCQ_S0_CASE(64)
         default: return MCQ_EUNSUPPORTED;
@@ -310,16 +324,18 @@ int launch_tf_stage0_k(int N, const float *G, const float *XC, const tf_code_of<
 }
 
 int launch_tf_stage0(int K, int N, const float *G, const float *XC, const uint16_t *idx, const float *R, const float *Q,
-                     long B, int keep, uint16_t *ent, float *S, uint16_t *fin, const int *nact, const int *map, hipStream_t st) {
+                     long B, int keep, uint16_t *ent, float *S, uint16_t *fin, const int *nact, const int *map, hipStream_t st,
+                     bool capped) {
     switch (K) {
-        case 512: return launch_tf_stage0_k<512>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st);
-        case 1024: return launch_tf_stage0_k<1024>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st);
+        case 512: return launch_tf_stage0_k<512>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
+        case 1024: return launch_tf_stage0_k<1024>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
         default: return MCQ_EUNSUPPORTED;
     }
 }
 
 int launch_tf_stage0(int K, int N, const float *G, const float *XC, const uint8_t *idx, const float *R, const float *Q,
-                     long B, int keep, uint8_t *ent, float *S, uint8_t *fin, const int *nact, const int *map, hipStream_t st) {
+                     long B, int keep, uint8_t *ent, float *S, uint8_t *fin, const int *nact, const int *map, hipStream_t st,
+                     bool capped) {
     if (K == 16 && N >= 4 && keep <= 16) {       // four codebooks per wave, rank-in-row selection
         const dim3 grid((unsigned)((B * (N / 4) + 3) / 4)), block(256);
 #define MCQ_S16_CASE(NN) \
@@ -333,11 +349,11 @@ int launch_tf_stage0(int K, int N, const float *G, const float *XC, const uint8_
         return 0;
     }
     switch (K) {
-        case 16: return launch_tf_stage0_k<16>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st);
-        case 32: return launch_tf_stage0_k<32>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st);
-        case 64: return launch_tf_stage0_k<64>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st);
-        case 128: return launch_tf_stage0_k<128>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st);
-        case 256: return launch_tf_stage0_k<256>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st);
+        case 16: return launch_tf_stage0_k<16>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
+        case 32: return launch_tf_stage0_k<32>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
+        case 64: return launch_tf_stage0_k<64>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
+        case 128: return launch_tf_stage0_k<128>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
+        case 256: return launch_tf_stage0_k<256>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
         default: return MCQ_EUNSUPPORTED;
     }
 }
@@ -380,11 +396,14 @@ int launch_tf_up(int kh, int kc, const TfLists &L, long B, int N, int u, int nta
 // combine of the siblings of level v >= 2 (list lengths kh at level v - 1, kc at level v)
 template <typename CT>
 int launch_tf_comb(int kh, int kc, const float *E, const TfLists &L, long B, int N, int v, int keep, const float *tabs,
-                   CT *fin, const int *nact, hipStream_t st) {
-    const dim3 grid((unsigned)(B * (N >> (v + 1)))), block(64);
+                   CT *fin, const int *nact, hipStream_t st, bool capped) {
+    // (capped: the last combine only; the others of more than 8 codebooks keep their full grid)
+    if (fin == nullptr) capped = false;
+    const dim3 grid(pass_grid((unsigned)(B * (N >> (v + 1))), capped, kCapWave)), block(64);
 #define MCQ_COMB_CASE(A, C)                                                                                                        \
     if (kh == A && kc == C) {                                                                                                     \
-        if (fin) hipLaunchKernelGGL((k_tf_comb<A, C, true, CT>), grid, block, 0, st, E, L, B, N, v, keep, tabs, fin, nact);       \
+        if (fin && capped) hipLaunchKernelGGL((k_tf_comb<A, C, true, CT, true>), grid, block, 0, st, E, L, B, N, v, keep, tabs, fin, nact); \
+        else if (fin) hipLaunchKernelGGL((k_tf_comb<A, C, true, CT>), grid, block, 0, st, E, L, B, N, v, keep, tabs, fin, nact);  \
         else hipLaunchKernelGGL((k_tf_comb<A, C, false, CT>), grid, block, 0, st, E, L, B, N, v, keep, tabs, fin, nact);          \
         MCQ_LAUNCH_CHECK();                                                                                                       \
         return 0;                                                                                                                 \
@@ -430,10 +449,16 @@ inline bool pass16_enabled() {
     static const bool on = !(getenv("MCQ_PASS16") && atoi(getenv("MCQ_PASS16")) == 0);
     return on;
 }
+// fixed-point skipping applies to chunks of at least this many vectors; MCQ_SKIP_MIN_BATCH=<n> moves the threshold (read per
+// call: tools/exp_skip_trained.py measures the crossover, the tests run the skipping path on small batches)
+inline long skip_min_batch() {
+    const char *v = getenv("MCQ_SKIP_MIN_BATCH");
+    return v ? atol(v) : 8192;      // (4,096 vectors: 0.472 ms with compaction, 0.477 without; 8,192: 0.773 / 0.800)
+}
 
 template <typename CT>
 int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const WorkspaceT<CT> &w, const TfLists &L, long B, int N,
-                    int K, const int *nact, hipStream_t st, Prof *prof) {
+                    int K, const int *nact, hipStream_t st, Prof *prof, bool capped) {
     const bool small = (K == 16);
     const int nlev = tf_levels(N);
     {   // level 0: single codebooks
@@ -446,7 +471,11 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
             // lists of 16 one-byte entries: the slot-major kernel (a 16-lane group of a gather = one table row: a fifth faster than
             // the lane-major one, profiles/r06_ab_pair0_slot_major.txt)
             if (!small) {
-                hipLaunchKernelGGL(k_tf_pair0s, grid, dim3(64), 0, st, G, idx_cur, w.E, L, B, N, K, keep, fin, nact);
+                if (capped)
+                    hipLaunchKernelGGL(k_tf_pair0s<true>, dim3(pass_grid(grid.x, true, kCapWave)), dim3(64), 0, st, G, idx_cur, w.E, L, B, N,
+                                       K, keep, fin, nact);
+                else
+                    hipLaunchKernelGGL(k_tf_pair0s<false>, grid, dim3(64), 0, st, G, idx_cur, w.E, L, B, N, K, keep, fin, nact);
                 done0 = true;
             }
         }
@@ -466,10 +495,15 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
         const int groups2 = N >> 3, per1 = 2, ntab1 = groups2 * per1 * per1;
         const unsigned pair_blocks = (unsigned)(B * (N / 4)), tab_blocks = (unsigned)(B * ntab1);
         const int ntab3 = fuse_l3 ? 16 : 1, per3 = fuse_l3 ? 4 : 1;
-        const dim3 grid(pair_blocks + tab_blocks + (fuse_l3 ? (unsigned)(B * ntab3) : 0u));
+        const unsigned vgrid = pair_blocks + tab_blocks + (fuse_l3 ? (unsigned)(B * ntab3) : 0u);
+        const dim3 grid(pass_grid(vgrid, capped, kCapWave));
         if (prof) prof->begin(CAT_LEVEL1_FUSED);
-        MCQ_TF_LAUNCH2((k_tf_level1<8, 8, CT>), (k_tf_level1<16, 16, CT>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, ntab1, per1, w.tabs[0],
-                       nact, pair_blocks, tab_blocks, ntab3, per3, w.tabs[1]);
+        if (capped)
+            MCQ_TF_LAUNCH2((k_tf_level1<8, 8, CT, true>), (k_tf_level1<16, 16, CT, true>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, ntab1,
+                           per1, w.tabs[0], nact, pair_blocks, tab_blocks, ntab3, per3, w.tabs[1], vgrid);
+        else
+            MCQ_TF_LAUNCH2((k_tf_level1<8, 8, CT>), (k_tf_level1<16, 16, CT>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, ntab1, per1, w.tabs[0],
+                           nact, pair_blocks, tab_blocks, ntab3, per3, w.tabs[1], vgrid);
         MCQ_LAUNCH_CHECK();
         if (prof) prof->end(CAT_LEVEL1_FUSED);
     } else if (N >= 4) {   // level 1: pairs of codebooks
@@ -513,7 +547,7 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
             cur ^= 1;
         }
         if (prof) prof->begin(cat_comb);
-        const int rc = launch_tf_comb<CT>(L.kc[v - 1], L.kc[v], w.E, L, B, N, v, keep, w.tabs[cur], fin, nact, st);
+        const int rc = launch_tf_comb<CT>(L.kc[v - 1], L.kc[v], w.E, L, B, N, v, keep, w.tabs[cur], fin, nact, st, capped);
         if (rc) return rc;
         if (prof) prof->end(cat_comb);
     }
@@ -541,9 +575,11 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
     if (chunk < B) chunk &= ~127L;
     const Prepared P = prepared_view(prepared, N, K, D);
     const int pack = (out_u8 != nullptr && K == 16 && N >= 2) ? 2 : 1;
-    // fixed-point skipping (opt-in): vectors whose indexes a pass leaves unchanged drop out of the later
-    // passes (k_compact); results are identical, the cost becomes data dependent
-    const bool skip = (flags & MCQ_ENCODE_SKIP_FIXED_POINTS) != 0 && iters >= 2;
+    // fixed-point skipping (the default; MCQ_ENCODE_ALL_PASSES turns it off): vectors whose indexes a pass leaves unchanged
+    // drop out of the later passes (k_compact) and their codes go straight to the caller's arrays; results are identical, the
+    // cost becomes data dependent.  Below skip_min_batch() vectors per chunk the passes are bound by the launch chain, and the
+    // compactions would only add launches to it
+    const bool want_skip = (flags & MCQ_ENCODE_ALL_PASSES) == 0 && iters >= 3;     // (with two passes the second one holds ~every vector)
 
     for (long lo = 0; lo < B; lo += chunk) {
         const long Bc = (B - lo < chunk) ? (B - lo) : chunk;
@@ -551,7 +587,6 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
         const int xh = (flags & MCQ_ENCODE_X_FP16) ? 1 : 0;   // rows of 2-byte elements
         const float *xc = xh ? reinterpret_cast<const float *>(reinterpret_cast<const uint16_t *>(x) + lo * D) : x + lo * D;
         int rc;
-        // the frames as limb planes (and |x|^2), once per call: both products of the call read them
         // the frames as limb planes, centered (x - mean: both products of the call read them; |x - mean|^2 rides along)
         if (init_idx == nullptr || iters > 0) {
             if (prof) prof->begin(CAT_XX);
@@ -578,11 +613,19 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
             if (rc) return rc;
             if (prof) prof->end(CAT_XC);
         }
+        // 16 or 8 codebooks of 16 entries (the trainer's first phase at 8 / 4 bytes per frame): ALL passes of the call in one launch of
+        // persistent workgroups that hold the Gram matrix in LDS (mcq_pass16_kernels.h); a wave leaves a vector at its fixed point
+        // by itself, without compaction.  Not under the profiler, whose categories are the separate launches
+        const bool use_p16 = sizeof(CT) == 1 && K == 16 && (N == 16 || N == 8) && iters > 0 && prof == nullptr && pass16_enabled();
+        const bool skip = want_skip && !use_p16 && Bc >= skip_min_batch();
         int iters_left = iters;
         // without skipping: indexes are refined in place in w.idx, nothing is packed
         CT *idx_cur = w.idx, *idx_new = skip ? w.idxB : w.idx, *idx_pk = w.idxC;
         const int *map_cur = nullptr, *nact = nullptr;
         int *map_nxt = w.map[0], *map_spare = w.map[1];
+        // E / R of the active slots; under skipping with E / R formed in the emit they move with the indexes into the packed
+        // slots, between w.E / w.R and a second pair in the Gram-terms buffer (which only the first pass's k_tf_gram_terms uses)
+        float *E_cur = w.E, *R_cur = w.R, *E_alt = w.gterms, *R_alt = w.gterms + ((Bc + 3) & ~3L);
         if (skip) {
             hipError_t e = hipMemsetAsync(w.cnt, 0, 64 * sizeof(int), st);
             if (e != hipSuccess) return (int)e;
@@ -590,10 +633,7 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
         }
         bool wrote_direct = false;
         if constexpr (sizeof(CT) == 1) {
-            // 16 or 8 codebooks of 16 entries (the trainer's first phase at 8 / 4 bytes per frame): ALL passes of the call in one launch of
-            // persistent workgroups that hold the Gram matrix in LDS (mcq_pass16_kernels.h); not under the profiler, whose
-            // categories are the separate launches
-            if (K == 16 && (N == 16 || N == 8) && iters > 0 && !skip && prof == nullptr && pass16_enabled()) {
+            if (use_p16) {
                 // (the dynamic LDS above 64 KB has to be allowed once per DEVICE: a process may drive several)
                 static bool allowed16[64] = {};
                 int dev = 0;
@@ -623,43 +663,55 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
             }
         }
         // E / R of pass it + 1 can be formed by the wave that emits the indexes of pass it (tf_emit), which saves that pass
-        // its two E / R launches: 4, 8 or 16 codebooks, no compaction of the vectors between the passes, not under the profiler
-        const bool er_in_emit = !skip && (N == 4 || N == 8 || N == 16);
+        // its two E / R launches (4, 8 or 16 codebooks); under skipping k_compact moves them into the packed slots
+        const bool er_in_emit = (N == 4 || N == 8 || N == 16);
         bool er_ready = false;
         for (int it = 0; it < iters_left; ++it) {
+            const bool last_pass = (it + 1 == iters);
+            // capped grids over the active vectors from the fourth pass on (passes 1-3 hold nearly every vector of an
+            // untrained batch, and the strided kernels cost the dense passes a few per cent: DESIGN.md section 4)
+            const bool capped = skip && it >= 3;
             if (!er_ready) {
                 if (prof) prof->begin(CAT_ER);
-                rc = launch_tf_er<CT>(N, P.G, w.XC, idx_cur, w.xx, Bc, K, w.E, w.R, w.gterms, nact, map_cur, st);
+                rc = launch_tf_er<CT>(N, P.G, w.XC, idx_cur, w.xx, Bc, K, E_cur, R_cur, w.gterms, nact, map_cur, st);
                 if (rc) return rc;
                 if (prof) prof->end(CAT_ER);
             }
             er_ready = false;
             if (prof) prof->begin(CAT_STAGE0);
-            rc = launch_tf_stage0(K, N, P.G, w.XC, idx_cur, w.R, P.Q, Bc, (N == 1) ? 1 : w.tf.kc[0], reinterpret_cast<CT *>(w.tf.ent),
-                                  w.tf.S[0], (N == 1) ? idx_new : static_cast<CT *>(nullptr), nact, map_cur, st);
+            rc = launch_tf_stage0(K, N, P.G, w.XC, idx_cur, R_cur, P.Q, Bc, (N == 1) ? 1 : w.tf.kc[0], reinterpret_cast<CT *>(w.tf.ent),
+                                  w.tf.S[0], (N == 1) ? idx_new : static_cast<CT *>(nullptr), nact, map_cur, st, capped);
             if (rc) return rc;
             if (prof) prof->end(CAT_STAGE0);
+            bool direct_out = false;
             if (N >= 2) {
-                // last pass, nothing to pack or to scatter back: the winners go straight to the caller's arrays (tf_emit)
+                // last pass: the winners go straight to the caller's arrays (tf_emit; under skipping to row map[slot])
                 TfLists L = w.tf;
-                if (er_in_emit && it + 1 < iters) {
-                    L.erG = P.G; L.erXC = w.XC; L.erxx = w.xx; L.erE = w.E; L.erR = w.R; L.erK = K;
+                L.map = map_cur;
+                if (er_in_emit && !last_pass) {
+                    L.erG = P.G; L.erXC = w.XC; L.erxx = w.xx; L.erE = E_cur; L.erR = R_cur; L.erK = K;
                     er_ready = true;
                 }
-                const bool direct_out = (it + 1 == iters) && !skip && pack == 1;
+                direct_out = last_pass;
                 if (direct_out) {
                     L.out_i64 = out_i64 ? out_i64 + lo * N : nullptr;
-                    L.out_u8 = out_u8 ? out_u8 + lo * N : (codes_also ? codes_also + lo * N : nullptr);
+                    L.out_u8 = out_u8 ? out_u8 + lo * (N / pack) : (codes_also ? codes_also + lo * N : nullptr);
+                    L.out_pack = out_u8 ? pack : 1;
                     wrote_direct = true;
                 }
-                rc = run_tf_combines<CT>(P.G, idx_cur, idx_new, w, L, Bc, N, K, nact, st, prof);
+                WorkspaceT<CT> wc = w;
+                wc.E = E_cur;
+                wc.R = R_cur;
+                rc = run_tf_combines<CT>(P.G, idx_cur, idx_new, wc, L, Bc, N, K, nact, st, prof, capped);
                 if (rc) return rc;
             }
-            if (skip) {
-                const int last = (it + 1 == iters) ? 1 : 0;
+            if (skip && !direct_out) {
                 if (prof) prof->begin(CAT_TAIL);
                 hipLaunchKernelGGL(k_compact<CT>, dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, idx_cur, idx_new,
-                                   map_cur, nact, Bc, N, last, w.final_idx, idx_pk, map_nxt, w.cnt + it);
+                                   map_cur, nact, Bc, N, last_pass ? 1 : 0, idx_pk, map_nxt, w.cnt + it,
+                                   er_ready ? E_cur : nullptr, er_ready ? R_cur : nullptr, E_alt, R_alt, pack,
+                                   out_u8 ? out_u8 + lo * (N / pack) : nullptr, out_i64 ? out_i64 + lo * N : nullptr,
+                                   codes_also ? codes_also + lo * N : nullptr);
                 MCQ_LAUNCH_CHECK();
                 if (prof) prof->end(CAT_TAIL);
                 // rotate: the packed list becomes the current one
@@ -668,13 +720,16 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
                 map_cur = map_nxt;
                 map_nxt = old_map ? old_map : map_spare;
                 nact = w.cnt + it;
+                if (er_ready) {
+                    std::swap(E_cur, E_alt);
+                    std::swap(R_cur, R_alt);
+                }
             }
         }
-        if (wrote_direct) continue;
-        const CT *result = (skip && iters > 0) ? w.final_idx : w.idx;
+        if (wrote_direct || skip) continue;      // (skipping: every vector left through k_compact or the last emit)
         const long outn = (out_i64 != nullptr) ? Bc * N : Bc * (N / pack);
         if (prof) prof->begin(CAT_TAIL);
-        hipLaunchKernelGGL(k_finalize<CT>, dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, st, result, Bc, N, pack,
+        hipLaunchKernelGGL(k_finalize<CT>, dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, st, w.idx, Bc, N, pack,
                            out_u8 ? out_u8 + lo * (N / pack) : nullptr, out_i64 ? out_i64 + lo * N : nullptr,
                            codes_also ? codes_also + lo * N : nullptr);
         MCQ_LAUNCH_CHECK();
@@ -1092,7 +1147,7 @@ int mcq_logits_refine_codes(const float *x, long B, const void *prepared, float 
     if (K > 256) return MCQ_EUNSUPPORTED;       // a trainer entry point (stored logits for the fused loss kernels): K <= 256
     if (B > 0 && (!logits_out || !idx_out)) return MCQ_EINVAL;
     return run_encode(x, B, prepared, lscale_exp, N, K, D, refine_iters, nullptr, idx_out, workspace, workspace_bytes,
-                      static_cast<hipStream_t>(stream), nullptr, nullptr, flags & ~MCQ_ENCODE_SKIP_FIXED_POINTS, logits_out,
+                      static_cast<hipStream_t>(stream), nullptr, nullptr, flags | MCQ_ENCODE_ALL_PASSES, logits_out,
                       codes_out);
 }
 
@@ -1386,7 +1441,8 @@ int mcq_profile_encode(const float *x, long B, const void *prepared, float lscal
         prof.stream = st;
         prof.only = only;
         rc = run_encode(x, B, prepared, lscale_exp, N, K, D, refine_iters, wide ? nullptr : dummy,
-                        wide ? reinterpret_cast<int64_t *>(dummy) : nullptr, workspace, workspace_bytes, st, &prof);
+                        wide ? reinterpret_cast<int64_t *>(dummy) : nullptr, workspace, workspace_bytes, st, &prof, nullptr,
+                        MCQ_ENCODE_ALL_PASSES);
         (void)hipStreamSynchronize(st);
         for (size_t i = 0; rc == 0 && i < prof.cat.size(); ++i) {
             float ms = 0.f;

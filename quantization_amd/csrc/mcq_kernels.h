@@ -565,27 +565,43 @@ __global__ void k_prepare_rows(const float *__restrict__ src, float scale, int a
 // ------------------------------------------------------- fixed-point skipping
 // _refine_indexes is a deterministic map F of (x, indexes): once F(idx) == idx every later pass
 // returns idx again, so such a vector can leave the active list without changing any result.
-// One thread per active slot: converged (or last pass) -> the indexes go to their original row of
-// `final_idx`; otherwise the slot is re-packed (order irrelevant: vectors are independent) for the
-// next pass.  `cnt_next` was zeroed by the host (memset node ahead of the launch).
+// One thread per active slot: converged (or last pass) -> the indexes go straight to the caller's
+// row orig = map_cur[s] of the output (int64 [+ bytes], bytes, or two 16-entry codes per byte);
+// otherwise the slot is re-packed (order irrelevant: vectors are independent) for the next pass,
+// with E / R of the next pass when the emitting wave formed them (E_in != nullptr).  `cnt_next` was
+// zeroed by the host (memset ahead of the first pass).
 template <typename CT>
 __global__ void k_compact(const CT *__restrict__ idx_old, const CT *__restrict__ idx_new,
                           const int *__restrict__ map_cur, const int *__restrict__ nact, long B, int N, int last,
-                          CT *__restrict__ final_idx, CT *__restrict__ idx_packed, int *__restrict__ map_next,
-                          int *__restrict__ cnt_next) {
+                          CT *__restrict__ idx_packed, int *__restrict__ map_next, int *__restrict__ cnt_next,
+                          const float *__restrict__ E_in, const float *__restrict__ R_in, float *__restrict__ E_out,
+                          float *__restrict__ R_out, int pack, uint8_t *__restrict__ out_u8, int64_t *__restrict__ out_i64,
+                          uint8_t *__restrict__ codes_also) {
     const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (nact) B = *nact;
     if (s >= B) return;
-    const int orig = map_cur ? map_cur[s] : (int)s;
+    const long orig = map_cur ? (long)map_cur[s] : s;
     bool changed = false;
     if (!last)
         for (int n = 0; n < N; ++n) changed = changed || (idx_old[s * N + n] != idx_new[s * N + n]);
     if (changed) {
-        const int slot = atomicAdd(cnt_next, 1);
-        for (int n = 0; n < N; ++n) idx_packed[(long)slot * N + n] = idx_new[s * N + n];
-        map_next[slot] = orig;
+        const long slot = atomicAdd(cnt_next, 1);
+        for (int n = 0; n < N; ++n) idx_packed[slot * N + n] = idx_new[s * N + n];
+        map_next[slot] = (int)orig;
+        if (E_in != nullptr) {
+            E_out[slot] = E_in[s];
+            for (int n = 0; n < N; ++n) R_out[slot * N + n] = R_in[s * N + n];
+        }
+    } else if (out_i64 != nullptr) {
+        for (int n = 0; n < N; ++n) {
+            const CT v = idx_new[s * N + n];
+            out_i64[orig * N + n] = v;
+            if (codes_also) codes_also[orig * N + n] = (uint8_t)v;
+        }
+    } else if (pack == 1) {
+        for (int n = 0; n < N; ++n) out_u8[orig * N + n] = (uint8_t)idx_new[s * N + n];
     } else {
-        for (int n = 0; n < N; ++n) final_idx[(long)orig * N + n] = idx_new[s * N + n];
+        for (int n = 0; n < N; n += 2) out_u8[orig * (N / 2) + n / 2] = (uint8_t)(idx_new[s * N + n] + 16 * idx_new[s * N + n + 1]);
     }
 }
 

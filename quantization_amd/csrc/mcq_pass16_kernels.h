@@ -133,6 +133,7 @@ k_tf_pass16(Pass16Args a) {
         for (int r = 0; r < XS; ++r) xcv[r] = a.XC[(size_t)b * NK + 64 * r + lane];
         int e = lane < N ? (int)a.idx[b * N + lane] & 15 : 0;
         const float xxb = a.xx[b];
+        bool converged = false;
         for (int pass = 0; pass < a.iters; ++pass) {
             // ---------------------------------------------------------------- E, R (the arithmetic of tf_er_wave)
             float E, Rv;
@@ -358,9 +359,12 @@ k_tf_pass16(Pass16Args a) {
                     p = pos1[((n >> 1) * 8 + p) * 2 + (n & 1)];                               // -> level-0 list of codebook n
                     en = ent0[n * 8 + p];
                 }
+                // a pass is a deterministic map of (x, indexes): once it returns its input, every later pass would too
+                converged = __ballot(lane < N && en != e) == 0;
                 e = en;
             }
             wave_lds_fence();
+            if (converged) break;
         }
         if (lane < N) {
             a.idx[b * N + lane] = (uint8_t)e;

@@ -38,6 +38,10 @@ struct TfLists {
     // to the caller's arrays (int64 [B][N] and / or uint8 [B][N]) and the encode tail needs no launch of its own
     int64_t *out_i64;
     uint8_t *out_u8;
+    int out_pack;               // 2: out_u8 holds two 16-entry codes per byte (low nibble = even codebook), 1: one code per byte
+    // fixed-point skipping: slot b of the pass holds the vector of row map[b] of the call (XC, xx, the caller's arrays);
+    // nullptr: slot b is row b
+    const int *map;
     // set for every pass but the last: the wave that emits a vector's new indexes also forms E and R[n] of the NEXT pass from
     // them (tf_er_wave: the arithmetic of k_tf_er), so that pass needs neither k_tf_gram_terms nor k_tf_er
     const float *erG, *erXC, *erxx;
@@ -163,11 +167,11 @@ k_tf_er(const float *__restrict__ gterms, const float *__restrict__ XC, const CT
 // One wave per (vector, codebook n): the K scores of :418 from N - 1 row segments of G, the vector's XC segment and
 // Q, then the first sort-and-truncate (:470-503).  Workgroup id mod N = n: an XCD's L2 holds G[:, segment n] only.
 template <int K, int N>
-__global__ void __launch_bounds__(256)
-k_tf_stage0(const float *__restrict__ G, const float *__restrict__ XC, const tf_code_of<K> *__restrict__ idx,
-            const float *__restrict__ R, const float *__restrict__ Q, long B, int keep,
-            tf_code_of<K> *__restrict__ ent_out, float *__restrict__ S_out, tf_code_of<K> *__restrict__ idx_final /* N == 1 */,
-            const int *__restrict__ nact, const int *__restrict__ map) {
+__device__ __forceinline__ void
+tf_stage0_body(unsigned bid, unsigned vgrid, const float *__restrict__ G, const float *__restrict__ XC, const tf_code_of<K> *__restrict__ idx,
+               const float *__restrict__ R, const float *__restrict__ Q, long B, int keep,
+               tf_code_of<K> *__restrict__ ent_out, float *__restrict__ S_out, tf_code_of<K> *__restrict__ idx_final /* N == 1 */,
+               const int *__restrict__ nact, const int *__restrict__ map) {
     using CT = tf_code_of<K>;
     constexpr int CB = (int)sizeof(CT);
     constexpr int VPL = (K >= 64) ? K / 64 : 1;
@@ -182,13 +186,13 @@ k_tf_stage0(const float *__restrict__ G, const float *__restrict__ XC, const tf_
     int n;
     long b;
     if constexpr (N > 8) {
-        const unsigned per_phase = gridDim.x / (N / 8);
-        const unsigned ph = blockIdx.x / per_phase, r = blockIdx.x - ph * per_phase;
+        const unsigned per_phase = vgrid / (N / 8);
+        const unsigned ph = bid / per_phase, r = bid - ph * per_phase;
         n = (int)(r & 7u) + 8 * (int)ph;
         b = (long)(r >> 3) * 4 + (threadIdx.x >> 6);
     } else {
-        n = blockIdx.x & (N - 1);
-        b = (long)(blockIdx.x / N) * 4 + (threadIdx.x >> 6);
+        n = bid & (N - 1);
+        b = (long)(bid / N) * 4 + (threadIdx.x >> 6);
     }
     if (b >= B) return;
     const int lane = lane_id();
@@ -276,7 +280,7 @@ k_tf_stage0(const float *__restrict__ G, const float *__restrict__ XC, const tf_
     bool has;
     wave_select_set<VPL>(sv, sp, keep, K, sel[threadIdx.x >> 6], has, dst, ov, op);
     stp.at(2);                                  // selection done
-    stp.flush(0, blockIdx.x, 16);
+    stp.flush(0, bid, 16);
     if (N == 1) {                                             // the best entry is the result (:468-469)
         if (lane == 0) idx_final[b] = (CT)op;
         return;
@@ -284,6 +288,31 @@ k_tf_stage0(const float *__restrict__ G, const float *__restrict__ XC, const tf_
     if (has) {                                                // the list in ascending entry: every survivor from the lane that holds it
         ent_out[(b * N + n) * keep + dst] = (CT)op;
         S_out[(b * N + n) * keep + dst] = ov;
+    }
+}
+
+// STRIDED (fixed-point skipping, later passes): a capped launch of gridDim.x <= vgrid workgroups walks the virtual workgroups
+// that hold active vectors (the first *nact slots) in strides of gridDim.x, a multiple of 8, so that virtual id mod 8 -- the
+// XCD of the full launch -- is the XCD that runs it.  The loop costs the dense passes 3-7 % per kernel (measured), so they
+// keep the plain form: one workgroup per virtual id, the empty ones returning at once.
+template <int K, int N, bool STRIDED = false>
+__global__ void __launch_bounds__(256)
+k_tf_stage0(const float *__restrict__ G, const float *__restrict__ XC, const tf_code_of<K> *__restrict__ idx,
+            const float *__restrict__ R, const float *__restrict__ Q, long B, int keep,
+            tf_code_of<K> *__restrict__ ent_out, float *__restrict__ S_out, tf_code_of<K> *__restrict__ idx_final /* N == 1 */,
+            const int *__restrict__ nact, const int *__restrict__ map, unsigned vgrid) {
+    if constexpr (!STRIDED) {
+        tf_stage0_body<K, N>(blockIdx.x, gridDim.x, G, XC, idx, R, Q, B, keep, ent_out, S_out, idx_final, nact, map);
+        return;
+    }
+    // (N > 8: the virtual launch is phase-major, ph * per_phase + r; the active part of every phase is its first `nr` ids)
+    const unsigned per = (N > 8) ? vgrid / (N / 8) : vgrid;
+    const unsigned nr = nact ? (unsigned)((*nact + 3) / 4) * (N > 8 ? 8u : (unsigned)N) : per;
+    const unsigned need = (N > 8) ? nr * (N / 8) : nr;
+    for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
+        const unsigned vb = (N > 8) ? (c / nr) * per + c % nr : c;
+        tf_stage0_body<K, N>(vb, vgrid, G, XC, idx, R, Q, B, keep, ent_out, S_out, idx_final, nact, map);
+        wave_lds_fence();
     }
 }
 
@@ -419,10 +448,10 @@ __device__ __forceinline__ void tf_leaf(const float *__restrict__ G, int NK, int
 // own (not inlined: the three instantiations inside every last-combine kernel sent the compiler's CFG simplification into
 // a crash).
 __device__ __attribute__((noinline)) void tf_er_next(const float *G, const float *XC, const float *xx, int K, float *E, float *R,
-                                                     long b, int N, int e) {
-    if (N == 8) tf_er_wave<8, true, uint8_t>(b, b, nullptr, e, nullptr, G, XC, xx, K, E, R);
-    else if (N == 4) tf_er_wave<4, true, uint8_t>(b, b, nullptr, e, nullptr, G, XC, xx, K, E, R);
-    else if (N == 16) tf_er_wave<16, true, uint8_t>(b, b, nullptr, e, nullptr, G, XC, xx, K, E, R);
+                                                     long b, long bx, int N, int e) {
+    if (N == 8) tf_er_wave<8, true, uint8_t>(b, bx, nullptr, e, nullptr, G, XC, xx, K, E, R);
+    else if (N == 4) tf_er_wave<4, true, uint8_t>(b, bx, nullptr, e, nullptr, G, XC, xx, K, E, R);
+    else if (N == 16) tf_er_wave<16, true, uint8_t>(b, bx, nullptr, e, nullptr, G, XC, xx, K, E, R);
 }
 
 // The winner's leaves, codebook by codebook (:468-469): lane n walks down the position tree.
@@ -443,10 +472,19 @@ __device__ __forceinline__ void tf_emit(const TfLists &L, long b, int N, int nle
         }
         e = reinterpret_cast<const CT *>(L.ent)[(b * N + n) * L.kc[0] + p];
         idx_out[b * N + n] = (CT)e;
-        if (L.out_i64) L.out_i64[b * N + n] = e;
-        if (L.out_u8) L.out_u8[b * N + n] = (uint8_t)e;      // (one-byte entries only: the host leaves it null otherwise)
     }
-    if (L.erE) tf_er_next(L.erG, L.erXC, L.erxx, L.erK, L.erE, L.erR, b, N, e);      // E, R[n] of the next pass, from the indexes in lanes 0 .. N - 1
+    // the caller's row of this slot (fixed-point skipping packs the active vectors into the first slots)
+    const long row = (L.map && (L.out_i64 || L.out_u8 || L.erE)) ? (long)L.map[b] : b;
+    if (L.out_i64 && n < N) L.out_i64[row * N + n] = e;
+    if (L.out_u8) {                                           // (one-byte entries only: the host leaves it null otherwise)
+        if (L.out_pack == 2) {                                // 16-entry codes: even lane n writes code n + 16 * code n + 1
+            const int hi = __builtin_amdgcn_ds_bpermute(((n + 1) & 63) << 2, e);
+            if (n < N && (n & 1) == 0) L.out_u8[row * (N / 2) + n / 2] = (uint8_t)(e + 16 * hi);
+        } else if (n < N) {
+            L.out_u8[row * N + n] = (uint8_t)e;
+        }
+    }
+    if (L.erE) tf_er_next(L.erG, L.erXC, L.erxx, L.erK, L.erE, L.erR, b, row, N, e);   // E, R[n] of the next pass, from the indexes in lanes 0 .. N - 1
 }
 
 // select `keep` of the wave's scores and write the next level's list (or, for the last combine, the result)
@@ -527,16 +565,16 @@ k_tf_pair0(const float *__restrict__ G, const CT *__restrict__ idx, const float 
 // load, the lane takes byte l / 16), the scores of a list reach the lanes as one coalesced load and four ds_bpermute, the border
 // lanes reuse the column entry they hold.  Same expressions, same values; the list leaves in ascending position as ever
 // (wave_select_set<kSlotMajor>).
-__global__ void __launch_bounds__(64)
-k_tf_pair0s(const float *__restrict__ G, const uint8_t *__restrict__ idx, const float *__restrict__ E, TfLists L, long B,
-            int N, int K, int keep, uint8_t *__restrict__ idx_final, const int *__restrict__ nact) {
+__device__ __forceinline__ void
+tf_pair0s_body(unsigned bid, const float *__restrict__ G, const uint8_t *__restrict__ idx, const float *__restrict__ E, const TfLists &L,
+               long B, int N, int K, int keep, uint8_t *__restrict__ idx_final, const int *__restrict__ nact) {
     constexpr int KC = 16, VPL = 4;
     __shared__ u64 scratch[kSelectLdsU64];
     Stamps stp;
     if (nact) B = *nact;
     const int Gout = N >> 1;
-    const int g = (int)(blockIdx.x & (unsigned)(Gout - 1));
-    const long b = (long)(blockIdx.x >> __builtin_ctz((unsigned)Gout));
+    const int g = (int)(bid & (unsigned)(Gout - 1));
+    const long b = (long)(bid >> __builtin_ctz((unsigned)Gout));
     if (b >= B) return;
     const int lane = lane_id();
     const int n = 2 * g, m = n + 1;
@@ -581,7 +619,23 @@ k_tf_pair0s(const float *__restrict__ G, const uint8_t *__restrict__ idx, const 
     stp.at(2);                                  // leaf table gathered, scores formed
     tf_finish<VPL, uint8_t, kSlotMajor>(sv, sp, keep, KC, scratch, L, 1, b, N, g, idx_final);
     stp.at(3);                                  // selection done, list written
-    stp.flush(1, blockIdx.x, 64);
+    stp.flush(1, bid, 64);
+}
+
+template <bool STRIDED = false>
+__global__ void __launch_bounds__(64)
+k_tf_pair0s(const float *__restrict__ G, const uint8_t *__restrict__ idx, const float *__restrict__ E, TfLists L, long B,
+            int N, int K, int keep, uint8_t *__restrict__ idx_final, const int *__restrict__ nact) {
+    if constexpr (!STRIDED) {
+        tf_pair0s_body(blockIdx.x, G, idx, E, L, B, N, K, keep, idx_final, nact);
+        return;
+    }
+    // (capped grid: see k_tf_stage0)
+    const unsigned need = nact ? (unsigned)*nact * (unsigned)(N >> 1) : gridDim.x;
+    for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
+        tf_pair0s_body(c, G, idx, E, L, B, N, K, keep, idx_final, nact);
+        wave_lds_fence();
+    }
 }
 
 // ------------------------------------------------------------ level-1 tables
@@ -876,15 +930,34 @@ k_tf_table1(const float *__restrict__ G, const CT *__restrict__ idx, TfLists L, 
 // The sibling combines of level 1 and the cousin tables the level-2 combine needs, in ONE launch: both read the level-1 lists
 // and nothing of each other; the workgroup-to-XCD mapping of both kinds is what it is in their own launches (the pair
 // blocks are a multiple of 8).
-template <int KCH, int KC, typename CT = uint8_t>
+template <int KCH, int KC, typename CT = uint8_t, bool STRIDED = false>
 __global__ void __launch_bounds__(64)
 k_tf_level1(const float *__restrict__ G, const CT *__restrict__ idx, const float *__restrict__ E, TfLists L, long B, int N,
             int K, int keep, int ntab, int per, float *__restrict__ tabs, const int *__restrict__ nact, unsigned pair_blocks,
-            unsigned tab_blocks, int ntab2, int per2, float *__restrict__ tabs2) {
+            unsigned tab_blocks, int ntab2, int per2, float *__restrict__ tabs2, unsigned vgrid) {
     __shared__ __attribute__((aligned(16))) float leaf[tf_leaf_lds_floats(KCH, sizeof(CT))];
-    if (blockIdx.x < pair_blocks) tf_pair1_body<KCH, KC, CT>(blockIdx.x, leaf, G, idx, E, L, B, N, K, keep, nullptr, nact);
-    else if (blockIdx.x < pair_blocks + tab_blocks) tf_table1_body<KCH, KC, CT>(blockIdx.x - pair_blocks, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
-    else tf_table1_body<KCH, KC, CT>(blockIdx.x - pair_blocks - tab_blocks, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);   // (16 codebooks: the tables of level 3 as well)
+    if constexpr (!STRIDED) {
+        if (blockIdx.x < pair_blocks) tf_pair1_body<KCH, KC, CT>(blockIdx.x, leaf, G, idx, E, L, B, N, K, keep, nullptr, nact);
+        else if (blockIdx.x < pair_blocks + tab_blocks) tf_table1_body<KCH, KC, CT>(blockIdx.x - pair_blocks, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
+        else tf_table1_body<KCH, KC, CT>(blockIdx.x - pair_blocks - tab_blocks, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);   // (16 codebooks: the tables of level 3 as well)
+        return;
+    }
+    // (capped grid: see k_tf_stage0.  The active ids of each of the three ranges, rounded up to a multiple of 8: a range's
+    // virtual id mod 8 stays that of the compact id as long as the full ranges are multiples of 8, as they are at the bench
+    // shape; the ids past the active vectors return at once)
+    unsigned r0 = pair_blocks, r1 = tab_blocks, r2 = vgrid - pair_blocks - tab_blocks;
+    if (nact) {
+        const unsigned na = (unsigned)*nact;
+        r0 = (na * (unsigned)(N / 4) + 7u) & ~7u;
+        r1 = (na * (unsigned)ntab + 7u) & ~7u;
+        r2 = r2 ? na * (unsigned)ntab2 : 0u;
+    }
+    for (unsigned c = blockIdx.x; c < r0 + r1 + r2; c += gridDim.x) {
+        if (c < r0) tf_pair1_body<KCH, KC, CT>(c, leaf, G, idx, E, L, B, N, K, keep, nullptr, nact);
+        else if (c < r0 + r1) tf_table1_body<KCH, KC, CT>(c - r0, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
+        else tf_table1_body<KCH, KC, CT>(c - r0 - r1, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);   // (16 codebooks: the tables of level 3 as well)
+        wave_lds_fence();
+    }
 }
 
 // copy COUNT tables of KH x KH floats each from global memory (rows of KH) to LDS (rows of KH + 1: the odd row stride keeps the
@@ -988,9 +1061,9 @@ k_tf_up(TfLists L, long B, int N, int u, int ntab, int per, const float *__restr
 // running arg-min over the scores, no score array and no selection: 86 registers -> the 8 waves per SIMD of the other pass kernels
 // (k_tf_comb<16,32> is the last launch of every pass of 8 codebooks).
 template <int KH, int KC, bool LAST, typename CT = uint8_t>
-__global__ void __launch_bounds__(64)
-k_tf_comb(const float *__restrict__ E, TfLists L, long B, int N, int v, int keep, const float *__restrict__ tabs,
-          CT *__restrict__ idx_final, const int *__restrict__ nact) {
+__device__ __forceinline__ void
+tf_comb_body(unsigned bid, const float *__restrict__ E, const TfLists &L, long B, int N, int v, int keep, const float *__restrict__ tabs,
+             CT *__restrict__ idx_final, const int *__restrict__ nact) {
     constexpr int MH = KH * KH, RS = KH + 1, TS = tf_tab_stride<KH>();
     constexpr int VPL = (KC * KC / 64 <= 16) ? KC * KC / 64 : 16;
     constexpr int CHUNKS = KC * KC / (64 * VPL);
@@ -1003,8 +1076,8 @@ k_tf_comb(const float *__restrict__ E, TfLists L, long B, int N, int v, int keep
     u64 *sel2 = sel2_store;
     if (nact) B = *nact;
     const int Gout = N >> (v + 1);
-    const int h = (int)(blockIdx.x & (unsigned)(Gout - 1));
-    const long b = (long)(blockIdx.x >> __builtin_ctz((unsigned)Gout));
+    const int h = (int)(bid & (unsigned)(Gout - 1));
+    const long b = (long)(bid >> __builtin_ctz((unsigned)Gout));
     if (b >= B) return;
     const int lane = lane_id();
     const int P = 2 * h, Q = P + 1, Gv = N >> v;
@@ -1078,6 +1151,22 @@ k_tf_comb(const float *__restrict__ E, TfLists L, long B, int N, int v, int keep
         wave_lexmin(bv, bp);
         if (bp > KC * KC - 1) bp = KC * KC - 1;                  // only reachable with NaN keys
         tf_emit(L, b, N, v + 1, bp, idx_final);                   // keep == 1, last combine
+    }
+}
+
+template <int KH, int KC, bool LAST, typename CT = uint8_t, bool STRIDED = false>
+__global__ void __launch_bounds__(64)
+k_tf_comb(const float *__restrict__ E, TfLists L, long B, int N, int v, int keep, const float *__restrict__ tabs,
+          CT *__restrict__ idx_final, const int *__restrict__ nact) {
+    if constexpr (!STRIDED) {
+        tf_comb_body<KH, KC, LAST, CT>(blockIdx.x, E, L, B, N, v, keep, tabs, idx_final, nact);
+        return;
+    }
+    // (capped grid: see k_tf_stage0)
+    const unsigned need = nact ? (unsigned)*nact * (unsigned)(N >> (v + 1)) : gridDim.x;
+    for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
+        tf_comb_body<KH, KC, LAST, CT>(c, E, L, B, N, v, keep, tabs, idx_final, nact);
+        wave_lds_fence();
     }
 }
 

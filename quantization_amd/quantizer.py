@@ -100,9 +100,10 @@ class Quantizer(nn.Module):
         id_bytes = binascii.b2a_hex(os.urandom(4))           # quantization.py:53-55
         self.id_str = id_bytes.decode("utf-8")
         self.register_buffer("id_buf", torch.tensor(list(id_bytes), dtype=torch.uint8))
-        # opt-in (not in the reference): vectors whose indexes a refinement pass leaves unchanged are
-        # final (the pass is a deterministic map) and skip the remaining passes; same codes, less work
-        self.skip_fixed_points = False
+        # (not in the reference) vectors whose indexes a refinement pass leaves unchanged are final (the
+        # pass is a deterministic map) and skip the remaining passes; same codes, less work.  On by
+        # default; False runs every pass on every vector (MCQ_ENCODE_ALL_PASSES)
+        self.skip_fixed_points = True
         self._pinned_scales = None   # pin_scale_factors()
         self._prep = None       # (key, device buffer) of derived state for the kernels
         self._ws = None         # cached encode workspace (device uint8 tensor)
@@ -315,7 +316,7 @@ class Quantizer(nn.Module):
             rc = L.mcq_encode_ex(x2d.data_ptr(), B, blob.data_ptr(), self._lscale_exp, N, K, D, int(iters),
                                  out.data_ptr() if as_bytes else None, None if as_bytes else out.data_ptr(),
                                  ws.data_ptr(), ws.numel(), st,
-                                 (1 if getattr(self, "skip_fixed_points", False) else 0) | self._scale_flags |
+                                 (0 if getattr(self, "skip_fixed_points", True) else _lib.MCQ_ENCODE_ALL_PASSES) | self._scale_flags |
                                  (4 if x_fp16 else 0))
         _lib.check(rc, "mcq_encode")
         return out
