@@ -626,9 +626,9 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
         // E / R of the active slots; under skipping with E / R formed in the emit they move with the indexes into the packed
         // slots, between w.E / w.R and a second pair in the Gram-terms buffer (which only the first pass's k_tf_gram_terms uses)
         float *E_cur = w.E, *R_cur = w.R, *E_alt = w.gterms, *R_alt = w.gterms + ((Bc + 3) & ~3L);
-        if (skip) {
-            hipError_t e = hipMemsetAsync(w.cnt, 0, 64 * sizeof(int), st);
-            if (e != hipSuccess) return (int)e;
+        if (skip) {     // (a kernel, not hipMemsetAsync: replays of a captured encode have to clear them too, LAB_NOTEBOOK.md)
+            hipLaunchKernelGGL(k_zero_counts, dim3(1), dim3(64), 0, st, w.cnt, 64);
+            MCQ_LAUNCH_CHECK();
             if (prof) prof->untimed();
         }
         bool wrote_direct = false;

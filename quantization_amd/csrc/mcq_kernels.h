@@ -563,13 +563,18 @@ __global__ void k_prepare_rows(const float *__restrict__ src, float scale, int a
 // (the inner-product tables of the path -- logits, x.C, the Gram matrix -- are formed by mcq_fix_kernels.h)
 
 // ------------------------------------------------------- fixed-point skipping
+// the pass counters of a chunk (active vectors after each pass), zeroed ahead of its first pass
+__global__ void __launch_bounds__(64) k_zero_counts(int *__restrict__ cnt, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) cnt[i] = 0;
+}
+
 // _refine_indexes is a deterministic map F of (x, indexes): once F(idx) == idx every later pass
 // returns idx again, so such a vector can leave the active list without changing any result.
 // One thread per active slot: converged (or last pass) -> the indexes go straight to the caller's
 // row orig = map_cur[s] of the output (int64 [+ bytes], bytes, or two 16-entry codes per byte);
 // otherwise the slot is re-packed (order irrelevant: vectors are independent) for the next pass,
 // with E / R of the next pass when the emitting wave formed them (E_in != nullptr).  `cnt_next` was
-// zeroed by the host (memset ahead of the first pass).
+// zeroed by k_zero_counts ahead of the first pass.
 template <typename CT>
 __global__ void k_compact(const CT *__restrict__ idx_old, const CT *__restrict__ idx_new,
                           const int *__restrict__ map_cur, const int *__restrict__ nact, long B, int N, int last,
