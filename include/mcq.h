@@ -207,7 +207,9 @@ int mcq_loss_bwd(const float *logits, const int64_t *idx, const float *lse, long
  *   sums = {sum err^2, sum (x-mean)^2, sum_n chosen_sum[n], total batch size}  (all-reduced in DP training)
  *   losses[4] = rel_reconstruction, logprob, logits_entropy, index_entropy losses;
  *   g[2] = d total / d sums[0], d total / d sums[2];  g_prob[N][K] = d total / d prob_sum
- * (g[1] and g_prob feed mcq_loss_bwd; 2 * g[0] scales mcq_decode_backward(err)).                */
+ * (g[1] and g_prob feed mcq_loss_bwd; 2 * g[0] scales mcq_decode_backward(err)).
+ * N is at most 64 here and in mcq_loss_head_tail (the per-codebook entropies live in shared memory): MCQ_EUNSUPPORTED
+ * past that, before any pointer is looked at.                                                      */
 int mcq_loss_tail(const float *sums, const float *prob_sum, const float *count, int N, int K, float entropy_scale,
                   float *losses, float *g, float *g_prob, void *stream);
 

@@ -1213,7 +1213,7 @@ int mcq_loss_bwd(const float *logits, const int64_t *idx, const float *lse, long
 
 int mcq_loss_tail(const float *sums, const float *prob_sum, const float *count, int N, int K, float entropy_scale,
                   float *losses, float *g, float *g_prob, void *stream) {
-    if (!is_pow2(K) || K < 16 || K > 256 || N < 1) return MCQ_EUNSUPPORTED;
+    if (!is_pow2(K) || K < 16 || K > 256 || N < 1 || N > 64) return MCQ_EUNSUPPORTED;     // (s_hl / s_hi of loss_tail_body: 64)
     if (!sums || !prob_sum || !count || !losses || !g || !g_prob) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_loss_tail, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), sums, prob_sum, count, N, K,
                        entropy_scale, losses, g, g_prob);
@@ -1307,7 +1307,7 @@ int mcq_adam_step(float *p, const float *g, float *m, float *v, long n, double l
 int mcq_loss_head_tail(const float *num_part, const float *den_part, long nparts, const float *chosen_n, int N, float batch,
                        float *head, const float *prob_sum, const float *count, int K, float entropy_scale, float *losses,
                        float *g, float *g_prob, void *stream) {
-    if (!is_pow2(K) || K < 16 || K > 256 || N < 1) return MCQ_EUNSUPPORTED;
+    if (!is_pow2(K) || K < 16 || K > 256 || N < 1 || N > 64) return MCQ_EUNSUPPORTED;     // (as mcq_loss_tail)
     if (nparts <= 0 || !num_part || !den_part || !chosen_n || !head || !prob_sum || !count || !losses || !g || !g_prob) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_loss_head_tail, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), num_part, den_part, nparts,
                        chosen_n, N, batch, head, prob_sum, count, K, entropy_scale, losses, g, g_prob);

@@ -58,6 +58,12 @@ def test_argument_validation_without_launch():
     assert L.mcq_decode_backward_u8_ex(None, None, 4, 4, 512, 64, None, None, None, 1.0, None, None, None) == m.MCQ_EUNSUPPORTED
     assert L.mcq_decode_backward_u8(None, None, 4, 4, 256, 64, None, None) == m.MCQ_EINVAL
     assert L.mcq_loss_fwd(None, None, 4, 4, 512, None, None, None, None, None, 0, None) == m.MCQ_EUNSUPPORTED
+    # the loss tail keeps one entropy pair per codebook in shared memory: N > 64 is refused before any pointer is read
+    assert L.mcq_loss_tail(None, None, None, 65, 256, 1.0, None, None, None, None) == m.MCQ_EUNSUPPORTED
+    assert L.mcq_loss_tail(None, None, None, 1 << 20, 16, 1.0, None, None, None, None) == m.MCQ_EUNSUPPORTED
+    assert L.mcq_loss_tail(None, None, None, 64, 256, 1.0, None, None, None, None) == m.MCQ_EINVAL
+    assert L.mcq_loss_head_tail(None, None, 1, None, 65, 1.0, None, None, None, 16, 1.0, None, None, None, None) == m.MCQ_EUNSUPPORTED
+    assert L.mcq_loss_head_tail(None, None, 1, None, 64, 1.0, None, None, None, 16, 1.0, None, None, None, None) == m.MCQ_EINVAL
     assert L.mcq_profile_encode(None, 4, None, 1.0, 8, 256, 64, 1, None, 0, None, None, None, 0) == m.MCQ_EINVAL     # no output array
 
 
