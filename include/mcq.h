@@ -288,6 +288,37 @@ int mcq_scatter_rows(const float *grad, long stride_b, long stride_n, const int6
 int mcq_decode_backward_u8(const float *grad_out, const uint8_t *codes, long B, int N, int K, int D, float *gC,
                            void *stream);
 
+/* ---- search over stored codes ----------------------------------------------------
+ * (not in the reference) Which stored vectors are nearest to a query, answered from the codes without decoding them.
+ * The quantizer is additive, x^_b = sum_n C[n][code[b][n]], so
+ *     |q - x^_b|^2 = |q|^2 + sum_n T_q[n][code[b][n]] + t_b,    T_q[n][k] = -2 <q, C[n][k]>,    t_b = |x^_b|^2:
+ * one table of N*K floats per query, one float per stored vector (formed once per store), N additions per (query, candidate).
+ * One-byte codes only: K <= 256 (MCQ_EUNSUPPORTED past that, as at the trainer's entry points), 1 <= k <= 64 (k > 64:
+ * MCQ_EUNSUPPORTED), B <= 2^31 - 1.  `prepared` of either flavour (the decode-only state is enough).
+ * The contract (the tests restate rules 3 and 4 in numpy and compare bit for bit):
+ *   1. tables[q][n*K + k] = -2 * sum_d q[d] * C[n][k][d]: one fp32 chain over d ascending (each product rounded, then added);
+ *      fp16 queries widen to fp32 first.
+ *   2. norms[b] = sum_d (sum_n C[n][code[b][n]][d])^2 in fp32: rows added n ascending, then 64 per-lane chains and the xor
+ *      butterfly; a code digit is masked with K - 1 as mcq_decode does.
+ *   3. score[q][b] = (((T[c_0] + T[c_1]) + ...) + T[c_{N-1}]) + norms[b]: fp32 additions in exactly this order.
+ *   4. per query the k candidates smallest under "(score, b) ascending" -- the lower position wins a tie --, listed in that
+ *      order; fewer than k candidates: the tail is (+inf, -1).
+ *   5. no floating-point atomics: the same inputs give the same bits.  A non-finite query or norm neither faults nor hangs; its
+ *      row of results is unspecified.
+ * mcq_search_tables: q fp32 or (q_is_fp16 != 0) IEEE fp16 [Q][D] -> tables_out float[Q][N*K].
+ * mcq_code_norms: codes uint8 [B][N], one per codebook (unpacked) -> norms_out float[B].
+ * mcq_search_scan: tables float[Q][N*K], codes uint8 [B][N] aligned to min(N, 16) bytes (MCQ_EINVAL otherwise), norms float[B]
+ *   -> out_score float[Q][k], out_index int64[Q][k].  workspace >= mcq_search_workspace_bytes(Q, B, N, K, k): partial lists
+ *   only (k entries per query and slice of the store); it does not depend on D and stops growing with B once the slice count
+ *   reaches its cap.  Q == 0 or B == 0 return 0 after filling the outputs as rule 4 says.  Everything is rejected before
+ *   anything touches the device.                                                                                       */
+int mcq_search_tables(const void *q, int q_is_fp16, long Q, const void *prepared, int N, int K, int D, float *tables_out,
+                      void *stream);
+int mcq_code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *norms_out, void *stream);
+size_t mcq_search_workspace_bytes(long Q, long B, int N, int K, int k);
+int mcq_search_scan(const float *tables, long Q, const uint8_t *codes, const float *norms, long B, int N, int K, int k,
+                    float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- test / profiling hooks -------------------------------------------------
  * Logits of Quantizer._logits (:277-279) for a batch, fp32 [B][N*K]; used by the
  * parity tests to localise a divergence.                                       */

@@ -21,6 +21,7 @@ SYMBOLS = (
     "mcq_jcl_prefix_fwd", "mcq_jcl_prefix_bwd", "mcq_scatter_rows", "mcq_decode_backward_u8",
     "mcq_weight_grad", "mcq_weight_grad_workspace_bytes", "mcq_adam_step", "mcq_loss_head", "mcq_loss_head_tail", "mcq_scales_exp",
     "mcq_decode_backward_waves", "mcq_decode_backward_u8_ex", "mcq_loss_bwd_waves", "mcq_loss_bwd_ex", "mcq_grad_tail",
+    "mcq_search_tables", "mcq_code_norms", "mcq_search_workspace_bytes", "mcq_search_scan",
 )
 
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
@@ -121,6 +122,14 @@ def lib():
     L.mcq_loss_bwd_ex.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
     L.mcq_grad_tail.restype = i32
     L.mcq_grad_tail.argtypes = [vp, i64, vp, vp, f32, vp, i64, f32, vp, vp, vp]
+    L.mcq_search_tables.restype = i32
+    L.mcq_search_tables.argtypes = [vp, i32, i64, vp, i32, i32, i32, vp, vp]
+    L.mcq_code_norms.restype = i32
+    L.mcq_code_norms.argtypes = [vp, i64, vp, i32, i32, i32, vp, vp]
+    L.mcq_search_workspace_bytes.restype = sz
+    L.mcq_search_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
+    L.mcq_search_scan.restype = i32
+    L.mcq_search_scan.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, sz, vp]
     L.mcq_last_encode_launches.restype = i32
     L.mcq_profile_encode.restype = i32
     L.mcq_profile_encode.argtypes = [vp, i64, vp, f32, i32, i32, i32, i32, vp, sz, vp, ctypes.POINTER(f32), ctypes.POINTER(i32), i32]

@@ -7,8 +7,10 @@
 #include "mcq_tf_kernels.h"
 #include "mcq_pass16_kernels.h"
 #include "mcq_train_kernels.h"
+#include "mcq_search_kernels.h"
 
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -784,6 +786,78 @@ int launch_decode_backward(const float *g, const IdxT *idx, long B, int N, int K
 }
 }  // namespace
 
+// ---- search over stored codes (mcq_search_kernels.h) -------------------------------------------------------------------
+namespace {
+
+// one-byte codes, lists of at most one entry per lane, positions that fit an int
+int search_domain(int N, int K, int D) {
+    if (!domain_ok(N, K, D)) return domain_err(N, K, D);
+    return K > 256 ? MCQ_EUNSUPPORTED : 0;
+}
+
+// the launch arithmetic of the scan (mirrored by tests/search_grid.py): a tile of qt queries per workgroup -- as many as fit
+// kScanTableLds, no more than the call has -- and as many slices of the store as fill the chip once
+struct ScanPlan {
+    int qt, qtiles, slices;
+    long per_slice;
+    size_t lds, ws_half;
+};
+
+ScanPlan scan_plan(long Q, long B, int N, int K, int k) {
+    ScanPlan p;
+    int cap = kScanQTMax;
+    while (cap > 1 && (size_t)cap * N * K * 4 > (size_t)kScanTableLds) cap /= 2;
+    int qt = 1;
+    while (qt < cap && qt < Q) qt *= 2;
+    p.qt = qt;
+    p.qtiles = (int)((Q + qt - 1) / qt);
+    long cap_slices = kScanTargetBlocks / (p.qtiles > 0 ? p.qtiles : 1);
+    cap_slices = cap_slices < 1 ? 1 : (cap_slices > kScanMaxSlices ? kScanMaxSlices : cap_slices);
+    const long steps = (B + 63) / 64;                                    // steps of 64 candidates; at least one per wave
+    long want = (steps + kScanWaves - 1) / kScanWaves;
+    want = want < 1 ? 1 : (want > cap_slices ? cap_slices : want);
+    p.per_slice = (((B + want - 1) / want) + 63) / 64 * 64;
+    if (p.per_slice < 64) p.per_slice = 64;
+    p.slices = (int)((B + p.per_slice - 1) / p.per_slice);
+    const size_t tab = (size_t)qt * N * K * 4, lists = (size_t)qt * kScanWaves * 64 * 8;
+    p.lds = tab > lists ? tab : lists;
+    p.ws_half = align256((size_t)Q * p.slices * k * 4);                  // scores, then positions
+    return p;
+}
+
+template <int QT, int NN>
+int launch_scan(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *norms, long B,
+                int K, int k, float *ws_s, int *ws_i) {
+    static bool allowed[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
+    if (!allowed[dev] || dev == 63) {
+        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_scan<QT, NN>),
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kScanTableLds);
+        if (attr != hipSuccess) return (int)attr;
+        allowed[dev] = true;
+    }
+    hipLaunchKernelGGL((k_search_scan<QT, NN>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kScanWaves), p.lds, st,
+                       tables, Q, codes, norms, B, K, k, p.slices, p.per_slice, ws_s, ws_i);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+template <int QT>
+int launch_scan_n(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *norms,
+                  long B, int N, int K, int k, float *ws_s, int *ws_i) {
+    switch (N) {
+#define MCQ_SCAN_CASE(NN) \
+    case NN: return launch_scan<QT, NN>(p, st, tables, Q, codes, norms, B, K, k, ws_s, ws_i);
+        MCQ_SCAN_CASE(1) MCQ_SCAN_CASE(2) MCQ_SCAN_CASE(4) MCQ_SCAN_CASE(8) MCQ_SCAN_CASE(16) MCQ_SCAN_CASE(32) MCQ_SCAN_CASE(64)
+#undef MCQ_SCAN_CASE
+    }
+    return MCQ_EUNSUPPORTED;
+}
+
+}  // namespace
+
+
 extern "C" {
 
 int mcq_abi_version(void) { return MCQ_ABI_VERSION; }
@@ -1382,6 +1456,77 @@ int mcq_grad_tail(const float *part_c, long n_c, const float *sa, const float *s
                        speed, out_c, out_l);
     MCQ_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- search over stored codes: mcq_search_kernels.h (the launch arithmetic is above, ahead of the C linkage block)
+int mcq_search_tables(const void *q, int q_is_fp16, long Q, const void *prepared, int N, int K, int D, float *tables_out,
+                      void *stream) {
+    if (const int rc = search_domain(N, K, D)) return rc;
+    if (Q < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
+    if (Q == 0) return 0;
+    if (!q || !prepared || !tables_out) return MCQ_EINVAL;
+    const Prepared P = prepared_view(prepared, N, K, D);
+    const int NK = N * K;
+    hipLaunchKernelGGL(k_search_tables, dim3((unsigned)((Q + kTabQueries - 1) / kTabQueries), (unsigned)((NK + kTabRows - 1) / kTabRows)),
+                       dim3(256), 0, static_cast<hipStream_t>(stream), q, q_is_fp16 ? 1 : 0, (int)Q, P.C, NK, D, round_up16(D),
+                       tables_out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int mcq_code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *norms_out, void *stream) {
+    if (const int rc = search_domain(N, K, D)) return rc;
+    if (B < 0) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (B == 0) return 0;
+    if (!codes || !prepared || !norms_out) return MCQ_EINVAL;
+    const Prepared P = prepared_view(prepared, N, K, D);
+    hipLaunchKernelGGL(k_code_norms, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
+                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), norms_out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+size_t mcq_search_workspace_bytes(long Q, long B, int N, int K, int k) {
+    if (Q <= 0 || B <= 0 || k < 1 || k > 64 || B > 0x7fffffffL || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
+    return 2 * scan_plan(Q, B, N, K, k).ws_half;
+}
+
+int mcq_search_scan(const float *tables, long Q, const uint8_t *codes, const float *norms, long B, int N, int K, int k,
+                    float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
+    if (const int rc = search_domain(N, K, 1)) return rc;
+    if (k > 64) return MCQ_EUNSUPPORTED;
+    if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (Q == 0) return 0;
+    if (!out_score || !out_index) return MCQ_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (B > 0) {
+        if (!tables || !codes || !norms || !workspace) return MCQ_EINVAL;
+        const int need = N >= 16 ? 16 : N;                                // the scan loads a candidate's codes as one vector
+        if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
+    }
+    ScanPlan p{};
+    float *ws_s = nullptr;
+    int *ws_i = nullptr;
+    if (B > 0) {
+        p = scan_plan(Q, B, N, K, k);
+        if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
+        ws_s = static_cast<float *>(workspace);
+        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
+        int rc = MCQ_EUNSUPPORTED;
+        switch (p.qt) {
+            case 1: rc = launch_scan_n<1>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
+            case 2: rc = launch_scan_n<2>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
+            case 4: rc = launch_scan_n<4>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
+            case 8: rc = launch_scan_n<8>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
+            case 16: rc = launch_scan_n<16>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
+        }
+        if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, p.slices, k, out_score, out_index);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
 }
 
 int mcq_last_encode_launches(void) { return g_last_launches; }

@@ -1,0 +1,299 @@
+// mcq_search_kernels.h -- gfx950 kernels of the search over STORED CODES: which stored vectors are nearest to a query,
+// answered from the codes themselves (no decode).  The quantizer is additive, x^_b = sum_n C[n][code[b][n]], so
+//     |q - x^_b|^2 = |q|^2 + sum_n T_q[n][code[b][n]] + t_b,     T_q[n][k] = -2 <q, C[n][k]>,     t_b = |x^_b|^2.
+//
+// Arithmetic contract (include/mcq.h, "search over stored codes"; the tests restate rules 3 and 4 in numpy):
+//   1. k_search_tables: T[q][n*K + k] = -2 * (one fp32 chain over d ascending, accumulator starting at +0, each product rounded,
+//      then added: -ffp-contract=off).  Chain length = the padded dim (the pad columns of `prepared` are zero).
+//   2. k_code_norms: per lane l and float4 group g = l, l + 64, ...: v = ((C[0][c_0] + C[1][c_1]) + ...) per component (N - 1
+//      additions), part = (((part + v0*v0) + v1*v1) + v2*v2) + v3*v3, then the xor butterfly 32, 16, 8, 4, 2, 1.  A code digit is
+//      masked with K - 1 (as mcq_decode does).
+//   3. k_search_scan: s[q][b] = (((T[c_0] + T[c_1]) + ...) + T[c_{N-1}]) + t[b], fp32 additions in exactly this order.
+//   4. the result lists are the k smallest under "(s, b) ascending", listed in that order: pair_less below is the ONLY comparison
+//      of the scan and of the merge, so the k indexes are a function of the scores alone.  No floating-point atomics anywhere.
+#pragma once
+#include "mcq_kernels.h"
+#include <hip/hip_fp16.h>
+
+namespace mcq {
+
+// ---- launch arithmetic (tests/search_grid.py reads these constants from this file and mirrors scan_plan of mcq_api.hip)
+constexpr int kTabRows = 64;              // k_search_tables: table rows (n*K + k) per workgroup
+constexpr int kTabQueries = 16;           //                  queries per workgroup
+constexpr int kTabChunk = 32;             //                  features staged per step
+constexpr int kNormWaves = 4;             // k_code_norms: stored vectors per workgroup, one wave each
+constexpr int kScanWaves = 8;             // k_search_scan: waves per workgroup (512 threads)
+constexpr int kScanQTMax = 16;            //                queries per tile at most
+constexpr int kScanTableLds = 128 * 1024; //                bytes of LDS the tables of a tile may take (160 KiB per CU)
+constexpr int kScanTargetBlocks = 256;    //                workgroups that fill the chip once (one per CU)
+constexpr int kScanMaxSlices = 256;       //                cap of the slice count: the workspace stops growing with B here
+constexpr int kNoIndex = 0x7fffffff;      // position of a list entry that holds no candidate (B <= 2^31 - 1: never a real one)
+
+// ---------------------------------------------------------------- the order
+__device__ __forceinline__ bool pair_less(float s, int b, float ts, int tb) { return s < ts || (s == ts && b < tb); }
+
+__device__ __forceinline__ float readlane_f(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+// The wave's list: lane l holds the entry of rank l under (s, b) (ls, li); (ts, tb) is the entry of rank k - 1 (uniform).
+// Every lane offers one candidate (s, b) when `cand`; those below the current worst are inserted one by one (a NaN score
+// compares false and is never inserted).  After warm-up inserts are rare: about k * ln(candidates / k) per list.
+__device__ __forceinline__ void list_insert(float &ls, int &li, float &ts, int &tb, float s, int b, bool cand, int k, int lane) {
+    u64 m = __ballot(cand && pair_less(s, b, ts, tb));
+    while (m) {
+        const int j = __builtin_ctzll(m);
+        m &= m - 1;
+        const float ns = readlane_f(s, j);
+        const int nb = __builtin_amdgcn_readlane(b, j);
+        if (!pair_less(ns, nb, ts, tb)) continue;           // (uniform) the worst moved up since the ballot
+        const float us = __shfl_up(ls, 1, 64);
+        const int ui = __shfl_up(li, 1, 64);
+        const bool after = pair_less(ns, nb, ls, li);       // my entry ranks after the new one: it moves down one lane
+        const bool up_after = lane > 0 && pair_less(ns, nb, us, ui);
+        if (after) {
+            ls = up_after ? us : ns;
+            li = up_after ? ui : nb;
+        }
+        ts = readlane_f(ls, k - 1);
+        tb = __builtin_amdgcn_readlane(li, k - 1);
+    }
+}
+
+// ------------------------------------------------------------------- tables
+// T[q][r] = -2 * sum_d q[d] * C[r][d], r = n*K + k: an LDS-tiled fp32 product, 64 rows x 16 queries per workgroup, thread
+// (r = tid & 63, g = tid >> 6) forms the four queries 4g .. 4g+3 of row r.  One chain over d ascending per entry.
+__global__ void __launch_bounds__(256)
+k_search_tables(const void *__restrict__ qv, int q_is_fp16, int Q, const float *__restrict__ C, int NK, int D, int Dp,
+                float *__restrict__ T) {
+    __shared__ float cs[kTabRows][kTabChunk + 1];           // (+1: lane r reads bank (r + d) mod 32)
+    __shared__ float qs[kTabQueries][kTabChunk];
+    const int tid = threadIdx.x, r = tid & 63, g = tid >> 6;
+    const int r0 = blockIdx.y * kTabRows, q0 = blockIdx.x * kTabQueries;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int d0 = 0; d0 < Dp; d0 += kTabChunk) {
+        for (int e = tid; e < kTabRows * kTabChunk; e += 256) {
+            const int rr = e / kTabChunk, dd = e % kTabChunk;
+            cs[rr][dd] = (r0 + rr < NK && d0 + dd < Dp) ? C[(long)(r0 + rr) * Dp + d0 + dd] : 0.f;
+        }
+        for (int e = tid; e < kTabQueries * kTabChunk; e += 256) {
+            const int qq = e / kTabChunk, dd = e % kTabChunk;
+            float v = 0.f;
+            if (q0 + qq < Q && d0 + dd < D) {
+                const long at = (long)(q0 + qq) * D + d0 + dd;
+                v = q_is_fp16 ? __half2float(static_cast<const __half *>(qv)[at]) : static_cast<const float *>(qv)[at];
+            }
+            qs[qq][dd] = v;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int dd = 0; dd < kTabChunk; ++dd) {
+            const float c = cs[r][dd];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = acc[i] + qs[4 * g + i][dd] * c;
+        }
+        __syncthreads();
+    }
+    if (r0 + r < NK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (q0 + 4 * g + i < Q) T[(long)(q0 + 4 * g + i) * NK + r0 + r] = -2.f * acc[i];
+    }
+}
+
+// -------------------------------------------------------------------- norms
+// t[b] = |sum_n C[n][code[b][n]]|^2: the decode body without the store.  One wave per stored vector.
+__global__ void __launch_bounds__(64 * kNormWaves)
+k_code_norms(const uint8_t *__restrict__ codes, long B, const float *__restrict__ C, int N, int K, int Dp,
+             float *__restrict__ norms) {
+    const long b = (long)blockIdx.x * kNormWaves + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = lane_id();
+    const int mine = (lane < N) ? (codes[b * N + lane] & (K - 1)) : 0;     // lane n holds digit n (N <= 64)
+    float part = 0.f;
+    for (int g0 = 0; g0 < Dp / 4; g0 += 64) {                // (uniform trip count: the digits are read from ALL lanes below)
+        const int g = g0 + lane;
+        const bool live = g < Dp / 4;
+        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < N; ++n) {
+            const int kk = __builtin_amdgcn_readlane(mine, n);
+            const f32x4 c = live ? *reinterpret_cast<const f32x4 *>(C + ((long)n * K + kk) * Dp + 4 * g) : v;
+            v = (n == 0) ? c : v + c;
+        }
+        if (!live) v = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) part = part + v[c] * v[c];
+    }
+    part = wave_sum_butterfly(part);
+    if (lane == 0) norms[b] = part;
+}
+
+// --------------------------------------------------------------------- scan
+// A workgroup owns a tile of QT queries and one slice of the stored codes.  The tile's tables sit in LDS INTERLEAVED by
+// query, Tl[(n*K + k) * QT + q]: the QT entries a candidate needs for codebook n are one contiguous run (QT / 4 ds_read_b128
+// at one address) instead of QT scattered ds_read_b32.  Each lane takes one candidate per step: it loads the N code bytes once
+// (one vector load) and reuses them for every query of the tile.  Every wave keeps one sorted list per query in registers, one
+// entry per lane; the waves' lists are merged per query through LDS (the tables are dead by then) and the workgroup leaves one
+// list of k entries per (query, slice) in the workspace.
+// Up to 8 codebooks' digits of one candidate: one vector load.
+template <int CH>
+struct CodeChunk {
+    uint32_t w[(CH + 3) / 4];
+    __device__ __forceinline__ void load(const uint8_t *__restrict__ p) {
+        if constexpr (CH == 1) {
+            w[0] = p[0];
+        } else if constexpr (CH == 2) {
+            w[0] = *reinterpret_cast<const uint16_t *>(p);
+        } else if constexpr (CH == 4) {
+            w[0] = *reinterpret_cast<const uint32_t *>(p);
+        } else {
+            static_assert(CH == 8, "chunks of 1, 2, 4 or 8 codebooks");
+            const uint2 v = *reinterpret_cast<const uint2 *>(p);
+            w[0] = v.x;
+            w[1] = v.y;
+        }
+    }
+    __device__ __forceinline__ int digit(int n, int kmask) const { return (int)(w[n >> 2] >> (8 * (n & 3))) & kmask; }
+};
+
+template <int QT, int N>
+__global__ void __launch_bounds__(64 * kScanWaves)
+k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ norms,
+              long B, int K, int k, int S, long per_slice, float *__restrict__ ws_s, int *__restrict__ ws_i) {
+    extern __shared__ __attribute__((aligned(16))) char search_smem[];
+    float *Tl = reinterpret_cast<float *>(search_smem);
+    constexpr int CH = N < 8 ? N : 8, NCH = N / CH;          // a candidate's digits arrive in NCH chunks of CH
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile = blockIdx.x / S, slice = blockIdx.x % S;
+    const int q0 = tile * QT, NK = N * K, kmask = K - 1;
+
+    for (int e = tid; e < NK * QT; e += 64 * kScanWaves) {
+        const int q = e % QT, j = e / QT;
+        Tl[e] = (q0 + q < Q) ? tables[(long)(q0 + q) * NK + j] : 0.f;
+    }
+    __syncthreads();
+
+    float ls[QT], ts[QT];
+    int li[QT], tb[QT];
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+        ls[q] = ts[q] = __builtin_inff();
+        li[q] = tb[q] = kNoIndex;
+    }
+
+    const long begin = (long)slice * per_slice;
+    const long end = (begin + per_slice < B) ? begin + per_slice : B;
+    const long nblk = (end - begin + 63) / 64;
+    // lanes past the end of the slice re-read its last candidate (in bounds) and offer nothing
+    auto at = [&](long blk) { const long b = begin + blk * 64 + lane; return b < end ? b : end - 1; };
+    CodeChunk<CH> cur;
+    float t = 0.f;
+    if (wave < nblk) {
+        cur.load(codes + at(wave) * N);
+        t = norms[at(wave)];
+    } else {
+        cur.w[0] = 0;
+        if constexpr (CH == 8) cur.w[1] = 0;
+    }
+    for (long blk = wave; blk < nblk; blk += kScanWaves) {
+        const long bl = begin + blk * 64 + lane;
+        const uint8_t *p = codes + at(blk) * N;
+        const long bnext = (blk + kScanWaves < nblk) ? at(blk + kScanWaves) : at(blk);
+        float tn = t;
+        float acc[QT];
+#pragma unroll
+        for (int q = 0; q < QT; ++q) acc[q] = -0.f;          // (-0) + x == x for every x, signed zeros included
+#pragma unroll 1
+        for (int c = 0; c < NCH; ++c) {
+            CodeChunk<CH> nxt;                               // the next step's digits travel while this one gathers
+            if (c + 1 < NCH) {
+                nxt.load(p + (c + 1) * CH);
+            } else {
+                nxt.load(codes + bnext * N);
+                tn = norms[bnext];
+            }
+#pragma unroll
+            for (int n = 0; n < CH; ++n) {
+                const float *row = Tl + ((c * CH + n) * K + cur.digit(n, kmask)) * QT;
+                if constexpr (QT >= 4) {
+#pragma unroll
+                    for (int q4 = 0; q4 < QT / 4; ++q4) {
+                        const f32x4 v = reinterpret_cast<const f32x4 *>(row)[q4];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) acc[4 * q4 + i] = acc[4 * q4 + i] + v[i];
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < QT; ++q) acc[q] = acc[q] + row[q];
+                }
+            }
+            cur = nxt;
+        }
+        const int bi = (int)bl;
+        const bool valid = bl < end;
+#pragma unroll
+        for (int q = 0; q < QT; ++q) list_insert(ls[q], li[q], ts[q], tb[q], acc[q] + t, bi, valid, k, lane);
+        t = tn;
+    }
+
+    // the waves' lists -> LDS -> one list per query of the tile
+    __syncthreads();
+    float *Ls = reinterpret_cast<float *>(search_smem);
+    int *Li = reinterpret_cast<int *>(search_smem + (size_t)QT * kScanWaves * 64 * 4);
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+        Ls[(q * kScanWaves + wave) * 64 + lane] = ls[q];
+        Li[(q * kScanWaves + wave) * 64 + lane] = li[q];
+    }
+    __syncthreads();
+    for (int q = wave; q < QT; q += kScanWaves) {
+        if (q0 + q >= Q) break;
+        float ms = __builtin_inff(), mts = __builtin_inff();
+        int mi = kNoIndex, mtb = kNoIndex;
+        for (int w = 0; w < kScanWaves; ++w) {
+            const float s = Ls[(q * kScanWaves + w) * 64 + lane];
+            const int b = Li[(q * kScanWaves + w) * 64 + lane];
+            list_insert(ms, mi, mts, mtb, s, b, lane < k && b != kNoIndex, k, lane);
+        }
+        if (lane < k) {
+            const long at = ((long)(q0 + q) * S + slice) * k + lane;
+            ws_s[at] = ms;
+            ws_i[at] = mi;
+        }
+    }
+}
+
+// -------------------------------------------------------------------- merge
+// One wave per query: the S lists of its slices -> the final k under the same order.  An entry that holds no candidate
+// (fewer than k stored vectors) leaves as (+inf, -1).  S == 0 (an empty store) only writes that fill.
+__global__ void __launch_bounds__(64)
+k_search_merge(const float *__restrict__ ws_s, const int *__restrict__ ws_i, int S, int k, float *__restrict__ out_s,
+               int64_t *__restrict__ out_i) {
+    const int q = blockIdx.x, lane = lane_id();
+    const long total = (long)S * k, base = (long)q * total;
+    float ms = __builtin_inff(), mts = __builtin_inff();
+    int mi = kNoIndex, mtb = kNoIndex;
+    float s = 0.f;
+    int b = kNoIndex;
+    if (lane < total) {
+        s = ws_s[base + lane];
+        b = ws_i[base + lane];
+    }
+    for (long e0 = 0; e0 < total; e0 += 64) {
+        float sn = 0.f;
+        int bn = kNoIndex;
+        if (e0 + 64 + lane < total) {
+            sn = ws_s[base + e0 + 64 + lane];
+            bn = ws_i[base + e0 + 64 + lane];
+        }
+        list_insert(ms, mi, mts, mtb, s, b, b != kNoIndex, k, lane);
+        s = sn;
+        b = bn;
+    }
+    if (lane < k) {
+        out_s[(long)q * k + lane] = ms;
+        out_i[(long)q * k + lane] = (mi == kNoIndex) ? (int64_t)-1 : (int64_t)mi;
+    }
+}
+
+}  // namespace mcq

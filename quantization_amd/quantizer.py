@@ -469,6 +469,104 @@ class Quantizer(nn.Module):
         _lib.check(rc, "mcq_decode")
         return out
 
+    # ------------------------------------------------- search over stored codes
+    def _search_state(self, dev):
+        """(L, blob, stream) for the search entry points: any flavour of derived state will do (they read the scaled centers)."""
+        self._check_domain()
+        if self.codebook_size > 256:
+            raise _lib.McqError("quantization_amd: the search over stored codes takes one-byte codes (codebook_size <= 256)")
+        with torch.no_grad():
+            blob = self._prepared(any_flavour=True)
+        return _lib.lib(), blob, torch.cuda.current_stream(dev).cuda_stream
+
+    def _unpacked_codes(self, codes: Tensor) -> Tensor:
+        """codes as encode(..., as_bytes=True) returned them -> uint8 (B, num_codebooks), one digit per byte, on the device."""
+        if not codes.is_cuda:
+            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
+        N, K = self.num_codebooks, self.codebook_size
+        flat = codes.reshape(-1, codes.shape[-1])
+        if flat.dtype != torch.uint8:
+            raise _lib.McqError("quantization_amd: the search takes uint8 codes (encode(..., as_bytes=True))")
+        if flat.shape[1] != N:
+            if not (K == 16 and flat.shape[1] * 2 == N):
+                raise _lib.McqError(f"codes of {flat.shape[1]} bytes per vector do not belong to {N} codebooks of {K}")
+            flat = torch.stack([flat & 15, flat >> 4], dim=2).reshape(-1, N)     # low nibble = even codebook (encode's packing)
+        flat = flat.contiguous()
+        if flat.data_ptr() % 16:
+            flat = flat.clone()
+        return flat
+
+    def search_tables(self, queries: Tensor) -> Tensor:
+        """queries (*, dim) fp32 or fp16 -> fp32 (Q, num_codebooks, codebook_size): T[q][n][k] = -2 <q, C[n][k]> (mcq_search_tables)."""
+        if not queries.is_cuda:
+            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
+        N, K, D = self.num_codebooks, self.codebook_size, self.dim
+        q2d = queries.detach().reshape(-1, D)
+        q2d = q2d.contiguous() if q2d.dtype == torch.float16 else q2d.to(torch.float32).contiguous()
+        Q, dev = q2d.shape[0], q2d.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            L, blob, st = self._search_state(dev)
+            out = torch.empty((Q, N, K), dtype=torch.float32, device=dev)
+            rc = L.mcq_search_tables(q2d.data_ptr(), int(q2d.dtype == torch.float16), Q, blob.data_ptr(), N, K, D,
+                                     out.data_ptr(), st)
+        _lib.check(rc, "mcq_search_tables")
+        return out
+
+    def code_norms(self, codes: Tensor) -> Tensor:
+        """codes (*, num_codebooks) uint8 (or packed, codebook_size 16) -> fp32 (B,): |decode(codes[b])|^2 (mcq_code_norms).
+        Formed once per store of codes and handed to search(norms=...)."""
+        N, K, D = self.num_codebooks, self.codebook_size, self.dim
+        flat = self._unpacked_codes(codes)
+        B, dev = flat.shape[0], flat.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            L, blob, st = self._search_state(dev)
+            out = torch.empty((B,), dtype=torch.float32, device=dev)
+            rc = L.mcq_code_norms(flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
+        _lib.check(rc, "mcq_code_norms")
+        return out
+
+    def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int):
+        """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, norms fp32 (B,) -> (scores fp32 (Q, k), indexes int64 (Q, k)):
+        the k smallest score[q][b] = sum_n tables[q][n][codes[b][n]] + norms[b] under (score, b) ascending (mcq_search_scan)."""
+        N, K = self.num_codebooks, self.codebook_size
+        if not (tables.is_cuda and codes.is_cuda and norms.is_cuda):
+            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
+        tables = tables.detach().to(torch.float32).contiguous()
+        norms = norms.detach().to(torch.float32).contiguous()
+        codes = codes.contiguous()
+        if codes.data_ptr() % 16:
+            codes = codes.clone()
+        Q, B, dev = tables.shape[0], codes.shape[0], tables.device
+        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and codes.dtype == torch.uint8
+        assert tuple(norms.shape) == (B,)
+        L = _lib.lib()
+        with torch.no_grad(), torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+            indexes = torch.empty((Q, k), dtype=torch.int64, device=dev)
+            ws = torch.empty(L.mcq_search_workspace_bytes(Q, B, N, K, k), dtype=torch.uint8, device=dev)
+            rc = L.mcq_search_scan(tables.data_ptr(), Q, codes.data_ptr(), norms.data_ptr(), B, N, K, int(k), scores.data_ptr(),
+                                   indexes.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        _lib.check(rc, "mcq_search_scan")
+        return scores, indexes
+
+    def search(self, queries: Tensor, codes: Tensor, k: int = 10, norms: Tensor = None):
+        """The k stored vectors nearest to each query, from the codes alone (nothing is decoded).
+        queries (*, dim) fp32 or fp16; codes (B, num_codebooks) uint8 as encode(..., as_bytes=True) returned them (packed
+        16-entry codes are unpacked first); norms = code_norms(codes) when not given (pass them in when searching repeatedly).
+        -> (distances fp32 (*, k), indexes int64 (*, k)): |q - decode(codes[b])|^2 clamped at 0, nearest first, the lower
+        position first among equal scores; with fewer than k stored vectors the tail is (+inf, -1).  Not differentiable."""
+        with torch.no_grad():
+            flat = self._unpacked_codes(codes)
+            if norms is None:
+                norms = self.code_norms(flat)
+            tables = self.search_tables(queries)
+            scores, indexes = self._search_scan(tables, flat, norms.reshape(-1), k)
+            q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
+            dist = (scores + (q2d * q2d).sum(dim=1, keepdim=True)).clamp_(min=0.0)
+        lead = queries.shape[:-1]
+        return dist.reshape(*lead, k), indexes.reshape(*lead, k)
+
     def logits_kernel(self, x: Tensor) -> Tensor:
         """Logits as the index-search kernel forms them (test hook; mcq_logits)."""
         L = _lib.lib()
