@@ -305,6 +305,17 @@ int mcq_decode_backward_u8(const float *grad_out, const uint8_t *codes, long B, 
  *      order; fewer than k candidates: the tail is (+inf, -1).
  *   5. no floating-point atomics: the same inputs give the same bits.  A non-finite query or norm neither faults nor hangs; its
  *      row of results is unspecified.
+ * Inner product and cosine come from the same tables (mcq_search_scan_metric; rules 1, 2, 4 and 5 hold as they stand):
+ *     <q, x^_b> = -1/2 * S,    cos(q, x^_b) = <q, x^_b> / (|q| |x^_b|),    S = ((T[c_0] + T[c_1]) + ...) + T[c_{N-1}] as in rule 3.
+ *   3'. score[q][b] per metric, with the per-candidate array w (float[B]):
+ *         MCQ_SEARCH_L2    w = norms                  score = S + w[b]      smaller = nearer (rule 3; this IS mcq_search_scan)
+ *         MCQ_SEARCH_IP    w is ignored, may be NULL  score = S             smaller = larger inner product; nothing is loaded
+ *         MCQ_SEARCH_COS   w = rnorms                 score = S * w[b]      smaller = larger cosine (|q| is constant per query);
+ *                                                                           one fp32 multiplication
+ *       The caller turns a score into a similarity: -0.5 * score (IP), -0.5 * score / |q| (cosine).
+ *   6. rnorms[b] = 1.0f / sqrtf(norms[b]), both operations correctly rounded in fp32, and 0 where norms[b] == 0 (an all-zero
+ *      reconstruction scores 0 under the cosine, never NaN).  mcq_code_rnorms forms norms[b] exactly as rule 2 says and converts;
+ *      mcq_rnorms_from_norms converts norms a store already keeps: the two agree bit for bit.
  * mcq_search_tables: q fp32 or (q_is_fp16 != 0) IEEE fp16 [Q][D] -> tables_out float[Q][N*K].
  * mcq_code_norms: codes uint8 [B][N], one per codebook (unpacked) -> norms_out float[B].
  * mcq_search_scan: tables float[Q][N*K], codes uint8 [B][N] aligned to min(N, 16) bytes (MCQ_EINVAL otherwise), norms float[B]
@@ -318,6 +329,21 @@ int mcq_code_norms(const uint8_t *codes, long B, const void *prepared, int N, in
 size_t mcq_search_workspace_bytes(long Q, long B, int N, int K, int k);
 int mcq_search_scan(const float *tables, long Q, const uint8_t *codes, const float *norms, long B, int N, int K, int k,
                     float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The scan under a metric (rules 3' and 6 above).  Arguments, limits, workspace (mcq_search_workspace_bytes serves every metric)
+ * and the order of the lists are those of mcq_search_scan; an unknown metric is MCQ_EINVAL, and so is w == NULL with
+ * MCQ_SEARCH_L2 or MCQ_SEARCH_COS when B > 0.  Fewer than k candidates: the tail is (+inf, -1) under every metric (scores
+ * ascend; a caller that reports similarities shows it as (-inf, -1)).
+ * mcq_code_rnorms: as mcq_code_norms, rnorms_out float[B].  mcq_rnorms_from_norms: norms float[B] -> rnorms_out float[B]
+ * (B > 2^31 - 1: MCQ_EUNSUPPORTED; in place is fine).                                                                    */
+#define MCQ_SEARCH_L2 0
+#define MCQ_SEARCH_IP 1
+#define MCQ_SEARCH_COS 2
+int mcq_search_scan_metric(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
+                           int metric, float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int mcq_code_rnorms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *rnorms_out, void *stream);
+int mcq_rnorms_from_norms(const float *norms, long B, float *rnorms_out, void *stream);
 
 /* ---- test / profiling hooks -------------------------------------------------
  * Logits of Quantizer._logits (:277-279) for a batch, fp32 [B][N*K]; used by the

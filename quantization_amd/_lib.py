@@ -22,9 +22,11 @@ SYMBOLS = (
     "mcq_weight_grad", "mcq_weight_grad_workspace_bytes", "mcq_adam_step", "mcq_loss_head", "mcq_loss_head_tail", "mcq_scales_exp",
     "mcq_decode_backward_waves", "mcq_decode_backward_u8_ex", "mcq_loss_bwd_waves", "mcq_loss_bwd_ex", "mcq_grad_tail",
     "mcq_search_tables", "mcq_code_norms", "mcq_search_workspace_bytes", "mcq_search_scan",
+    "mcq_search_scan_metric", "mcq_code_rnorms", "mcq_rnorms_from_norms",
 )
 
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
+MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
 _lib = None
 
@@ -130,6 +132,14 @@ def lib():
     L.mcq_search_workspace_bytes.argtypes = [i64, i64, i32, i32, i32]
     L.mcq_search_scan.restype = i32
     L.mcq_search_scan.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, sz, vp]
+    # (an older build under the A/B hook above knows the L2 search only: its other metrics stay unbound, and calling one raises)
+    if not (_ALT and not hasattr(L, "mcq_search_scan_metric")):
+        L.mcq_search_scan_metric.restype = i32
+        L.mcq_search_scan_metric.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+        L.mcq_code_rnorms.restype = i32
+        L.mcq_code_rnorms.argtypes = [vp, i64, vp, i32, i32, i32, vp, vp]
+        L.mcq_rnorms_from_norms.restype = i32
+        L.mcq_rnorms_from_norms.argtypes = [vp, i64, vp, vp]
     L.mcq_last_encode_launches.restype = i32
     L.mcq_profile_encode.restype = i32
     L.mcq_profile_encode.argtypes = [vp, i64, vp, f32, i32, i32, i32, i32, vp, sz, vp, ctypes.POINTER(f32), ctypes.POINTER(i32), i32]

@@ -825,32 +825,48 @@ ScanPlan scan_plan(long Q, long B, int N, int K, int k) {
     return p;
 }
 
-template <int QT, int NN>
+template <int QT, int NN, int M>
 int launch_scan(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *norms, long B,
                 int K, int k, float *ws_s, int *ws_i) {
     static bool allowed[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
     if (!allowed[dev] || dev == 63) {
-        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_scan<QT, NN>),
+        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_scan<QT, NN, M>),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kScanTableLds);
         if (attr != hipSuccess) return (int)attr;
         allowed[dev] = true;
     }
-    hipLaunchKernelGGL((k_search_scan<QT, NN>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kScanWaves), p.lds, st,
+    hipLaunchKernelGGL((k_search_scan<QT, NN, M>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kScanWaves), p.lds, st,
                        tables, Q, codes, norms, B, K, k, p.slices, p.per_slice, ws_s, ws_i);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
 
-template <int QT>
+template <int QT, int M>
 int launch_scan_n(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *norms,
                   long B, int N, int K, int k, float *ws_s, int *ws_i) {
     switch (N) {
 #define MCQ_SCAN_CASE(NN) \
-    case NN: return launch_scan<QT, NN>(p, st, tables, Q, codes, norms, B, K, k, ws_s, ws_i);
+    case NN: return launch_scan<QT, NN, M>(p, st, tables, Q, codes, norms, B, K, k, ws_s, ws_i);
         MCQ_SCAN_CASE(1) MCQ_SCAN_CASE(2) MCQ_SCAN_CASE(4) MCQ_SCAN_CASE(8) MCQ_SCAN_CASE(16) MCQ_SCAN_CASE(32) MCQ_SCAN_CASE(64)
 #undef MCQ_SCAN_CASE
+    }
+    return MCQ_EUNSUPPORTED;
+}
+
+// the metric is a template parameter of the scan: the L2 instantiations are the code they were before
+// the other two metrics existed
+static_assert(kMetricL2 == MCQ_SEARCH_L2 && kMetricIP == MCQ_SEARCH_IP && kMetricCos == MCQ_SEARCH_COS, "include/mcq.h");
+template <int M>
+int launch_scan_qt(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
+                   int N, int K, int k, float *ws_s, int *ws_i) {
+    switch (p.qt) {
+        case 1: return launch_scan_n<1, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
+        case 2: return launch_scan_n<2, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
+        case 4: return launch_scan_n<4, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
+        case 8: return launch_scan_n<8, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
+        case 16: return launch_scan_n<16, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
     }
     return MCQ_EUNSUPPORTED;
 }
@@ -1481,7 +1497,7 @@ int mcq_code_norms(const uint8_t *codes, long B, const void *prepared, int N, in
     if (B == 0) return 0;
     if (!codes || !prepared || !norms_out) return MCQ_EINVAL;
     const Prepared P = prepared_view(prepared, N, K, D);
-    hipLaunchKernelGGL(k_code_norms, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
+    hipLaunchKernelGGL(k_code_norms<false>, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
                        static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), norms_out);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
@@ -1492,17 +1508,50 @@ size_t mcq_search_workspace_bytes(long Q, long B, int N, int K, int k) {
     return 2 * scan_plan(Q, B, N, K, k).ws_half;
 }
 
+int mcq_code_rnorms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *rnorms_out, void *stream) {
+    if (const int rc = search_domain(N, K, D)) return rc;
+    if (B < 0) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (B == 0) return 0;
+    if (!codes || !prepared || !rnorms_out) return MCQ_EINVAL;
+    const Prepared P = prepared_view(prepared, N, K, D);
+    hipLaunchKernelGGL(k_code_norms<true>, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
+                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), rnorms_out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int mcq_rnorms_from_norms(const float *norms, long B, float *rnorms_out, void *stream) {
+    if (B < 0) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (B == 0) return 0;
+    if (!norms || !rnorms_out) return MCQ_EINVAL;
+    hipLaunchKernelGGL(k_rnorms_from_norms, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       norms, B, rnorms_out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
 int mcq_search_scan(const float *tables, long Q, const uint8_t *codes, const float *norms, long B, int N, int K, int k,
                     float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
+    return mcq_search_scan_metric(tables, Q, codes, norms, B, N, K, k, MCQ_SEARCH_L2, out_score, out_index, workspace,
+                                  workspace_bytes, stream);
+}
+
+int mcq_search_scan_metric(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
+                           int metric, float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes,
+                           void *stream) {
     if (const int rc = search_domain(N, K, 1)) return rc;
     if (k > 64) return MCQ_EUNSUPPORTED;
     if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
+    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
     if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
     if (Q == 0) return 0;
     if (!out_score || !out_index) return MCQ_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (B > 0) {
-        if (!tables || !codes || !norms || !workspace) return MCQ_EINVAL;
+        if (!tables || !codes || !workspace) return MCQ_EINVAL;
+        if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;              // (the inner-product scan never reads w)
         const int need = N >= 16 ? 16 : N;                                // the scan loads a candidate's codes as one vector
         if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
     }
@@ -1515,12 +1564,10 @@ int mcq_search_scan(const float *tables, long Q, const uint8_t *codes, const flo
         ws_s = static_cast<float *>(workspace);
         ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
         int rc = MCQ_EUNSUPPORTED;
-        switch (p.qt) {
-            case 1: rc = launch_scan_n<1>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
-            case 2: rc = launch_scan_n<2>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
-            case 4: rc = launch_scan_n<4>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
-            case 8: rc = launch_scan_n<8>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
-            case 16: rc = launch_scan_n<16>(p, st, tables, (int)Q, codes, norms, B, N, K, k, ws_s, ws_i); break;
+        switch (metric) {
+            case MCQ_SEARCH_L2: rc = launch_scan_qt<kMetricL2>(p, st, tables, (int)Q, codes, w, B, N, K, k, ws_s, ws_i); break;
+            case MCQ_SEARCH_IP: rc = launch_scan_qt<kMetricIP>(p, st, tables, (int)Q, codes, nullptr, B, N, K, k, ws_s, ws_i); break;
+            case MCQ_SEARCH_COS: rc = launch_scan_qt<kMetricCos>(p, st, tables, (int)Q, codes, w, B, N, K, k, ws_s, ws_i); break;
         }
         if (rc != 0) return rc;
     }

@@ -9,6 +9,12 @@
 //      additions), part = (((part + v0*v0) + v1*v1) + v2*v2) + v3*v3, then the xor butterfly 32, 16, 8, 4, 2, 1.  A code digit is
 //      masked with K - 1 (as mcq_decode does).
 //   3. k_search_scan: s[q][b] = (((T[c_0] + T[c_1]) + ...) + T[c_{N-1}]) + t[b], fp32 additions in exactly this order.
+//      With a metric (k_search_scan<QT, N, M>; S is the sum of the N table entries above, w the per-candidate array):
+//        kMetricL2   w[b] = t[b]                                   score = S + w[b]      (the line above)
+//        kMetricIP   no w: the pointer is never read               score = S             (= -2 <q, x^_b>)
+//        kMetricCos  w[b] = r[b] = 1 / sqrt(t[b]), 0 where t == 0  score = S * w[b]      (= -2 |q| cos(q, x^_b); one fp32 product)
+//      r[b] is formed by k_code_norms<true> / k_rnorms_from_norms: a correctly rounded square root, then a correctly rounded
+//      division (no v_rsq_f32, no fast-math: the tests restate it as float32(1) / sqrt(t) in numpy and compare bits).
 //   4. the result lists are the k smallest under "(s, b) ascending", listed in that order: pair_less below is the ONLY comparison
 //      of the scan and of the merge, so the k indexes are a function of the scores alone.  No floating-point atomics anywhere.
 #pragma once
@@ -28,6 +34,10 @@ constexpr int kScanTableLds = 128 * 1024; //                bytes of LDS the tab
 constexpr int kScanTargetBlocks = 256;    //                workgroups that fill the chip once (one per CU)
 constexpr int kScanMaxSlices = 256;       //                cap of the slice count: the workspace stops growing with B here
 constexpr int kNoIndex = 0x7fffffff;      // position of a list entry that holds no candidate (B <= 2^31 - 1: never a real one)
+// the finishing operation of a candidate's score (MCQ_SEARCH_L2 / _IP / _COS of include/mcq.h): a template parameter of the scan
+constexpr int kMetricL2 = 0;
+constexpr int kMetricIP = 1;
+constexpr int kMetricCos = 2;
 
 // ---------------------------------------------------------------- the order
 __device__ __forceinline__ bool pair_less(float s, int b, float ts, int tb) { return s < ts || (s == ts && b < tb); }
@@ -102,7 +112,12 @@ k_search_tables(const void *__restrict__ qv, int q_is_fp16, int Q, const float *
 }
 
 // -------------------------------------------------------------------- norms
-// t[b] = |sum_n C[n][code[b][n]]|^2: the decode body without the store.  One wave per stored vector.
+// r = 1 / sqrt(t), and 0 for t == 0 (an all-zero reconstruction scores 0 under the cosine, never NaN).  A negative or NaN t
+// gives NaN, which no list ever takes.
+__device__ __forceinline__ float rnorm_of(float t) { return t == 0.f ? 0.f : 1.0f / sqrtf(t); }
+
+// t[b] = |sum_n C[n][code[b][n]]|^2: the decode body without the store.  One wave per stored vector.  RNORM: r[b] leaves instead.
+template <bool RNORM>
 __global__ void __launch_bounds__(64 * kNormWaves)
 k_code_norms(const uint8_t *__restrict__ codes, long B, const float *__restrict__ C, int N, int K, int Dp,
              float *__restrict__ norms) {
@@ -125,7 +140,14 @@ k_code_norms(const uint8_t *__restrict__ codes, long B, const float *__restrict_
         for (int c = 0; c < 4; ++c) part = part + v[c] * v[c];
     }
     part = wave_sum_butterfly(part);
-    if (lane == 0) norms[b] = part;
+    if (lane == 0) norms[b] = RNORM ? rnorm_of(part) : part;
+}
+
+// r[b] from t[b] a store already keeps (code_norms): no center is gathered again
+__global__ void __launch_bounds__(256)
+k_rnorms_from_norms(const float *__restrict__ norms, long B, float *__restrict__ rnorms) {
+    const long b = (long)blockIdx.x * 256 + threadIdx.x;
+    if (b < B) rnorms[b] = rnorm_of(norms[b]);
 }
 
 // --------------------------------------------------------------------- scan
@@ -156,9 +178,10 @@ struct CodeChunk {
     __device__ __forceinline__ int digit(int n, int kmask) const { return (int)(w[n >> 2] >> (8 * (n & 3))) & kmask; }
 };
 
-template <int QT, int N>
+// M: what finishes a score (rule 3).  w is t[b] (L2) or r[b] (cosine); the inner-product scan has no w and loads none.
+template <int QT, int N, int M>
 __global__ void __launch_bounds__(64 * kScanWaves)
-k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ norms,
+k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w,
               long B, int K, int k, int S, long per_slice, float *__restrict__ ws_s, int *__restrict__ ws_i) {
     extern __shared__ __attribute__((aligned(16))) char search_smem[];
     float *Tl = reinterpret_cast<float *>(search_smem);
@@ -190,7 +213,7 @@ k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict
     float t = 0.f;
     if (wave < nblk) {
         cur.load(codes + at(wave) * N);
-        t = norms[at(wave)];
+        if constexpr (M != kMetricIP) t = w[at(wave)];
     } else {
         cur.w[0] = 0;
         if constexpr (CH == 8) cur.w[1] = 0;
@@ -210,7 +233,7 @@ k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict
                 nxt.load(p + (c + 1) * CH);
             } else {
                 nxt.load(codes + bnext * N);
-                tn = norms[bnext];
+                if constexpr (M != kMetricIP) tn = w[bnext];
             }
 #pragma unroll
             for (int n = 0; n < CH; ++n) {
@@ -232,7 +255,10 @@ k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict
         const int bi = (int)bl;
         const bool valid = bl < end;
 #pragma unroll
-        for (int q = 0; q < QT; ++q) list_insert(ls[q], li[q], ts[q], tb[q], acc[q] + t, bi, valid, k, lane);
+        for (int q = 0; q < QT; ++q) {
+            const float s = M == kMetricL2 ? acc[q] + t : (M == kMetricCos ? acc[q] * t : acc[q]);
+            list_insert(ls[q], li[q], ts[q], tb[q], s, bi, valid, k, lane);
+        }
         t = tn;
     }
 

@@ -525,37 +525,90 @@ class Quantizer(nn.Module):
         _lib.check(rc, "mcq_code_norms")
         return out
 
-    def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int):
+    def code_rnorms(self, codes: Tensor) -> Tensor:
+        """codes as for code_norms -> fp32 (B,): 1 / sqrt(code_norms(codes)), 0 for an all-zero reconstruction (mcq_code_rnorms).
+        What the cosine search multiplies by: formed once per store and handed to search(metric="cosine", rnorms=...)."""
+        N, K, D = self.num_codebooks, self.codebook_size, self.dim
+        flat = self._unpacked_codes(codes)
+        B, dev = flat.shape[0], flat.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            L, blob, st = self._search_state(dev)
+            out = torch.empty((B,), dtype=torch.float32, device=dev)
+            rc = L.mcq_code_rnorms(flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
+        _lib.check(rc, "mcq_code_rnorms")
+        return out
+
+    def rnorms_from_norms(self, norms: Tensor) -> Tensor:
+        """norms fp32 (B,) as code_norms returned them -> fp32 (B,): the same values code_rnorms gives, without a gather
+        (mcq_rnorms_from_norms)."""
+        if not norms.is_cuda:
+            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
+        norms = norms.detach().reshape(-1).to(torch.float32).contiguous()
+        dev = norms.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            out = torch.empty_like(norms)
+            rc = _lib.lib().mcq_rnorms_from_norms(norms.data_ptr(), norms.numel(), out.data_ptr(),
+                                                  torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "mcq_rnorms_from_norms")
+        return out
+
+    _METRICS = {"l2": _lib.MCQ_SEARCH_L2, "ip": _lib.MCQ_SEARCH_IP, "cosine": _lib.MCQ_SEARCH_COS}
+
+    def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int, metric: str = "l2"):
         """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, norms fp32 (B,) -> (scores fp32 (Q, k), indexes int64 (Q, k)):
-        the k smallest score[q][b] = sum_n tables[q][n][codes[b][n]] + norms[b] under (score, b) ascending (mcq_search_scan)."""
+        the k smallest score[q][b] = sum_n tables[q][n][codes[b][n]] + norms[b] under (score, b) ascending (mcq_search_scan).
+        metric "ip": the score is the sum alone and `norms` is not looked at (None will do); "cosine": `norms` holds the
+        reciprocal roots (code_rnorms) and the score is the sum times norms[b] (mcq_search_scan_metric)."""
         N, K = self.num_codebooks, self.codebook_size
-        if not (tables.is_cuda and codes.is_cuda and norms.is_cuda):
+        if metric not in self._METRICS:
+            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
+        if metric == "ip":
+            norms = None
+        elif norms is None:
+            raise ValueError(f"metric {metric!r} needs the per-candidate array")
+        if not (tables.is_cuda and codes.is_cuda and (norms is None or norms.is_cuda)):
             raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
         tables = tables.detach().to(torch.float32).contiguous()
-        norms = norms.detach().to(torch.float32).contiguous()
+        if norms is not None:
+            norms = norms.detach().to(torch.float32).contiguous()
         codes = codes.contiguous()
         if codes.data_ptr() % 16:
             codes = codes.clone()
         Q, B, dev = tables.shape[0], codes.shape[0], tables.device
         assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and codes.dtype == torch.uint8
-        assert tuple(norms.shape) == (B,)
+        assert norms is None or tuple(norms.shape) == (B,)
         L = _lib.lib()
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
             indexes = torch.empty((Q, k), dtype=torch.int64, device=dev)
             ws = torch.empty(L.mcq_search_workspace_bytes(Q, B, N, K, k), dtype=torch.uint8, device=dev)
-            rc = L.mcq_search_scan(tables.data_ptr(), Q, codes.data_ptr(), norms.data_ptr(), B, N, K, int(k), scores.data_ptr(),
-                                   indexes.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        _lib.check(rc, "mcq_search_scan")
+            if metric == "l2":
+                rc = L.mcq_search_scan(tables.data_ptr(), Q, codes.data_ptr(), norms.data_ptr(), B, N, K, int(k),
+                                       scores.data_ptr(), indexes.data_ptr(), ws.data_ptr(), ws.numel(), st)
+            else:
+                rc = L.mcq_search_scan_metric(tables.data_ptr(), Q, codes.data_ptr(), None if norms is None else norms.data_ptr(),
+                                              B, N, K, int(k), self._METRICS[metric], scores.data_ptr(), indexes.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), st)
+        _lib.check(rc, "mcq_search_scan" if metric == "l2" else "mcq_search_scan_metric")
         return scores, indexes
 
-    def search(self, queries: Tensor, codes: Tensor, k: int = 10, norms: Tensor = None):
+    def search(self, queries: Tensor, codes: Tensor, k: int = 10, norms: Tensor = None, metric: str = "l2",
+               rnorms: Tensor = None):
         """The k stored vectors nearest to each query, from the codes alone (nothing is decoded).
         queries (*, dim) fp32 or fp16; codes (B, num_codebooks) uint8 as encode(..., as_bytes=True) returned them (packed
         16-entry codes are unpacked first); norms = code_norms(codes) when not given (pass them in when searching repeatedly).
         -> (distances fp32 (*, k), indexes int64 (*, k)): |q - decode(codes[b])|^2 clamped at 0, nearest first, the lower
-        position first among equal scores; with fewer than k stored vectors the tail is (+inf, -1).  Not differentiable."""
+        position first among equal scores; with fewer than k stored vectors the tail is (+inf, -1).  Not differentiable.
+        metric="ip": -> (similarities, indexes), <q, decode(codes[b])>, largest first; norms are neither needed nor formed.
+        metric="cosine": -> (similarities, indexes), cos(q, decode(codes[b])), largest first, 0 for a zero query or an
+        all-zero reconstruction; it multiplies by rnorms = code_rnorms(codes): pass them in when searching repeatedly, or pass
+        norms and they are converted on the device (rnorms_from_norms), else code_rnorms(codes) is run.
+        Under both the lower position comes first among equal scores and the tail of a short store is (-inf, -1)."""
+        if metric not in self._METRICS:
+            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
+        if metric != "l2":
+            return self._search_similarity(queries, codes, k, norms, metric, rnorms)
         with torch.no_grad():
             flat = self._unpacked_codes(codes)
             if norms is None:
@@ -566,6 +619,28 @@ class Quantizer(nn.Module):
             dist = (scores + (q2d * q2d).sum(dim=1, keepdim=True)).clamp_(min=0.0)
         lead = queries.shape[:-1]
         return dist.reshape(*lead, k), indexes.reshape(*lead, k)
+
+    def _search_similarity(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms):
+        """search() under "ip" and "cosine": the scan's scores are -2 <q, x^> and -2 |q| cos; halving is exact"""
+        with torch.no_grad():
+            flat = self._unpacked_codes(codes)
+            w = None
+            if metric == "cosine":
+                if rnorms is not None:
+                    w = rnorms.reshape(-1)
+                elif norms is not None:
+                    w = self.rnorms_from_norms(norms)
+                else:
+                    w = self.code_rnorms(flat)
+            tables = self.search_tables(queries)
+            scores, indexes = self._search_scan(tables, flat, w, k, metric=metric)
+            sim = scores * -0.5
+            if metric == "cosine":
+                q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
+                qn = (q2d * q2d).sum(dim=1, keepdim=True).sqrt_()
+                sim = sim / qn.masked_fill_(qn == 0, 1.0)          # (a zero query: every score is a zero, and so is 0 / 1)
+        lead = queries.shape[:-1]
+        return sim.reshape(*lead, k), indexes.reshape(*lead, k)
 
     def logits_kernel(self, x: Tensor) -> Tensor:
         """Logits as the index-search kernel forms them (test hook; mcq_logits)."""
