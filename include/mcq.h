@@ -139,6 +139,11 @@ int mcq_encode(const float *x, long B, const void *prepared, float lscale_exp, i
  * quantization/quantization.py:798): rows widen to fp32 in the kernels' load path.  Every fp16 value
  * is an fp32 value, so the codes equal those of the widened input bit for bit.                   */
 #define MCQ_ENCODE_X_FP16 4u
+/* The initial codes are the arg max of the classifier logits.  When a call wants codes only, six of the ten limb
+ * products of each logit pick the winner wherever their error bound separates it from the runner-up, and the remaining
+ * (frame, codebook) pairs are recomputed exactly: same codes, less work.  MCQ_ENCODE_EXACT_LOGITS forces the ten-product
+ * kernel for every pair (the A/B switch of that path; the environment hook MCQ_EXACT_LOGITS=1 does the same per process). */
+#define MCQ_ENCODE_EXACT_LOGITS 16u
 int mcq_encode_ex(const float *x, long B, const void *prepared, float lscale_exp, int N, int K, int D,
                   int refine_iters, uint8_t *out_u8, int64_t *out_i64, void *workspace,
                   size_t workspace_bytes, void *stream, unsigned flags);

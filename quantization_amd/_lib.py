@@ -28,6 +28,7 @@ SYMBOLS = (
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
 MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
+MCQ_ENCODE_EXACT_LOGITS = 16    # mcq_encode_ex: the initial arg max from all ten limb products (the screened path is the default)
 _lib = None
 
 

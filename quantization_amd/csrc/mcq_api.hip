@@ -226,13 +226,14 @@ FixRowsArgs fix_rows_args(const float *src, int xh, long R, int D, long ld, int8
                           const float *bias_src = nullptr, float *bias_dst = nullptr, const float *sub = nullptr,
                           long sub_per = 0, long sub_ld = 0, const float *dot_vec = nullptr, float *dot_out = nullptr) {
     return FixRowsArgs{src, xh, R, fix_round_rows(R), D, ld, fix_round_cols(D), planes, exps, xx, bias_src, bias_dst,
-                       sub, sub_per, sub_ld, dot_vec, dot_out};
+                       sub, sub_per, sub_ld, dot_vec, dot_out, nullptr};
 }
 
 // sub != nullptr: the rows are centered by sub[0 .. D) (the frames of the search and of the logits: x - mean)
 int launch_fix_rows(const float *src, int xh, long R, int D, long ld, int8_t *planes, int *exps, float *xx, hipStream_t st,
-                    const float *sub = nullptr) {
-    const FixRowsArgs a = fix_rows_args(src, xh, R, D, ld, planes, exps, xx, nullptr, nullptr, sub, 0, 0);
+                    const float *sub = nullptr, unsigned *clear = nullptr) {
+    FixRowsArgs a = fix_rows_args(src, xh, R, D, ld, planes, exps, xx, nullptr, nullptr, sub, 0, 0);
+    a.clear = clear;
     // four rows per workgroup, one per wave (16 rows per workgroup and 256-byte runs into the planes measured slower:
     // 0.086 vs 0.071 ms at 65,536 x 512)
     hipLaunchKernelGGL(k_fix_rows<4>, dim3((unsigned)(a.Rp / 4)), dim3(256), 0, st, a);
@@ -252,20 +253,21 @@ template <int MODE>
 int launch_fgemm(FixGemm g, hipStream_t st) {
     // the kernel's 132 KB of dynamic LDS has to be allowed once per device (a process may drive several)
     static bool allowed[64] = {};
+    constexpr int lds = MODE == FG_SCREEN ? kFixLdsScreen : kFixLds;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
     if (!allowed[dev] || dev == 63) {
         const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgemm<MODE>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kFixLds);
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (attr != hipSuccess) return (int)attr;
         allowed[dev] = true;
     }
     const long MT = g.RA / kFixTile, NT = g.RB / kFixTile;
-    const int H = (MODE == FG_LOGITS && g.K > kFixTile) ? g.K / kFixTile : 1;
+    const int H = (MODE != FG_STORE && g.K > kFixTile) ? g.K / kFixTile : 1;
     const long big = g.walk_rows ? NT : MT, small_units = (g.walk_rows ? MT : NT) / H;
     long units = (big + 7) / 8 * small_units;          // per XCD
     if (units > 32) units = 32;                        // 32 CUs per XCD, one workgroup each
-    hipLaunchKernelGGL((k_fgemm<MODE>), dim3((unsigned)(8 * units)), dim3(512), kFixLds, st, g);
+    hipLaunchKernelGGL((k_fgemm<MODE>), dim3((unsigned)(8 * units)), dim3(512), lds, st, g);
     MCQ_LAUNCH_CHECK();
     return 0;
 }
@@ -284,9 +286,18 @@ int launch_xc(const int8_t *xf, const int *xe, long B, const int8_t *Cf, const i
     return launch_fgemm<FG_STORE>(g, st);
 }
 
-// logits[b][r] = fixdot(x_b, W_r) * lscale + bias[r] (stored when logits != nullptr) and the arg max per codebook
+// MCQ_EXACT_LOGITS=1: the initial codes from the full ten-product kernel (same-box A/B of the screened path; identical results)
+inline bool exact_logits_forced() {
+    static const bool on = getenv("MCQ_EXACT_LOGITS") && atoi(getenv("MCQ_EXACT_LOGITS")) != 0;
+    return on;
+}
+
+// logits[b][r] = fixdot(x_b, W_r) * lscale + bias[r] (stored when logits != nullptr) and the arg max per codebook.
+// und_cnt != nullptr (arg max only): six limb products decide the winner where they can (k_fgemm<FG_SCREEN>), the pairs they
+// cannot decide are listed in und_list (room for B * N entries of two words; *und_cnt is zero on entry) and redone exactly by k_fscreen_recheck
 int launch_logits(const int8_t *xf, const int *xe, long B, const Prepared &P, int N, int K, int D, float lscale,
-                  const float *lscale_ptr, float *logits, void *idx, hipStream_t st) {
+                  const float *lscale_ptr, float *logits, void *idx, hipStream_t st, unsigned *und_cnt = nullptr,
+                  unsigned *und_list = nullptr) {
     const long nk = (long)N * K;
     FixGemm g{};
     g.A = P.Wf; g.ea = P.We; g.RA = fix_round_rows(nk); g.M = nk;
@@ -295,7 +306,19 @@ int launch_logits(const int8_t *xf, const int *xe, long B, const Prepared &P, in
     g.walk_rows = 1;
     g.bias = P.bias; g.wmu = P.wmu; g.lscale = lscale; g.lscale_ptr = lscale_ptr;
     g.logits = logits; g.ldo = nk; g.idx = idx; g.idx_wide = K > 256 ? 1 : 0; g.K = K; g.ncb = N;
-    return launch_fgemm<FG_LOGITS>(g, st);
+    if (und_cnt == nullptr) return launch_fgemm<FG_LOGITS>(g, st);
+    if (logits != nullptr) return MCQ_EINVAL;
+    g.und_cnt = und_cnt; g.und_list = und_list; g.und_cap = (unsigned)(B * N);
+    const int rc = launch_fgemm<FG_SCREEN>(g, st);
+    if (rc) return rc;
+    FixRecheck r{};
+    r.W = P.Wf; r.X = xf; r.ew = P.We; r.ex = xe; r.RW = g.RA; r.RX = g.RB; r.Dq = g.Dq;
+    r.bias = P.bias; r.wmu = P.wmu; r.lscale_ptr = lscale_ptr; r.lscale = lscale;
+    r.idx = idx; r.idx_wide = g.idx_wide; r.K = K; r.ncb = N; r.cnt = und_cnt; r.list = und_list; r.cap = g.und_cap;
+    const long waves = B * N;          // a wave per pair at most, 4,096 waves (16 per CU) striding over the list at the most
+    hipLaunchKernelGGL(k_fscreen_recheck, dim3((unsigned)(waves < 4096 ? (waves + 3) / 4 : 1024)), dim3(256), 0, st, r);
+    MCQ_LAUNCH_CHECK();
+    return 0;
 }
 
 // ---------------------------------------------------------------- the refinement pass
@@ -421,7 +444,7 @@ int launch_tf_comb(int kh, int kc, const float *E, const TfLists &L, long B, int
 enum { CAT_LOGITS = 0, CAT_XX = 1, CAT_STAGE0 = 2, CAT_XC = 3, CAT_LEVEL0 = 4, CAT_LEVEL1 = 5, CAT_TABLES = 6, CAT_COMBINE = 7,
        CAT_TABLES_UP = 8, CAT_COMBINE_UP = 9, CAT_ER = 10, CAT_LEVEL1_FUSED = 11, CAT_TAIL = 12, CAT_COUNT = 13 };
 const char *const kCatNames[CAT_COUNT] = {
-    "logits_product_argmax",      // k_fgemm<FG_LOGITS>
+    "logits_product_argmax",      // k_fgemm<FG_LOGITS>, or k_fgemm<FG_SCREEN> + k_fscreen_recheck
     "frames_to_limbs",            // k_fix_rows
     "stage0_tables",              // k_tf_stage0 / k_tf_stage0_k16
     "xc_product",                 // k_fgemm<FG_STORE>
@@ -589,10 +612,16 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
         const int xh = (flags & MCQ_ENCODE_X_FP16) ? 1 : 0;   // rows of 2-byte elements
         const float *xc = xh ? reinterpret_cast<const float *>(reinterpret_cast<const uint16_t *>(x) + lo * D) : x + lo * D;
         int rc;
+        // codes only: the initial arg max from six of the ten limb products, the pairs they leave open redone exactly (same
+        // codes).  The list lies in the x.C products, which the launch after the recheck writes; its counter is the last
+        // of the 64 pass counters (passes use the first 60), cleared by the frames' limb kernel
+        const bool screen = init_idx == nullptr && logits_out == nullptr && (flags & MCQ_ENCODE_EXACT_LOGITS) == 0 &&
+                            !exact_logits_forced() && (size_t)Bc * N < ((size_t)1 << 31);
+        unsigned *const und_cnt = reinterpret_cast<unsigned *>(w.cnt + 63), *const und_list = reinterpret_cast<unsigned *>(w.XC);
         // the frames as limb planes, centered (x - mean: both products of the call read them; |x - mean|^2 rides along)
         if (init_idx == nullptr || iters > 0) {
             if (prof) prof->begin(CAT_XX);
-            rc = launch_fix_rows(xc, xh, Bc, D, D, w.xf, w.xe, w.xx, st, P.mean);
+            rc = launch_fix_rows(xc, xh, Bc, D, D, w.xf, w.xe, w.xx, st, P.mean, screen ? und_cnt : nullptr);
             if (rc) return rc;
             if (prof) prof->end(CAT_XX);
         }
@@ -605,7 +634,7 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
             if (prof) prof->begin(CAT_LOGITS);
             rc = launch_logits(w.xf, w.xe, Bc, P, N, K, D, lscale,
                                (flags & MCQ_ENCODE_LSCALE_FROM_PREPARED) ? P.scales + 1 : nullptr,
-                               logits_out ? logits_out + lo * N * K : nullptr, w.idx, st);
+                               logits_out ? logits_out + lo * N * K : nullptr, w.idx, st, screen ? und_cnt : nullptr, und_list);
             if (rc) return rc;
             if (prof) prof->end(CAT_LOGITS);
         }

@@ -29,6 +29,7 @@ constexpr int kFixSlot = 32768;        // 2 operands x 8 planes x 2 KB
 constexpr int kFixOperand = 16384;
 constexpr int kFixInfo = kFixRing * kFixSlot;      // per-tile row / column data after the ring (4 KB)
 constexpr int kFixLds = kFixInfo + 4096;
+constexpr int kFixLdsScreen = kFixLds + 1024;      // k_fgemm<FG_SCREEN>: two more arg-max exchange arrays after the info area
 
 __host__ __device__ inline long fix_round_rows(long r) { return (r + kFixTile - 1) / kFixTile * kFixTile; }
 __host__ __device__ inline int fix_round_cols(int d) { return (d + kFixColPad - 1) / kFixColPad * kFixColPad; }
@@ -69,6 +70,7 @@ struct FixRowsArgs {
     // kernel has in its registers anyway (the classifier rows against the data mean: what centering the frame takes out of a logit)
     const float *dot_vec;
     float *dot_out;
+    unsigned *clear;      // optional: one word this launch sets to zero (the counter of the screened logits' recheck list)
 };
 
 template <int RW, bool DOT>      // DOT: also the rows' fixed-point products with a.dot_vec (the classifier rows of mcq_prepare)
@@ -87,6 +89,7 @@ __device__ __forceinline__ void fix_rows_body(const FixRowsArgs &a, unsigned bid
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long row0 = (long)bid * RW;
     if (bias_src && tid < RW && row0 + tid < R) bias_dst[row0 + tid] = bias_src[row0 + tid];
+    if (a.clear && bid == 0 && tid == 0) *a.clear = 0u;
     const _Float16 *srch = reinterpret_cast<const _Float16 *>(src);
     const bool vec_ok = ((ld & 3) == 0) && ((D & 3) == 0) && ((reinterpret_cast<uintptr_t>(src) & (xh ? 7 : 15)) == 0);
     auto load4 = [&](long row, int q) -> f32x4 {      // float4 group q of a row, zero past D
@@ -264,7 +267,9 @@ __global__ void __launch_bounds__(256) k_fix_rows2(const FixRowsArgs a, const Fi
 
 // ------------------------------------------------------------------ the GEMM
 // out-of-kernel description of what the epilogue does with a tile of t values
-enum { FG_STORE = 0, FG_LOGITS = 1 };
+// FG_SCREEN: the logits product for callers that want the ARG MAX only, from limbs 0-2 of both operands (six limb
+// products, T_0 .. T_2); pairs whose winner the dropped class T_3 could change go to a list for k_fscreen_recheck
+enum { FG_STORE = 0, FG_LOGITS = 1, FG_SCREEN = 2 };
 
 struct FixGemm {
     const int8_t *A, *B;           // limb planes: A rows are the tile rows (M), B rows the tile columns (N)
@@ -288,6 +293,10 @@ struct FixGemm {
     void *idx;                     // uint8 [N cols][ncb], or uint16 when idx_wide (codebooks of more than 256 entries)
     int idx_wide;
     int K, ncb;
+    // FG_SCREEN: the undecided (frame, codebook) pairs, two words each (col * ncb + codebook; the second's entry, bit 31: more than
+    // two contenders), appended at atomicAdd(und_cnt, 1)
+    unsigned *und_cnt, *und_list;
+    unsigned und_cap;
 };
 
 __device__ __forceinline__ void fg_store_idx(const FixGemm &g, long pos, long entry) {
@@ -313,12 +322,15 @@ template <int MODE>
 __global__ void __launch_bounds__(512)
 k_fgemm(const FixGemm g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // FG_SCREEN runs the same walk with limbs 0-2 only: NL pieces per wave and stage, NL accumulator sets, 6 limb pairs
+    constexpr bool SCREEN = MODE == FG_SCREEN, LOGITS = MODE != FG_STORE;
+    constexpr int NL = SCREEN ? 3 : 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;          // 64-row half, 32-column quarter of the tile
     const int r32 = lane & 31, kh = lane >> 5;
     const long MT = g.RA / kFixTile, NT = g.RB / kFixTile;
     // K = 256 logits: the two row tiles of a codebook are consecutive tiles of one workgroup (running arg max in registers)
-    const int H = (MODE == FG_LOGITS && g.K > kFixTile) ? g.K / kFixTile : 1;
+    const int H = (LOGITS && g.K > kFixTile) ? g.K / kFixTile : 1;
     const long big = g.walk_rows ? NT : MT, small_units = (g.walk_rows ? MT : NT) / H;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
     auto tile_of = [&](long t, long &m0, long &n0) -> bool {      // t-th tile of this workgroup
@@ -329,7 +341,7 @@ k_fgemm(const FixGemm g) {
         n0 = (g.walk_rows ? bt : st) * kFixTile;
         return bt < big;
     };
-    i32x16 acc[2][4];
+    i32x16 acc[2][NL];
     const int nst = g.Dq / 32;
     // this wave's 4 pieces of a stage (1 KB each): waves 0..3 bring operand A, 4..7 operand B; bit 1 of the wave picks the
     // 16-column chunk, bit 0 the 64-row half, g4 = 0..3 the limb plane
@@ -357,7 +369,7 @@ k_fgemm(const FixGemm g) {
     // arg-max exchange, [640..767] wmu.  (Rows past M read whatever follows the bias / wmu inside `prepared`: they never reach an
     // output.)
     auto issue_info = [&](long m0, long n0) {
-        if (wu < (MODE == FG_LOGITS ? 8 : 4)) {
+        if (wu < (LOGITS ? 8 : 4)) {
             const void *src = wu < 2 ? static_cast<const void *>(g.ea + m0 + 64 * wu)
                                      : (wu < 4 ? static_cast<const void *>(g.eb + n0 + 64 * (wu - 2))
                                                : (wu < 6 ? static_cast<const void *>(g.bias + m0 + 64 * (wu - 4))
@@ -374,16 +386,17 @@ k_fgemm(const FixGemm g) {
     long m0, n0, m0n = 0, n0n = 0;
     if (!tile_of(0, m0, n0)) return;
     const int8_t *pcur = base_of(m0, n0), *pnext = pcur;
-    auto step = [&](int st, const i32x4 (&a)[2][4], const i32x4 (&b)[4], i32x4 (&an)[2][4], i32x4 (&bn)[4]) {
+    auto step = [&](int st, const i32x4 (&a)[2][NL], const i32x4 (&b)[NL], i32x4 (&an)[2][NL], i32x4 (&bn)[NL]) {
         const char *base = smem + ((st + 1) % kFixRing) * kFixSlot;
         // (after the last tile the stage four ahead does not exist: the pieces are requested all the same, from the start of
         // the current tile (pnext == pcur then) into a slot nobody reads any more -- no branch round the DMA)
         const int8_t *p = (st + 4 < nst) ? pcur + (st + 4) * sstride : pnext + (st + 4 - nst) * sstride;
         constexpr int PI[10] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3};      // limb pairs (i, j), i + j <= 3, dealt 3, 3, 2, 2
         constexpr int PJ[10] = {0, 1, 0, 2, 1, 0, 3, 2, 1, 0};
-        constexpr int LO[5] = {0, 3, 6, 8, 10};
+        // (FG_SCREEN: the first six pairs, i + j <= 2, dealt 2, 2, 2 -- every pair of a group has its limbs read by then)
+        constexpr int LO[5] = {0, SCREEN ? 2 : 3, SCREEN ? 4 : 6, SCREEN ? 6 : 8, 10};
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
+        for (int g4 = 0; g4 < NL; ++g4) {
             issue1(p, st, g4);
 #pragma unroll
             for (int t = 0; t < 2; ++t)
@@ -398,16 +411,18 @@ k_fgemm(const FixGemm g) {
             __builtin_amdgcn_sched_barrier(0);      // (everything requested up front instead: 0.59 against 0.53 ms)
         }
     };
-    i32x4 a0[2][4], b0[4], a1[2][4], b1[4];
+    i32x4 a0[2][NL], b0[NL], a1[2][NL], b1[NL];
     issue_info(m0, n0);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) issue1(pcur + q * sstride, q, g4);
-    asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+        for (int g4 = 0; g4 < NL; ++g4) issue1(pcur + q * sstride, q, g4);
+    // stage 0 has landed when only the NL pieces of each of the three later stages are outstanding
+    if constexpr (SCREEN) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 #pragma unroll
-    for (int l = 0; l < 4; ++l) {
+    for (int l = 0; l < NL; ++l) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
             a0[t][l] = *reinterpret_cast<const i32x4 *>(smem + (kh * 4 + l) * 2048 + (64 * wm + 32 * t + r32) * 16);
@@ -418,30 +433,35 @@ k_fgemm(const FixGemm g) {
     // running arg max of a codebook that spans several row tiles: per lane, its column
     float runv = 0.f;
     int runk = 0;
+    float runs = 0.f, runt = 0.f, runq = 0.f;      // FG_SCREEN: the running second / third value, magnitude, second's row and
+    int runj = 0, rune = 0;                        // largest row exponent (see the epilogue)
     for (long t = 0;; ++t) {
         const bool has_next = tile_of(t + 1, m0n, n0n);
         pnext = has_next ? base_of(m0n, n0n) : pcur;
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int s = 0; s < 4; ++s)
+            for (int s = 0; s < NL; ++s)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) acc[a][s][v] = 0;
         // before the reads of stage st + 1: it has landed everywhere and every wave has left slot st % ring.  Two later
-        // stages stay in flight
+        // stages stay in flight: 2 * NL pieces of this wave
         for (int st = 0; st < nst; st += 2) {
-            asm volatile("s_waitcnt vmcnt(8)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+            if constexpr (SCREEN) asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(8)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             step(st, a0, b0, a1, b1);
-            asm volatile("s_waitcnt vmcnt(8)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+            if constexpr (SCREEN) asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(8)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             step(st + 1, a1, b1, a0, b0);      // (reads past the end of the last tile hit a slot nobody uses)
         }
         // ---- epilogue.  The info words of this tile landed during its first steps (requested at its start, made visible by
         // the step barriers)
         auto value = [&](int ta, int v, int e) -> float {
-            float tt = (float)acc[ta][3][v];
-            tt = __builtin_fmaf((float)acc[ta][2][v], 256.0f, tt);
+            float tt;
+            if constexpr (SCREEN) tt = __fmul_rn((float)acc[ta][2][v], 256.0f);      // t' of the six products (exact: a power of two)
+            else tt = __builtin_fmaf((float)acc[ta][2][v], 256.0f, (float)acc[ta][NL - 1][v]);
             tt = __builtin_fmaf((float)acc[ta][1][v], 65536.0f, tt);
             tt = __builtin_fmaf((float)acc[ta][0][v], 16777216.0f, tt);
             return ldexpf(tt, e);
@@ -478,6 +498,150 @@ k_fgemm(const FixGemm g) {
                         const float val = value(ta, v, er[ta][v >> 2][v & 3] + ecol);
                         if (col_ok && ro < rows_left) orow[(long)ro * g.ldo] = val;
                     }
+            }
+        } else if constexpr (SCREEN) {
+            // The screened logit of a row is the chain of FG_LOGITS applied to t' (limbs 0-2) instead of t (all ten products):
+            //     y = ldexp(t, e)   s1 = fl(y + wmu)   s2 = fl(s1 * ls)   L = fl(s2 + bias)        (y', s1', s2', L' from t')
+            // The winner of (frame, codebook) is DECIDED when best' - second' > margin, where margin >= 2 max_r |L_r - L'_r|:
+            // then L_b - L_r >= (L'_b - L'_r) - |L_b - L'_b| - |L_r - L'_r| > 0 for every other row r, so the exact first arg max is b.
+            // Everything else (equal screened values included: their difference is 0) goes to the list of k_fscreen_recheck.
+            //
+            // Bound of |L - L'| for one row.  u = 2^-24, A = 128 * 128 * Dq (Dq columns of limb products, |limb| <= 128), so
+            // |T_s| <= (s + 1) A.  Both chains convert the SAME integers T_0, T_1, T_2 to the same floats c_0, c_1, c_2
+            // (|c_s| <= (s + 1) A (1 + u)); they differ in
+            //     exact:     r3 = fl(T_3)   r2 = fl(c_2 2^8 + r3)   r1 = fl(c_1 2^16 + r2)    t  = fl(c_0 2^24 + r1)
+            //     screened:                 r2' = c_2 2^8 (exact)   r1' = fl(c_1 2^16 + r2')  t' = fl(c_0 2^24 + r1')
+            // (a) |r3| <= 4 A (1 + u); |r2 - r2'| <= |r3| + u |c_2 2^8 + r3| <= A (1 + u) (4 + 772 u).
+            // (b) |r1 - r1'| <= |r2 - r2'| + u (|c_1 2^16 + r2| + |c_1 2^16 + r2'|) <= A (4 + 2^-5).
+            // (c) |t - t'| <= |r1 - r1'| + u (|t| + |t'|) / (1 - u), and |t| <= |t'| + |t - t'|, hence
+            //     |t - t'| <= 4.0625 A + 2^-22 |t'|;  |t'| <= 2^24 A (1 + 2^-7 + 2^-14) (1 + u)^4, so |t - t'| <= 8.1 A =: dt.
+            // (d) ldexp is exact (a result in the subnormal range is rounded by at most 2^-150: the constant added last covers
+            //     it), so |y - y'| <= d = dt 2^e, e = ea[row] + eb[col] - 36.  Rounding to nearest is monotone and moves a value
+            //     x by at most u |x|; for reals p, p' that gives |fl(p) - fl(p')| <= |p - p'| (1 + u) + 2 u |fl(p')| / (1 - u).
+            //     Applied three times (ls > 0 scales a difference by ls):
+            //     |L - L'| <= (1 + u)^3 ls d + 2 u (1 + u)^2 / (1 - u)^2 (ls |s1'| + |s2'| + |L'|),  ls |s1'| <= |s2'| / (1 - u)
+            //             <= 1.000001 ls d + 2^-22 * 3 max(|s2'|, |L'|).
+            // margin = 16.5 A 2^e ls + 2^-19 q + 2^-120, with e from the LARGEST row exponent of the tile(s) of the codebook and q the
+            // largest max(|s2'|, |L'|) among the rows this merge path has seen for the frame (a superset of the codebook's rows):
+            // 16.5 > 2 * 8.1 * 1.000001 and 2^-19 > 2 * 3 * 2^-22 leave 1.8 % and 25 % for the few fp32 roundings in forming the
+            // margin and the difference.  An infinite or NaN margin or difference fails the test and lists the pair.
+            const float ls = g.lscale_ptr ? *g.lscale_ptr : g.lscale;
+            // An undecided pair whose THIRD-best screened value is below best' - margin has two contenders only (every row whose
+            // exact logit can reach the winner's has L' >= best' - margin): the list carries the second's row, and the recheck
+            // forms two exact logits instead of K.  Which of two equal screened values counts as the better one is immaterial
+            // here: a decided pair has best' > second', an undecided one is settled by exact values (lower row on equal ones).
+            float bv[4], sv[4], tv[4], qm = 0.f;   // best / second / third value of the 16-row group, this lane's 8 rows of it
+            int bk[4], sk[4];                      // rows of the best and the second
+            const long col = n0 + cbase;
+#pragma unroll
+            for (int ta = 0; ta < 2; ++ta) {
+#pragma unroll
+                for (int v4 = 0; v4 < 4; ++v4) {
+                    const f32x4 br4 = *reinterpret_cast<const f32x4 *>(&infof[256 + rbase + 32 * ta + 8 * v4]);
+                    const f32x4 wm4 = *reinterpret_cast<const f32x4 *>(&infof[640 + rbase + 32 * ta + 8 * v4]);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int v = 4 * v4 + c;
+                        const int rl = rbase + 32 * ta + 8 * v4 + c;
+                        const float s2 = __fmul_rn(__fadd_rn(value(ta, v, er[ta][v4][c] + ecol), wm4[c]), ls);
+                        const float val = __fadd_rn(s2, br4[c]);
+                        qm = fmaxf(qm, fmaxf(fabsf(s2), fabsf(val)));
+                        const int gi = 2 * ta + (v4 >> 1);
+                        if ((v4 & 1) == 0 && c == 0) { bv[gi] = val; bk[gi] = sk[gi] = rl; sv[gi] = tv[gi] = -INFINITY; }
+                        else {
+                            const bool c1 = val > bv[gi], c2 = val > sv[gi];
+                            tv[gi] = __builtin_amdgcn_fmed3f(tv[gi], sv[gi], val);      // (tv <= sv <= bv: the middle one is the new third,
+                            sv[gi] = __builtin_amdgcn_fmed3f(sv[gi], bv[gi], val);      //  the new second)
+                            sk[gi] = c1 ? bk[gi] : (c2 ? rl : sk[gi]);
+                            bk[gi] = c1 ? rl : bk[gi];
+                            bv[gi] = fmaxf(bv[gi], val);
+                        }
+                    }
+                }
+            }
+            // the largest row exponent of this tile (every wave forms it)
+            int em = info[lane] > info[lane + 64] ? info[lane] : info[lane + 64];
+            for (int s = 32; s >= 1; s >>= 1) { const int o = __shfl_xor(em, s, 64); em = o > em ? o : em; }
+            // the three largest values (and the rows of two) of the union of two disjoint sets of rows, each given by its own three
+            auto merge = [](float &b1, int &k1, float &s1, int &j1, float &t1, float b2, int k2, float s2, int j2, float t2) {
+                if (b2 > b1) {      // the set with the larger best first
+                    float f = b1; b1 = b2; b2 = f;
+                    f = s1; s1 = s2; s2 = f;
+                    t1 = t2;        // (the other set's third is below its second: it cannot be among the union's three)
+                    int i = k1; k1 = k2; k2 = i;
+                    j1 = j2;
+                }
+                if (b2 > s1) { t1 = fmaxf(s1, s2); s1 = b2; j1 = k2; }      // b1 >= b2 > s1
+                else t1 = fmaxf(t1, b2);                                   // b1 >= s1 >= b2
+            };
+            const float cA = 16.5f * 16384.0f * (float)g.Dq;
+            auto undecided = [&](float v, float s, float q, int e) {
+                const float margin = __fadd_rn(__fadd_rn(__fmul_rn(ldexpf(cA, e + ecol), ls), __fmul_rn(q, 1.9073486328125e-6f)), 7.5231638452626401e-37f);
+                return !(__fsub_rn(v, s) > margin);
+            };
+            // a list entry: the pair and the second's entry of the codebook, bit 31 set when more than two rows contend
+            auto append = [&](long pos, unsigned second_entry, bool many) {
+                const unsigned at = atomicAdd(g.und_cnt, 1u);
+                if (at < g.und_cap) {
+                    g.und_list[2 * (size_t)at] = (unsigned)pos;
+                    g.und_list[2 * (size_t)at + 1] = second_entry | (many ? 0x80000000u : 0u);
+                }
+            };
+            const int K = g.K;
+#pragma unroll
+            for (int gi = 0; gi < 4; ++gi)
+                merge(bv[gi], bk[gi], sv[gi], sk[gi], tv[gi], __shfl_xor(bv[gi], 32, 64), __shfl_xor(bk[gi], 32, 64),
+                      __shfl_xor(sv[gi], 32, 64), __shfl_xor(sk[gi], 32, 64), __shfl_xor(tv[gi], 32, 64));
+            qm = fmaxf(qm, __shfl_xor(qm, 32, 64));
+            if (K >= 32) {
+                merge(bv[0], bk[0], sv[0], sk[0], tv[0], bv[1], bk[1], sv[1], sk[1], tv[1]);
+                merge(bv[2], bk[2], sv[2], sk[2], tv[2], bv[3], bk[3], sv[3], sk[3], tv[3]);
+            }
+            if (K >= 64) merge(bv[0], bk[0], sv[0], sk[0], tv[0], bv[2], bk[2], sv[2], sk[2], tv[2]);
+            if (K <= 64) {
+                if (kh == 0) {
+                    const int span = K / 16;
+#pragma unroll
+                    for (int gi = 0; gi < 4; ++gi) {
+                        const long row = m0 + bk[gi];
+                        if ((gi % span) == 0 && col < g.N && row < g.M) {
+                            fg_store_idx(g, col * g.ncb + row / K, row % K);
+                            if (undecided(bv[gi], sv[gi], qm, em))
+                                append(col * g.ncb + row / K, (unsigned)((m0 + sk[gi]) % K), undecided(bv[gi], tv[gi], qm, em));
+                        }
+                    }
+                }
+            } else {
+                // (words 768 .. 1023 of the info area, where no DMA piece lands, and the kilobyte after it)
+                float *exv = infof + 384, *exs = infof + 768, *exq = infof + 896;
+                int *exk = info + 384 + 128;
+                float *ext = reinterpret_cast<float *>(smem + kFixInfo + 4096);
+                int *exj = reinterpret_cast<int *>(smem + kFixInfo + 4096 + 512);
+                if (wm == 1 && kh == 0) {
+                    exv[cbase] = bv[0]; exk[cbase] = bk[0]; exs[cbase] = sv[0]; exq[cbase] = qm;
+                    ext[cbase] = tv[0]; exj[cbase] = sk[0];
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                if (wm == 0 && kh == 0) {
+                    const int hf = (int)(t % H);
+                    float v = bv[0], s = sv[0], t3 = tv[0], q = fmaxf(qm, exq[cbase]);
+                    int kk = bk[0], jj = sk[0];
+                    merge(v, kk, s, jj, t3, exv[cbase], exk[cbase], exs[cbase], exj[cbase], ext[cbase]);
+                    kk += (int)m0;      // rows of the whole matrix from here on
+                    jj += (int)m0;
+                    if (hf > 0) {
+                        merge(v, kk, s, jj, t3, runv, runk, runs, runj, runt);
+                        q = fmaxf(q, runq);
+                        em = em > rune ? em : rune;
+                    }
+                    runv = v; runk = kk; runs = s; runj = jj; runt = t3; runq = q; rune = em;
+                    const long k = kk;
+                    if (hf == H - 1 && col < g.N && k < g.M) {
+                        fg_store_idx(g, col * g.ncb + k / K, k % K);
+                        if (undecided(v, s, q, em)) append(col * g.ncb + k / K, (unsigned)(jj % K), undecided(v, t3, q, em));
+                    }
+                }
             }
         } else {
             const float ls = g.lscale_ptr ? *g.lscale_ptr : g.lscale;
@@ -568,6 +732,97 @@ k_fgemm(const FixGemm g) {
         issue_info(m0, n0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the pieces still on their way to this workgroup's LDS
+}
+
+// ------------------------------------------------------------------ the exact recheck of the screened arg max
+// The pairs k_fgemm<FG_SCREEN> could not decide: a wave per listed (frame, codebook) recomputes the logits of the contenders from
+// the full ten limb products (integer dot products of the limb planes, the same three fmas and the same chain as the FG_LOGITS
+// epilogue) and overwrites the code with the first arg max.  Two contenders (the screened winner, whose entry is the code
+// already written, and the second the list names): half a wave per row, a lane per 16-column chunk.  More than two: all K
+// rows, a lane per row (K * Dq * 4 bytes of planes per pair: rare by construction, slow when it is not).  A fixed grid strides
+// over the list; the count is read on the device.
+struct FixRecheck {
+    const int8_t *W, *X;           // limb planes of the classifier rows / of the frames
+    const int *ew, *ex;
+    long RW, RX;                   // padded row counts
+    int Dq;
+    const float *bias, *wmu, *lscale_ptr;
+    float lscale;
+    void *idx;
+    int idx_wide;
+    int K, ncb;
+    const unsigned *cnt, *list;
+    unsigned cap;
+};
+
+__global__ void __launch_bounds__(256) k_fscreen_recheck(const FixRecheck a) {
+    const int lane = threadIdx.x & 63;
+    const unsigned wv = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), nwv = gridDim.x * 4;
+    unsigned n = *a.cnt;
+    n = n < a.cap ? n : a.cap;
+    const float ls = a.lscale_ptr ? *a.lscale_ptr : a.lscale;
+    const int K = a.K, nch = a.Dq / 16;
+    for (unsigned i = wv; i < n; i += nwv) {
+        const unsigned pos = a.list[2 * (size_t)i], snd = a.list[2 * (size_t)i + 1];
+        const long col = pos / (unsigned)a.ncb;
+        const int cb = (int)(pos % (unsigned)a.ncb);
+        const int ecol = a.ex[col] - 36;
+        auto chunk = [&](int (&T)[4], int c, long row) {      // the ten limb products of one 16-column chunk
+            i32x4 xl[4], wl[4];
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                xl[l] = *reinterpret_cast<const i32x4 *>(a.X + (((long)c * 4 + l) * a.RX + col) * 16);
+                wl[l] = *reinterpret_cast<const i32x4 *>(a.W + (((long)c * 4 + l) * a.RW + row) * 16);
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int q = 0; p + q < 4; ++q)
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) T[p + q] = __builtin_amdgcn_sdot4(wl[p][d], xl[q][d], T[p + q], false);
+        };
+        auto logit = [&](const int (&T)[4], long row) -> float {
+            float tt = (float)T[3];
+            tt = __builtin_fmaf((float)T[2], 256.0f, tt);
+            tt = __builtin_fmaf((float)T[1], 65536.0f, tt);
+            tt = __builtin_fmaf((float)T[0], 16777216.0f, tt);
+            return __fadd_rn(__fmul_rn(__fadd_rn(ldexpf(tt, a.ew[row] + ecol), a.wmu[row]), ls), a.bias[row]);
+        };
+        float bv = -INFINITY;
+        int bk = 0x7fffffff;
+        if ((snd & 0x80000000u) == 0) {
+            const int first = a.idx_wide ? (int)static_cast<const uint16_t *>(a.idx)[pos] : (int)static_cast<const uint8_t *>(a.idx)[pos];
+            const int j = (lane < 32) ? first : (int)snd;
+            const long row = (long)cb * K + j;
+            int T[4] = {0, 0, 0, 0};
+            for (int c = lane & 31; c < nch; c += 32) chunk(T, c, row);
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                for (int sft = 16; sft >= 1; sft >>= 1) T[p] += __shfl_xor(T[p], sft, 64);      // exact integers, within each half
+            bv = logit(T, row);
+            bk = j;
+        } else {
+            for (int j = lane; j < K; j += 64) {      // ascending rows per lane: a later one wins only with a larger value
+                const long row = (long)cb * K + j;
+                int T[4] = {0, 0, 0, 0};
+                // (four chunks' loads in flight: one such pair among thousands of two-row ones is the launch's critical path, and a
+                // chunk at a time it took 60 us)
+#pragma unroll 4
+                for (int c = 0; c < nch; ++c) chunk(T, c, row);
+                const float val = logit(T, row);
+                if (j == lane || val > bv) { bv = val; bk = j; }
+            }
+        }
+        for (int s = 32; s >= 1; s >>= 1) {
+            const float ov = __shfl_xor(bv, s, 64);
+            const int ok = __shfl_xor(bk, s, 64);
+            if ((ov > bv) | ((ov == bv) & (ok < bk))) { bv = ov; bk = ok; }
+        }
+        if (lane == 0) {
+            if (a.idx_wide) static_cast<uint16_t *>(a.idx)[pos] = (uint16_t)bk;
+            else static_cast<uint8_t *>(a.idx)[pos] = (uint8_t)bk;
+        }
+    }
 }
 
 }  // namespace mcq

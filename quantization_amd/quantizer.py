@@ -104,6 +104,10 @@ class Quantizer(nn.Module):
         # pass is a deterministic map) and skip the remaining passes; same codes, less work.  On by
         # default; False runs every pass on every vector (MCQ_ENCODE_ALL_PASSES)
         self.skip_fixed_points = True
+        # (not in the reference) the initial codes come from six of the ten limb products of a logit wherever their error
+        # bound decides the arg max, the rest is recomputed exactly; same codes.  True forces the ten-product kernel
+        # (MCQ_ENCODE_EXACT_LOGITS)
+        self.exact_logits = False
         self._pinned_scales = None   # pin_scale_factors()
         self._prep = None       # (key, device buffer) of derived state for the kernels
         self._ws = None         # cached encode workspace (device uint8 tensor)
@@ -317,7 +321,7 @@ class Quantizer(nn.Module):
                                  out.data_ptr() if as_bytes else None, None if as_bytes else out.data_ptr(),
                                  ws.data_ptr(), ws.numel(), st,
                                  (0 if getattr(self, "skip_fixed_points", True) else _lib.MCQ_ENCODE_ALL_PASSES) | self._scale_flags |
-                                 (4 if x_fp16 else 0))
+                                 (4 if x_fp16 else 0) | (_lib.MCQ_ENCODE_EXACT_LOGITS if getattr(self, "exact_logits", False) else 0))
         _lib.check(rc, "mcq_encode")
         return out
 
