@@ -350,6 +350,38 @@ int mcq_search_scan_metric(const float *tables, long Q, const uint8_t *codes, co
 int mcq_code_rnorms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *rnorms_out, void *stream);
 int mcq_rnorms_from_norms(const float *norms, long B, float *rnorms_out, void *stream);
 
+/* ---- range search over stored codes -----------------------------------------------
+ * Every stored vector within a threshold of a query, instead of the k best.  Same tables, same codes, same per-candidate
+ * array w and the same score[q][b] as rule 3' defines it under the metric (L2 S + w[b], IP S, cosine S * w[b]); rules 1, 2,
+ * 3, 3' and 6 hold as they stand, no k appears anywhere.  The contract continues (the tests restate rules 7 and 8 in numpy
+ * and compare bit for bit):
+ *   7. stored vector b is LISTED for query q iff score[q][b] <= thr[q]: one fp32 comparison, inclusive.  A NaN on either side
+ *      lists nothing.  thr is float[Q], one threshold per query, in the score domain of the scan (smaller = nearer under all
+ *      three metrics: an inner product >= s is thr = -2 s, a cosine >= c is thr = -2 c |q|, a squared distance <= r is
+ *      thr = r - |q|^2).
+ *   8. the output is CSR.  lims is int64[Q + 1], lims[0] = 0, lims[q+1] - lims[q] = the number of b listed for q.  The entries
+ *      of query q occupy [lims[q], lims[q+1]) IN ASCENDING POSITION b, as (score fp32, position int64).  The output is a
+ *      function of scores and thresholds alone: the same inputs give the same bits (rule 5; the only sums are of integers).
+ *   9. Q == 0 or B == 0: lims is all zeros and nothing else is written (lims itself is always needed).  Every argument is
+ *      rejected before anything touches the device, with the status codes and the domain of mcq_search_scan_metric: one-byte
+ *      codes (K <= 256), N a power of two <= 64, B <= 2^31 - 1 (MCQ_EUNSUPPORTED past these), codes aligned to min(N, 16)
+ *      bytes, w == NULL only with MCQ_SEARCH_IP, an unknown metric MCQ_EINVAL, a short workspace MCQ_EWORKSPACE.
+ * The size of the result depends on the data, so the call is split where the caller allocates:
+ *   count  -> lims (device memory, int64[Q + 1]), and per-(query, slice, wave) start offsets in the workspace;
+ *   the caller reads lims[Q] (one synchronisation), allocates out_score float[total] and out_index int64[total];
+ *   fill   with the SAME arguments, the same lims and the same, untouched workspace -> the entries.
+ * fill stores no entry whose slot is outside [0, capacity): whatever lims and the workspace hold, nothing is written out of
+ * bounds (a caller with less room than lims[Q] gets a truncated, otherwise correct CSR).  capacity == 0 writes nothing.
+ * Both sweeps compute a score with one and the same routine, so they agree about every borderline candidate.
+ * workspace >= what the size query below returns for (Q, B, N, K): 8 bytes per (query, slice of the store, wave); it does
+ * not depend on D nor on the number of results, and stops growing with B once the slice count reaches its cap.            */
+size_t mcq_search_range_workspace_bytes(long Q, long B, int N, int K);
+int mcq_search_range_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+                           const float *thr, int64_t *lims, void *workspace, size_t workspace_bytes, void *stream);
+int mcq_search_range_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+                          const float *thr, const int64_t *lims, float *out_score, int64_t *out_index, long capacity,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- test / profiling hooks -------------------------------------------------
  * Logits of Quantizer._logits (:277-279) for a batch, fp32 [B][N*K]; used by the
  * parity tests to localise a divergence.                                       */

@@ -23,6 +23,7 @@ SYMBOLS = (
     "mcq_decode_backward_waves", "mcq_decode_backward_u8_ex", "mcq_loss_bwd_waves", "mcq_loss_bwd_ex", "mcq_grad_tail",
     "mcq_search_tables", "mcq_code_norms", "mcq_search_workspace_bytes", "mcq_search_scan",
     "mcq_search_scan_metric", "mcq_code_rnorms", "mcq_rnorms_from_norms",
+    "mcq_search_range_workspace_bytes", "mcq_search_range_count", "mcq_search_range_fill",
 )
 
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
@@ -141,6 +142,14 @@ def lib():
         L.mcq_code_rnorms.argtypes = [vp, i64, vp, i32, i32, i32, vp, vp]
         L.mcq_rnorms_from_norms.restype = i32
         L.mcq_rnorms_from_norms.argtypes = [vp, i64, vp, vp]
+    # (likewise the range search: an older build has none, and calling it raises)
+    if not (_ALT and not hasattr(L, "mcq_search_range_count")):
+        L.mcq_search_range_workspace_bytes.restype = sz
+        L.mcq_search_range_workspace_bytes.argtypes = [i64, i64, i32, i32]
+        L.mcq_search_range_count.restype = i32
+        L.mcq_search_range_count.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, sz, vp]
+        L.mcq_search_range_fill.restype = i32
+        L.mcq_search_range_fill.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, i64, vp, sz, vp]
     L.mcq_last_encode_launches.restype = i32
     L.mcq_profile_encode.restype = i32
     L.mcq_profile_encode.argtypes = [vp, i64, vp, f32, i32, i32, i32, i32, vp, sz, vp, ctypes.POINTER(f32), ctypes.POINTER(i32), i32]

@@ -8,6 +8,7 @@
 #include "mcq_pass16_kernels.h"
 #include "mcq_train_kernels.h"
 #include "mcq_search_kernels.h"
+#include "mcq_range_kernels.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -903,6 +904,115 @@ int launch_scan_qt(const ScanPlan &p, hipStream_t st, const float *tables, int Q
 }  // namespace
 
 
+// ---- range search over stored codes (mcq_range_kernels.h) ---------------------------------------------------------------
+namespace {
+
+// the launch arithmetic of the two sweeps (mirrored by tests/search_range_grid.py): the tile and the slices of scan_plan with
+// kRangeWaves waves per workgroup, and one int64 per (query, slice, wave) of workspace
+struct RangePlan {
+    int qt, qtiles, slices;
+    long per_slice;
+    size_t lds, ws_bytes;
+};
+
+RangePlan range_plan(long Q, long B, int N, int K) {
+    RangePlan p;
+    int cap = kScanQTMax;
+    while (cap > 1 && (size_t)cap * N * K * 4 > (size_t)kScanTableLds) cap /= 2;
+    int qt = 1;
+    while (qt < cap && qt < Q) qt *= 2;
+    p.qt = qt;
+    p.qtiles = (int)((Q + qt - 1) / qt);
+    long cap_slices = kScanTargetBlocks / (p.qtiles > 0 ? p.qtiles : 1);
+    cap_slices = cap_slices < 1 ? 1 : (cap_slices > kScanMaxSlices ? kScanMaxSlices : cap_slices);
+    const long steps = (B + 63) / 64;                                    // steps of 64 candidates; at least one per wave
+    long want = (steps + kRangeWaves - 1) / kRangeWaves;
+    want = want < 1 ? 1 : (want > cap_slices ? cap_slices : want);
+    p.per_slice = (((B + want - 1) / want) + 63) / 64 * 64;
+    if (p.per_slice < 64) p.per_slice = 64;
+    p.slices = (int)((B + p.per_slice - 1) / p.per_slice);
+    p.lds = (size_t)qt * N * K * 4 + (size_t)kRangeWaves * qt * 8;       // the tables, then one slot base per (wave, query)
+    p.ws_bytes = align256((size_t)Q * p.slices * kRangeWaves * 8);
+    return p;
+}
+
+struct RangeArgs {
+    const float *tables;
+    int Q;
+    const uint8_t *codes;
+    const float *w;
+    long B;
+    int N, K, metric;
+    const float *thr;
+    int64_t *ws;
+    const int64_t *lims;
+    float *out_s;
+    int64_t *out_i;
+    long capacity;
+};
+
+template <int QT, int CH, bool FILL>
+int launch_range(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
+    static bool allowed[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
+    if (!allowed[dev] || dev == 63) {
+        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_range_sweep<QT, CH, FILL>),
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                    kScanTableLds + kRangeWaves * kScanQTMax * 8);
+        if (attr != hipSuccess) return (int)attr;
+        allowed[dev] = true;
+    }
+    hipLaunchKernelGGL((k_range_sweep<QT, CH, FILL>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kRangeWaves), p.lds,
+                       st, a.tables, a.Q, a.codes, a.w, a.B, a.N, a.K, a.metric, p.slices, p.per_slice, a.thr, a.ws, a.lims,
+                       a.out_s, a.out_i, a.capacity);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+template <int QT, bool FILL>
+int launch_range_ch(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
+    switch (a.N < 8 ? a.N : 8) {                                          // a candidate's digits arrive in chunks of CH
+        case 1: return launch_range<QT, 1, FILL>(p, st, a);
+        case 2: return launch_range<QT, 2, FILL>(p, st, a);
+        case 4: return launch_range<QT, 4, FILL>(p, st, a);
+        case 8: return launch_range<QT, 8, FILL>(p, st, a);
+    }
+    return MCQ_EUNSUPPORTED;
+}
+
+template <bool FILL>
+int launch_range_qt(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
+    switch (p.qt) {
+        case 1: return launch_range_ch<1, FILL>(p, st, a);
+        case 2: return launch_range_ch<2, FILL>(p, st, a);
+        case 4: return launch_range_ch<4, FILL>(p, st, a);
+        case 8: return launch_range_ch<8, FILL>(p, st, a);
+        case 16: return launch_range_ch<16, FILL>(p, st, a);
+    }
+    return MCQ_EUNSUPPORTED;
+}
+
+// rule 9: what both range entry points reject, in the order of mcq_search_scan_metric; nothing touches the device
+int range_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+                const float *thr, const int64_t *lims, const void *workspace, size_t workspace_bytes) {
+    if (const int rc = search_domain(N, K, 1)) return rc;
+    if (Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
+    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (!lims) return MCQ_EINVAL;
+    if (Q == 0 || B == 0) return 0;
+    if (!tables || !codes || !thr || !workspace) return MCQ_EINVAL;
+    if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;                  // (the inner-product sweep never reads w)
+    const int need = N >= 16 ? 16 : N;                                    // a candidate's codes are loaded as one vector
+    if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
+    if (workspace_bytes < range_plan(Q, B, N, K).ws_bytes) return MCQ_EWORKSPACE;
+    return 0;
+}
+
+}  // namespace
+
+
 extern "C" {
 
 int mcq_abi_version(void) { return MCQ_ABI_VERSION; }
@@ -1603,6 +1713,45 @@ int mcq_search_scan_metric(const float *tables, long Q, const uint8_t *codes, co
     hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, p.slices, k, out_score, out_index);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
+}
+
+// ---- range search over stored codes: mcq_range_kernels.h (rules 7-9 of include/mcq.h)
+size_t mcq_search_range_workspace_bytes(long Q, long B, int N, int K) {
+    if (Q <= 0 || B <= 0 || B > 0x7fffffffL || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
+    return range_plan(Q, B, N, K).ws_bytes;
+}
+
+int mcq_search_range_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+                           const float *thr, int64_t *lims, void *workspace, size_t workspace_bytes, void *stream) {
+    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, thr, lims, workspace, workspace_bytes)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool empty = Q == 0 || B == 0;
+    if (!empty) {
+        const RangePlan p = range_plan(Q, B, N, K);
+        int64_t *ws = static_cast<int64_t *>(workspace);
+        const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr, ws, nullptr,
+                          nullptr, nullptr, 0};
+        if (const int rc = launch_range_qt<false>(p, st, a)) return rc;
+        hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)Q), dim3(64), 0, st, ws, p.slices * kRangeWaves, lims);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(k_range_lims, dim3(1), dim3(64), 0, st, lims, Q, empty ? 1 : 0);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int mcq_search_range_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+                          const float *thr, const int64_t *lims, float *out_score, int64_t *out_index, long capacity,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, thr, lims, workspace, workspace_bytes)) return rc;
+    if (capacity < 0) return MCQ_EINVAL;
+    if (Q == 0 || B == 0 || capacity == 0) return 0;                       // nothing can be stored
+    if (!out_score || !out_index) return MCQ_EINVAL;
+    const RangePlan p = range_plan(Q, B, N, K);
+    const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
+                      static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity};
+    return launch_range_qt<true>(p, static_cast<hipStream_t>(stream), a);
 }
 
 int mcq_last_encode_launches(void) { return g_last_launches; }

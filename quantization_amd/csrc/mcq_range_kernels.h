@@ -1,0 +1,186 @@
+// mcq_range_kernels.h -- gfx950 kernels of the RANGE search over stored codes: every stored vector whose score does not exceed
+// a per-query threshold, in CSR form.  Same tables, same tiling and the same score as the top-k scan (mcq_search_kernels.h,
+// rules 1, 2, 3, 3' and 6 of include/mcq.h), but no list: one comparison, one ballot and a rare store per candidate.
+//
+// Arithmetic contract (include/mcq.h, rules 7-9; tests/search_range_grid.py restates 7 and 8 in numpy):
+//   7. b is listed for q iff score[q][b] <= thr[q]: one fp32 comparison, inclusive; a NaN on either side lists nothing.
+//   8. lims int64[Q + 1], lims[0] = 0; the entries of q occupy [lims[q], lims[q+1]) in ascending position b, as (score, position).
+//   9. Q == 0 or B == 0: lims is all zeros and nothing else is written.
+// Two sweeps over the store share ONE scoring routine (k_range_sweep below), so they cannot disagree about a borderline
+// candidate: the COUNT sweep leaves one count per (query, slice, wave); k_range_offsets and k_range_lims turn the counts into
+// lims and into one start offset per (query, slice, wave); the FILL sweep recomputes the scores and stores the hits.  A wave
+// owns a CONTIGUOUS run of its slice's steps of 64 candidates, so ascending position is (slice, wave, step, lane) and the fill
+// learns its offsets from the counts alone.  Integer sums only: the output is a function of scores and thresholds.
+#pragma once
+#include "mcq_search_kernels.h"
+
+namespace mcq {
+
+// ---- launch arithmetic (tests/search_range_grid.py reads these constants from this file and mirrors range_plan of mcq_api.hip;
+// the tile, LDS and slice caps are kScanQTMax, kScanTableLds, kScanTargetBlocks and kScanMaxSlices of the top-k scan)
+constexpr int kRangeWaves = 16;           // k_range_sweep: waves per workgroup (1024 threads).  The tables of a 16 x 8 x 256 tile
+                                          // take 128 KiB, so ONE workgroup fits a CU: 16 waves are 4 per SIMD, and with no
+                                          // list in registers the sweep stays far below the 128 VGPRs that allows
+
+// The metric is a wave-uniform runtime switch at the score's last operation (the top-k scan makes it a template parameter
+// because its lists sit at the register edge; nothing does here, and it keeps the number of instantiations down).
+__device__ __forceinline__ float range_finish(float S, float t, int metric) {
+    return metric == kMetricL2 ? S + t : (metric == kMetricCos ? S * t : S);
+}
+
+// QT queries per tile, digits in chunks of CH codebooks (N = nch * CH), FILL: the second sweep.
+// ws: int64 [Q][S][kRangeWaves] -- counts out (COUNT), start offsets relative to lims[q] in (FILL).
+template <int QT, int CH, bool FILL>
+__global__ void __launch_bounds__(64 * kRangeWaves)
+k_range_sweep(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w, long B,
+              int N, int K, int metric, int S, long per_slice, const float *__restrict__ thr, int64_t *__restrict__ ws,
+              const int64_t *__restrict__ lims, float *__restrict__ out_s, int64_t *__restrict__ out_i, long capacity) {
+    extern __shared__ __attribute__((aligned(16))) char range_smem[];
+    float *Tl = reinterpret_cast<float *>(range_smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile = blockIdx.x / S, slice = blockIdx.x % S;
+    const int q0 = tile * QT, NK = N * K, kmask = K - 1, nch = N / CH;
+
+    for (int e = tid; e < NK * QT; e += 64 * kRangeWaves) {
+        const int q = e % QT, j = e / QT;
+        Tl[e] = (q0 + q < Q) ? tables[(long)(q0 + q) * NK + j] : 0.f;
+    }
+    __syncthreads();
+
+    // FILL: the slot of this wave's first hit per query, lims[q] + the wave's start offset, waits in LDS behind the tables (it
+    // is read only in a step that has a hit; 32 scalar registers of bases would push the 16 x 8 sweep into scratch)
+    long *base_at = reinterpret_cast<long *>(range_smem + (size_t)NK * QT * 4) + wave * QT;
+    if (FILL && lane < QT)
+        base_at[lane] = (q0 + lane < Q) ? lims[q0 + lane] + ws[((long)(q0 + lane) * S + slice) * kRangeWaves + wave] : 0;
+    float th[QT];                                            // (uniform) a query past the end of the tile lists nothing: NaN
+    int cnt[QT];                                             // (uniform) this wave's hits so far, per query
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+        th[q] = (q0 + q < Q) ? thr[q0 + q] : __builtin_nanf("");
+        cnt[q] = 0;
+    }
+
+    const long begin = (long)slice * per_slice;
+    const long end = (begin + per_slice < B) ? begin + per_slice : B;
+    const long nblk = (end - begin + 63) / 64;
+    const long run = (nblk + kRangeWaves - 1) / kRangeWaves;  // steps per wave: wave v owns [v * run, (v + 1) * run)
+    const long first = (long)wave * run;
+    const long stop = first + run < nblk ? first + run : nblk;
+    // lanes past the end of the slice re-read its last candidate (in bounds) and offer nothing
+    auto at = [&](long blk) { const long b = begin + blk * 64 + lane; return b < end ? b : end - 1; };
+    const u64 below = (1ull << lane) - 1;
+    CodeChunk<CH> cur;
+    float t = 0.f;
+    if (first < stop) {
+        cur.load(codes + at(first) * N);
+        if (metric != kMetricIP) t = w[at(first)];
+    } else {
+        cur.w[0] = 0;
+        if constexpr (CH == 8) cur.w[1] = 0;
+    }
+    for (long blk = first; blk < stop; ++blk) {
+        const long bl = begin + blk * 64 + lane;
+        const uint8_t *p = codes + at(blk) * N;
+        const long bnext = (blk + 1 < stop) ? at(blk + 1) : at(blk);
+        float tn = t;
+        float acc[QT];
+#pragma unroll
+        for (int q = 0; q < QT; ++q) acc[q] = -0.f;          // (-0) + x == x for every x, signed zeros included
+        // rule 3's sum, operation for operation the loop of k_search_scan
+#pragma unroll 1
+        for (int c = 0; c < nch; ++c) {
+            CodeChunk<CH> nxt;                               // the next step's digits travel while this one gathers
+            if (c + 1 < nch) {
+                nxt.load(p + (c + 1) * CH);
+            } else {
+                nxt.load(codes + bnext * N);
+                if (metric != kMetricIP) tn = w[bnext];
+            }
+#pragma unroll
+            for (int n = 0; n < CH; ++n) {
+                const float *row = Tl + ((c * CH + n) * K + cur.digit(n, kmask)) * QT;
+                if constexpr (QT >= 4) {
+#pragma unroll
+                    for (int q4 = 0; q4 < QT / 4; ++q4) {
+                        const f32x4 v = reinterpret_cast<const f32x4 *>(row)[q4];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) acc[4 * q4 + i] = acc[4 * q4 + i] + v[i];
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < QT; ++q) acc[q] = acc[q] + row[q];
+                }
+            }
+            cur = nxt;
+        }
+        const bool valid = bl < end;
+#pragma unroll
+        for (int q = 0; q < QT; ++q) {
+            const float s = range_finish(acc[q], t, metric);
+            const bool hit = valid && s <= th[q];            // rule 7 (a NaN compares false)
+            const u64 m = __ballot(hit);
+            if constexpr (FILL) {
+                if (m) {                                     // (uniform) hits are rare
+                    const long slot = base_at[q] + cnt[q] + __builtin_popcountll(m & below);
+                    if (hit && (unsigned long)slot < (unsigned long)capacity) {
+                        out_s[slot] = s;
+                        out_i[slot] = bl;
+                    }
+                }
+            }
+            cnt[q] += __builtin_popcountll(m);
+        }
+        t = tn;
+    }
+
+    if constexpr (!FILL) {
+        if (lane == 0) {
+#pragma unroll
+            for (int q = 0; q < QT; ++q)
+                if (q0 + q < Q) ws[((long)(q0 + q) * S + slice) * kRangeWaves + wave] = cnt[q];
+        }
+    }
+}
+
+// inclusive prefix sum over the 64 lanes of a wave (integers: any order gives the same sum)
+__device__ __forceinline__ long wave_scan_incl(long v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const long u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
+// One wave per query: its `per` = S * kRangeWaves counts become exclusive start offsets (in place, in (slice, wave) order) and
+// their sum goes to lims[q + 1].
+__global__ void __launch_bounds__(64)
+k_range_offsets(int64_t *__restrict__ ws, int per, int64_t *__restrict__ lims) {
+    const int q = blockIdx.x, lane = lane_id();
+    int64_t *c = ws + (long)q * per;
+    long base = 0;
+    for (int e0 = 0; e0 < per; e0 += 64) {
+        const long v = (e0 + lane < per) ? (long)c[e0 + lane] : 0;
+        const long incl = wave_scan_incl(v, lane);
+        if (e0 + lane < per) c[e0 + lane] = base + incl - v;
+        base += __shfl(incl, 63, 64);
+    }
+    if (lane == 0) lims[q + 1] = base;
+}
+
+// One wave: lims[0] = 0 and lims[1 .. Q] (the per-query totals) become their inclusive prefix sums.  zero: all of lims is 0.
+__global__ void __launch_bounds__(64)
+k_range_lims(int64_t *__restrict__ lims, long Q, int zero) {
+    const int lane = lane_id();
+    if (lane == 0) lims[0] = 0;
+    long base = 0;
+    for (long e0 = 0; e0 < Q; e0 += 64) {
+        const bool live = e0 + lane < Q;
+        const long v = (live && !zero) ? (long)lims[1 + e0 + lane] : 0;
+        const long incl = wave_scan_incl(v, lane);
+        if (live) lims[1 + e0 + lane] = base + incl;
+        base += __shfl(incl, 63, 64);
+    }
+}
+
+}  // namespace mcq

@@ -646,6 +646,107 @@ class Quantizer(nn.Module):
         lead = queries.shape[:-1]
         return sim.reshape(*lead, k), indexes.reshape(*lead, k)
 
+    # ------------------------------------------------- range search over stored codes
+    def _search_range(self, tables: Tensor, codes: Tensor, w: Tensor, thr: Tensor, metric: str = "l2",
+                      max_results: int = None):
+        """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, w as _search_scan takes it under the metric (norms, None,
+        reciprocal roots), thr fp32 (Q,) -> (lims int64 (Q + 1,), scores fp32 (total,), indexes int64 (total,)): every b with
+        score[q][b] <= thr[q], the entries of query q at [lims[q], lims[q+1]) in ascending position (mcq_search_range_count,
+        one host synchronisation to read lims[Q], mcq_search_range_fill).  More than max_results entries: McqError."""
+        N, K = self.num_codebooks, self.codebook_size
+        if metric not in self._METRICS:
+            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
+        if metric == "ip":
+            w = None
+        elif w is None:
+            raise ValueError(f"metric {metric!r} needs the per-candidate array")
+        if not (tables.is_cuda and codes.is_cuda and thr.is_cuda and (w is None or w.is_cuda)):
+            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
+        L = _lib.lib()
+        if not hasattr(L, "mcq_search_range_count"):
+            raise _lib.McqError(f"{_lib.LIB_PATH} has no range search (mcq_search_range_count)")
+        tables = tables.detach().to(torch.float32).contiguous()
+        thr = thr.detach().reshape(-1).to(torch.float32).contiguous()
+        if w is not None:
+            w = w.detach().to(torch.float32).contiguous()
+        codes = codes.contiguous()
+        if codes.data_ptr() % 16:
+            codes = codes.clone()
+        Q, B, dev = tables.shape[0], codes.shape[0], tables.device
+        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and codes.dtype == torch.uint8
+        assert (w is None or tuple(w.shape) == (B,)) and tuple(thr.shape) == (Q,)
+        with torch.no_grad(), torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            lims = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
+            ws = torch.empty(L.mcq_search_range_workspace_bytes(Q, B, N, K), dtype=torch.uint8, device=dev)
+            args = (tables.data_ptr(), Q, codes.data_ptr(), None if w is None else w.data_ptr(), B, N, K, self._METRICS[metric],
+                    thr.data_ptr(), lims.data_ptr())
+            _lib.check(L.mcq_search_range_count(*args, ws.data_ptr(), ws.numel(), st), "mcq_search_range_count")
+            total = int(lims[Q])                                  # the one host synchronisation: the result is allocated next
+            if max_results is not None and total > max_results:
+                raise _lib.McqError(f"range search: {total} results exceed max_results = {max_results}")
+            scores = torch.empty((total,), dtype=torch.float32, device=dev)
+            indexes = torch.empty((total,), dtype=torch.int64, device=dev)
+            _lib.check(L.mcq_search_range_fill(*args, scores.data_ptr(), indexes.data_ptr(), total, ws.data_ptr(), ws.numel(), st),
+                       "mcq_search_range_fill")
+        return lims, scores, indexes
+
+    def range_search(self, queries: Tensor, codes: Tensor, radius, norms: Tensor = None, metric: str = "l2",
+                     rnorms: Tensor = None, max_results: int = 1 << 26):
+        """Every stored vector within `radius` of each query, from the codes alone (nothing is decoded).
+        queries (*, dim) fp32 or fp16, flattened to Q rows; codes, norms and rnorms exactly as search takes them; radius a
+        Python float or a tensor of Q values.
+        -> (lims int64 (Q + 1,), values fp32 (total,), indexes int64 (total,)): CSR, the results of query q are
+        values[lims[q]:lims[q+1]] and indexes[lims[q]:lims[q+1]], IN ASCENDING POSITION (sort a query's values within its
+        lims for nearest first); values are what search reports for the same (query, position).
+        metric="l2": radius is a SQUARED distance, as search returns them; a vector is listed iff its score
+        sum_n T[n][code] + norm <= radius - |q|^2 in fp32, so a reported distance may exceed radius by the rounding of |q|^2.
+        metric="ip": listed iff <q, decode(codes[b])> >= radius.  metric="cosine": listed iff cos >= radius; a zero query has
+        every similarity 0: everything is listed when radius <= 0 and nothing otherwise.
+        One host synchronisation (reading lims[Q]) separates counting from filling; more than max_results entries raise
+        McqError, naming the count, before anything is allocated for them.  Not differentiable."""
+        if metric not in self._METRICS:
+            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
+        with torch.no_grad():
+            flat = self._unpacked_codes(codes)
+            tables = self.search_tables(queries)
+            Q, dev = tables.shape[0], tables.device
+            if isinstance(radius, Tensor):
+                if radius.numel() != Q:
+                    raise ValueError(f"radius of {radius.numel()} values for {Q} queries")
+                rad = radius.detach().reshape(-1).to(device=dev, dtype=torch.float32)
+            else:
+                rad = torch.full((Q,), float(radius), dtype=torch.float32, device=dev)
+            q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
+            qq = (q2d * q2d).sum(dim=1, keepdim=True)
+            w = qn = None
+            if metric == "l2":
+                w = self.code_norms(flat) if norms is None else norms.reshape(-1)
+                thr = rad - qq[:, 0]
+            elif metric == "ip":
+                thr = rad * -2.0
+            else:
+                if rnorms is not None:
+                    w = rnorms.reshape(-1)
+                elif norms is not None:
+                    w = self.rnorms_from_norms(norms)
+                else:
+                    w = self.code_rnorms(flat)
+                qn = qq.sqrt()
+                thr = rad * -2.0 * qn[:, 0]
+                zero = qn[:, 0] == 0                               # every similarity of a zero query is 0
+                thr = torch.where(zero, torch.where(rad <= 0, float("inf"), float("-inf")).to(thr.dtype), thr)
+                qn = qn.masked_fill(qn == 0, 1.0)
+            lims, scores, indexes = self._search_range(tables, flat, w, thr, metric, max_results)
+            rows = torch.repeat_interleave(torch.arange(Q, device=dev), lims[1:] - lims[:-1], output_size=scores.numel())
+            if metric == "l2":
+                values = (scores + qq[:, 0][rows]).clamp_(min=0.0)
+            else:
+                values = scores * -0.5
+                if metric == "cosine":
+                    values = values / qn[:, 0][rows]
+        return lims, values, indexes
+
     def logits_kernel(self, x: Tensor) -> Tensor:
         """Logits as the index-search kernel forms them (test hook; mcq_logits)."""
         L = _lib.lib()
