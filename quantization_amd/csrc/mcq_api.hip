@@ -825,16 +825,69 @@ int search_domain(int N, int K, int D) {
     return K > 256 ? MCQ_EUNSUPPORTED : 0;
 }
 
-// the launch arithmetic of the scan (mirrored by tests/search_grid.py): a tile of qt queries per workgroup -- as many as fit
-// kScanTableLds, no more than the call has -- and as many slices of the store as fill the chip once
-struct ScanPlan {
+// What every scan and sweep entry point rejects, in this order (tests/test_search_host.py, test_search_metric_host.py and
+// test_search_range_host.py pin it); nothing touches the device.  k: 1 where the entry has none.  outs_ok: the outputs this
+// call writes are there (the caller knows which of them an empty call still writes).  A call with Q == 0 or B == 0 reads no
+// input, so none is looked at.
+int search_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
+                 bool outs_ok, const void *workspace) {
+    if (const int rc = search_domain(N, K, 1)) return rc;
+    if (k > 64) return MCQ_EUNSUPPORTED;
+    if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
+    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (!outs_ok) return MCQ_EINVAL;
+    if (Q == 0 || B == 0) return 0;
+    if (!tables || !codes || !workspace) return MCQ_EINVAL;
+    if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;                  // (the inner product never reads w)
+    const int need = N >= 16 ? 16 : N;                                    // a candidate's codes are loaded as one vector
+    if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
+    return 0;
+}
+
+// what a launch left behind, as the entry points return it (not MCQ_LAUNCH_CHECK: that one counts encode launches)
+inline int launch_rc() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+// Allow `kernel` up to `bytes` of dynamic LDS, once per device.  `allowed` is the calling launcher's static flag array: one
+// per kernel instantiation.
+int allow_dynamic_lds(bool (&allowed)[64], const void *kernel, int bytes) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
+    if (!allowed[dev] || dev == 63) {
+        const hipError_t attr = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (attr != hipSuccess) return (int)attr;
+        allowed[dev] = true;
+    }
+    return 0;
+}
+
+// mcq_code_norms (t[b]) and mcq_code_rnorms (RNORM: r[b])
+template <bool RNORM>
+int code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *out, void *stream) {
+    if (const int rc = search_domain(N, K, D)) return rc;
+    if (B < 0) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (B == 0) return 0;
+    if (!codes || !prepared || !out) return MCQ_EINVAL;
+    const Prepared P = prepared_view(prepared, N, K, D);
+    hipLaunchKernelGGL(k_code_norms<RNORM>, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
+                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), out);
+    return launch_rc();
+}
+
+// the launch arithmetic of the scan and of the sweeps (mirrored by tile_plan of tests/search_grid.py): a tile of qt queries per
+// workgroup -- as many as fit kScanTableLds, no more than the call has -- and as many slices of the store as fill the chip
+// once, none shorter than one step of 64 candidates for each of the workgroup's `waves` waves
+struct TilePlan {
     int qt, qtiles, slices;
     long per_slice;
-    size_t lds, ws_half;
 };
 
-ScanPlan scan_plan(long Q, long B, int N, int K, int k) {
-    ScanPlan p;
+TilePlan tile_plan(long Q, long B, int N, int K, int waves) {
+    TilePlan p;
     int cap = kScanQTMax;
     while (cap > 1 && (size_t)cap * N * K * 4 > (size_t)kScanTableLds) cap /= 2;
     int qt = 1;
@@ -844,12 +897,22 @@ ScanPlan scan_plan(long Q, long B, int N, int K, int k) {
     long cap_slices = kScanTargetBlocks / (p.qtiles > 0 ? p.qtiles : 1);
     cap_slices = cap_slices < 1 ? 1 : (cap_slices > kScanMaxSlices ? kScanMaxSlices : cap_slices);
     const long steps = (B + 63) / 64;                                    // steps of 64 candidates; at least one per wave
-    long want = (steps + kScanWaves - 1) / kScanWaves;
+    long want = (steps + waves - 1) / waves;
     want = want < 1 ? 1 : (want > cap_slices ? cap_slices : want);
     p.per_slice = (((B + want - 1) / want) + 63) / 64 * 64;
     if (p.per_slice < 64) p.per_slice = 64;
     p.slices = (int)((B + p.per_slice - 1) / p.per_slice);
-    const size_t tab = (size_t)qt * N * K * 4, lists = (size_t)qt * kScanWaves * 64 * 8;
+    return p;
+}
+
+// the scan: LDS holds the tables, then the waves' lists; the workspace k (score, position) pairs per (query, slice)
+struct ScanPlan : TilePlan {
+    size_t lds, ws_half;
+};
+
+ScanPlan scan_plan(long Q, long B, int N, int K, int k) {
+    ScanPlan p{tile_plan(Q, B, N, K, kScanWaves), 0, 0};
+    const size_t tab = (size_t)p.qt * N * K * 4, lists = (size_t)p.qt * kScanWaves * 64 * 8;
     p.lds = tab > lists ? tab : lists;
     p.ws_half = align256((size_t)Q * p.slices * k * 4);                  // scores, then positions
     return p;
@@ -859,18 +922,11 @@ template <int QT, int NN, int M>
 int launch_scan(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *norms, long B,
                 int K, int k, float *ws_s, int *ws_i) {
     static bool allowed[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
-    if (!allowed[dev] || dev == 63) {
-        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_scan<QT, NN, M>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kScanTableLds);
-        if (attr != hipSuccess) return (int)attr;
-        allowed[dev] = true;
-    }
+    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_scan<QT, NN, M>), kScanTableLds))
+        return rc;
     hipLaunchKernelGGL((k_search_scan<QT, NN, M>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kScanWaves), p.lds, st,
                        tables, Q, codes, norms, B, K, k, p.slices, p.per_slice, ws_s, ws_i);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 
 template <int QT, int M>
@@ -907,31 +963,14 @@ int launch_scan_qt(const ScanPlan &p, hipStream_t st, const float *tables, int Q
 // ---- range search over stored codes (mcq_range_kernels.h) ---------------------------------------------------------------
 namespace {
 
-// the launch arithmetic of the two sweeps (mirrored by tests/search_range_grid.py): the tile and the slices of scan_plan with
-// kRangeWaves waves per workgroup, and one int64 per (query, slice, wave) of workspace
-struct RangePlan {
-    int qt, qtiles, slices;
-    long per_slice;
+// the two sweeps: one slot base per (wave, query) behind the tables in LDS, one int64 per (query, slice, wave) of workspace
+struct RangePlan : TilePlan {
     size_t lds, ws_bytes;
 };
 
 RangePlan range_plan(long Q, long B, int N, int K) {
-    RangePlan p;
-    int cap = kScanQTMax;
-    while (cap > 1 && (size_t)cap * N * K * 4 > (size_t)kScanTableLds) cap /= 2;
-    int qt = 1;
-    while (qt < cap && qt < Q) qt *= 2;
-    p.qt = qt;
-    p.qtiles = (int)((Q + qt - 1) / qt);
-    long cap_slices = kScanTargetBlocks / (p.qtiles > 0 ? p.qtiles : 1);
-    cap_slices = cap_slices < 1 ? 1 : (cap_slices > kScanMaxSlices ? kScanMaxSlices : cap_slices);
-    const long steps = (B + 63) / 64;                                    // steps of 64 candidates; at least one per wave
-    long want = (steps + kRangeWaves - 1) / kRangeWaves;
-    want = want < 1 ? 1 : (want > cap_slices ? cap_slices : want);
-    p.per_slice = (((B + want - 1) / want) + 63) / 64 * 64;
-    if (p.per_slice < 64) p.per_slice = 64;
-    p.slices = (int)((B + p.per_slice - 1) / p.per_slice);
-    p.lds = (size_t)qt * N * K * 4 + (size_t)kRangeWaves * qt * 8;       // the tables, then one slot base per (wave, query)
+    RangePlan p{tile_plan(Q, B, N, K, kRangeWaves), 0, 0};
+    p.lds = (size_t)p.qt * N * K * 4 + (size_t)kRangeWaves * p.qt * 8;
     p.ws_bytes = align256((size_t)Q * p.slices * kRangeWaves * 8);
     return p;
 }
@@ -954,20 +993,13 @@ struct RangeArgs {
 template <int QT, int CH, bool FILL>
 int launch_range(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
     static bool allowed[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
-    if (!allowed[dev] || dev == 63) {
-        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_range_sweep<QT, CH, FILL>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    kScanTableLds + kRangeWaves * kScanQTMax * 8);
-        if (attr != hipSuccess) return (int)attr;
-        allowed[dev] = true;
-    }
+    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_sweep<QT, CH, FILL>),
+                                         kScanTableLds + kRangeWaves * kScanQTMax * 8))
+        return rc;
     hipLaunchKernelGGL((k_range_sweep<QT, CH, FILL>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kRangeWaves), p.lds,
                        st, a.tables, a.Q, a.codes, a.w, a.B, a.N, a.K, a.metric, p.slices, p.per_slice, a.thr, a.ws, a.lims,
                        a.out_s, a.out_i, a.capacity);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 
 template <int QT, bool FILL>
@@ -993,19 +1025,12 @@ int launch_range_qt(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
     return MCQ_EUNSUPPORTED;
 }
 
-// rule 9: what both range entry points reject, in the order of mcq_search_scan_metric; nothing touches the device
+// rule 9: what both range entry points reject (lims is written even by an empty call); nothing touches the device
 int range_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
                 const float *thr, const int64_t *lims, const void *workspace, size_t workspace_bytes) {
-    if (const int rc = search_domain(N, K, 1)) return rc;
-    if (Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
-    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
-    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
-    if (!lims) return MCQ_EINVAL;
+    if (const int rc = search_check(tables, Q, codes, w, B, N, K, 1, metric, lims != nullptr, workspace)) return rc;
     if (Q == 0 || B == 0) return 0;
-    if (!tables || !codes || !thr || !workspace) return MCQ_EINVAL;
-    if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;                  // (the inner-product sweep never reads w)
-    const int need = N >= 16 ? 16 : N;                                    // a candidate's codes are loaded as one vector
-    if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
+    if (!thr) return MCQ_EINVAL;                     // (after w and the alignment now: all three are MCQ_EINVAL, no code moved)
     if (workspace_bytes < range_plan(Q, B, N, K).ws_bytes) return MCQ_EWORKSPACE;
     return 0;
 }
@@ -1625,21 +1650,11 @@ int mcq_search_tables(const void *q, int q_is_fp16, long Q, const void *prepared
     hipLaunchKernelGGL(k_search_tables, dim3((unsigned)((Q + kTabQueries - 1) / kTabQueries), (unsigned)((NK + kTabRows - 1) / kTabRows)),
                        dim3(256), 0, static_cast<hipStream_t>(stream), q, q_is_fp16 ? 1 : 0, (int)Q, P.C, NK, D, round_up16(D),
                        tables_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 
 int mcq_code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *norms_out, void *stream) {
-    if (const int rc = search_domain(N, K, D)) return rc;
-    if (B < 0) return MCQ_EINVAL;
-    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
-    if (B == 0) return 0;
-    if (!codes || !prepared || !norms_out) return MCQ_EINVAL;
-    const Prepared P = prepared_view(prepared, N, K, D);
-    hipLaunchKernelGGL(k_code_norms<false>, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
-                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), norms_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return code_norms<false>(codes, B, prepared, N, K, D, norms_out, stream);
 }
 
 size_t mcq_search_workspace_bytes(long Q, long B, int N, int K, int k) {
@@ -1648,16 +1663,7 @@ size_t mcq_search_workspace_bytes(long Q, long B, int N, int K, int k) {
 }
 
 int mcq_code_rnorms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *rnorms_out, void *stream) {
-    if (const int rc = search_domain(N, K, D)) return rc;
-    if (B < 0) return MCQ_EINVAL;
-    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
-    if (B == 0) return 0;
-    if (!codes || !prepared || !rnorms_out) return MCQ_EINVAL;
-    const Prepared P = prepared_view(prepared, N, K, D);
-    hipLaunchKernelGGL(k_code_norms<true>, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
-                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), rnorms_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return code_norms<true>(codes, B, prepared, N, K, D, rnorms_out, stream);
 }
 
 int mcq_rnorms_from_norms(const float *norms, long B, float *rnorms_out, void *stream) {
@@ -1667,8 +1673,7 @@ int mcq_rnorms_from_norms(const float *norms, long B, float *rnorms_out, void *s
     if (!norms || !rnorms_out) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_rnorms_from_norms, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        norms, B, rnorms_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 
 int mcq_search_scan(const float *tables, long Q, const uint8_t *codes, const float *norms, long B, int N, int K, int k,
@@ -1680,20 +1685,10 @@ int mcq_search_scan(const float *tables, long Q, const uint8_t *codes, const flo
 int mcq_search_scan_metric(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
                            int metric, float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes,
                            void *stream) {
-    if (const int rc = search_domain(N, K, 1)) return rc;
-    if (k > 64) return MCQ_EUNSUPPORTED;
-    if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
-    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
-    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (const int rc = search_check(tables, Q, codes, w, B, N, K, k, metric, Q == 0 || (out_score && out_index), workspace))
+        return rc;
     if (Q == 0) return 0;
-    if (!out_score || !out_index) return MCQ_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (B > 0) {
-        if (!tables || !codes || !workspace) return MCQ_EINVAL;
-        if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;              // (the inner-product scan never reads w)
-        const int need = N >= 16 ? 16 : N;                                // the scan loads a candidate's codes as one vector
-        if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
-    }
     ScanPlan p{};
     float *ws_s = nullptr;
     int *ws_i = nullptr;
@@ -1711,8 +1706,7 @@ int mcq_search_scan_metric(const float *tables, long Q, const uint8_t *codes, co
         if (rc != 0) return rc;
     }
     hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, p.slices, k, out_score, out_index);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 
 // ---- range search over stored codes: mcq_range_kernels.h (rules 7-9 of include/mcq.h)
@@ -1733,12 +1727,10 @@ int mcq_search_range_count(const float *tables, long Q, const uint8_t *codes, co
                           nullptr, nullptr, 0};
         if (const int rc = launch_range_qt<false>(p, st, a)) return rc;
         hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)Q), dim3(64), 0, st, ws, p.slices * kRangeWaves, lims);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
+        if (const int rc = launch_rc()) return rc;
     }
     hipLaunchKernelGGL(k_range_lims, dim3(1), dim3(64), 0, st, lims, Q, empty ? 1 : 0);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 
 int mcq_search_range_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,

@@ -6,11 +6,12 @@
 //   7. b is listed for q iff score[q][b] <= thr[q]: one fp32 comparison, inclusive; a NaN on either side lists nothing.
 //   8. lims int64[Q + 1], lims[0] = 0; the entries of q occupy [lims[q], lims[q+1]) in ascending position b, as (score, position).
 //   9. Q == 0 or B == 0: lims is all zeros and nothing else is written.
-// Two sweeps over the store share ONE scoring routine (k_range_sweep below), so they cannot disagree about a borderline
-// candidate: the COUNT sweep leaves one count per (query, slice, wave); k_range_offsets and k_range_lims turn the counts into
-// lims and into one start offset per (query, slice, wave); the FILL sweep recomputes the scores and stores the hits.  A wave
-// owns a CONTIGUOUS run of its slice's steps of 64 candidates, so ascending position is (slice, wave, step, lane) and the fill
-// learns its offsets from the counts alone.  Integer sums only: the output is a function of scores and thresholds.
+// Two sweeps over the store are ONE kernel (k_range_sweep below, over the scan's own tile_step), so they cannot disagree
+// about a borderline candidate: the COUNT sweep leaves one count per (query, slice, wave); k_range_offsets and k_range_lims
+// turn the counts into lims and into one start offset per (query, slice, wave); the FILL sweep recomputes the scores and
+// stores the hits.  A wave owns a CONTIGUOUS run of its slice's steps of 64 candidates, so ascending position is (slice,
+// wave, step, lane) and the fill learns its offsets from the counts alone.  Integer sums only: the output is a function of
+// scores and thresholds.
 #pragma once
 #include "mcq_search_kernels.h"
 
@@ -22,13 +23,11 @@ constexpr int kRangeWaves = 16;           // k_range_sweep: waves per workgroup 
                                           // take 128 KiB, so ONE workgroup fits a CU: 16 waves are 4 per SIMD, and with no
                                           // list in registers the sweep stays far below the 128 VGPRs that allows
 
-// The metric is a wave-uniform runtime switch at the score's last operation (the top-k scan makes it a template parameter
-// because its lists sit at the register edge; nothing does here, and it keeps the number of instantiations down).
-__device__ __forceinline__ float range_finish(float S, float t, int metric) {
-    return metric == kMetricL2 ? S + t : (metric == kMetricCos ? S * t : S);
-}
-
-// QT queries per tile, digits in chunks of CH codebooks (N = nch * CH), FILL: the second sweep.
+// QT queries per tile, digits in chunks of CH codebooks (N a multiple of CH), FILL: the second sweep.  The scores are those of
+// tile_step and score_finish (mcq_search_kernels.h), the scan's own: a wave owns a contiguous run of steps (so its next
+// step is blk + 1) and compares each score with thr[q].
+// The metric is a wave-uniform runtime switch at the score's last operation (score_finish; the top-k scan makes it a template
+// parameter because its lists sit at the register edge; nothing does here, and it keeps the number of instantiations down).
 // ws: int64 [Q][S][kRangeWaves] -- counts out (COUNT), start offsets relative to lims[q] in (FILL).
 template <int QT, int CH, bool FILL>
 __global__ void __launch_bounds__(64 * kRangeWaves)
@@ -39,13 +38,8 @@ k_range_sweep(const float *__restrict__ tables, int Q, const uint8_t *__restrict
     float *Tl = reinterpret_cast<float *>(range_smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tile = blockIdx.x / S, slice = blockIdx.x % S;
-    const int q0 = tile * QT, NK = N * K, kmask = K - 1, nch = N / CH;
-
-    for (int e = tid; e < NK * QT; e += 64 * kRangeWaves) {
-        const int q = e % QT, j = e / QT;
-        Tl[e] = (q0 + q < Q) ? tables[(long)(q0 + q) * NK + j] : 0.f;
-    }
-    __syncthreads();
+    const int q0 = tile * QT, NK = N * K;
+    tile_stage<QT, 64 * kRangeWaves>(Tl, tables, Q, q0, NK, tid);
 
     // FILL: the slot of this wave's first hit per query, lims[q] + the wave's start offset, waits in LDS behind the tables (it
     // is read only in a step that has a hit; 32 scalar registers of bases would push the 16 x 8 sweep into scratch)
@@ -60,63 +54,24 @@ k_range_sweep(const float *__restrict__ tables, int Q, const uint8_t *__restrict
         cnt[q] = 0;
     }
 
-    const long begin = (long)slice * per_slice;
-    const long end = (begin + per_slice < B) ? begin + per_slice : B;
-    const long nblk = (end - begin + 63) / 64;
-    const long run = (nblk + kRangeWaves - 1) / kRangeWaves;  // steps per wave: wave v owns [v * run, (v + 1) * run)
+    const Slice sl = slice_of(slice, per_slice, B);
+    const long run = (sl.steps + kRangeWaves - 1) / kRangeWaves;  // steps per wave: wave v owns [v * run, (v + 1) * run)
     const long first = (long)wave * run;
-    const long stop = first + run < nblk ? first + run : nblk;
-    // lanes past the end of the slice re-read its last candidate (in bounds) and offer nothing
-    auto at = [&](long blk) { const long b = begin + blk * 64 + lane; return b < end ? b : end - 1; };
+    const long stop = first + run < sl.steps ? first + run : sl.steps;
     const u64 below = (1ull << lane) - 1;
     CodeChunk<CH> cur;
     float t = 0.f;
-    if (first < stop) {
-        cur.load(codes + at(first) * N);
-        if (metric != kMetricIP) t = w[at(first)];
-    } else {
-        cur.w[0] = 0;
-        if constexpr (CH == 8) cur.w[1] = 0;
-    }
+    tile_first(cur, t, codes, w, metric, N, sl, first, stop, lane);
     for (long blk = first; blk < stop; ++blk) {
-        const long bl = begin + blk * 64 + lane;
-        const uint8_t *p = codes + at(blk) * N;
-        const long bnext = (blk + 1 < stop) ? at(blk + 1) : at(blk);
+        const long bl = sl.begin + blk * 64 + lane;
+        const long bnext = blk + 1 < stop ? step_at(sl, blk + 1, lane) : step_at(sl, blk, lane);
         float tn = t;
         float acc[QT];
-#pragma unroll
-        for (int q = 0; q < QT; ++q) acc[q] = -0.f;          // (-0) + x == x for every x, signed zeros included
-        // rule 3's sum, operation for operation the loop of k_search_scan
-#pragma unroll 1
-        for (int c = 0; c < nch; ++c) {
-            CodeChunk<CH> nxt;                               // the next step's digits travel while this one gathers
-            if (c + 1 < nch) {
-                nxt.load(p + (c + 1) * CH);
-            } else {
-                nxt.load(codes + bnext * N);
-                if (metric != kMetricIP) tn = w[bnext];
-            }
-#pragma unroll
-            for (int n = 0; n < CH; ++n) {
-                const float *row = Tl + ((c * CH + n) * K + cur.digit(n, kmask)) * QT;
-                if constexpr (QT >= 4) {
-#pragma unroll
-                    for (int q4 = 0; q4 < QT / 4; ++q4) {
-                        const f32x4 v = reinterpret_cast<const f32x4 *>(row)[q4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[4 * q4 + i] = acc[4 * q4 + i] + v[i];
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < QT; ++q) acc[q] = acc[q] + row[q];
-                }
-            }
-            cur = nxt;
-        }
-        const bool valid = bl < end;
+        tile_step(acc, cur, tn, Tl, codes, w, metric, N, K, step_at(sl, blk, lane), bnext);
+        const bool valid = bl < sl.end;
 #pragma unroll
         for (int q = 0; q < QT; ++q) {
-            const float s = range_finish(acc[q], t, metric);
+            const float s = score_finish(acc[q], t, metric);
             const bool hit = valid && s <= th[q];            // rule 7 (a NaN compares false)
             const u64 m = __ballot(hit);
             if constexpr (FILL) {

@@ -8,7 +8,8 @@
 //   2. k_code_norms: per lane l and float4 group g = l, l + 64, ...: v = ((C[0][c_0] + C[1][c_1]) + ...) per component (N - 1
 //      additions), part = (((part + v0*v0) + v1*v1) + v2*v2) + v3*v3, then the xor butterfly 32, 16, 8, 4, 2, 1.  A code digit is
 //      masked with K - 1 (as mcq_decode does).
-//   3. k_search_scan: s[q][b] = (((T[c_0] + T[c_1]) + ...) + T[c_{N-1}]) + t[b], fp32 additions in exactly this order.
+//   3. tile_step + score_finish (in k_search_scan, and in k_range_sweep of mcq_range_kernels.h):
+//      s[q][b] = (((T[c_0] + T[c_1]) + ...) + T[c_{N-1}]) + t[b], fp32 additions in exactly this order.
 //      With a metric (k_search_scan<QT, N, M>; S is the sum of the N table entries above, w the per-candidate array):
 //        kMetricL2   w[b] = t[b]                                   score = S + w[b]      (the line above)
 //        kMetricIP   no w: the pointer is never read               score = S             (= -2 <q, x^_b>)
@@ -23,7 +24,8 @@
 
 namespace mcq {
 
-// ---- launch arithmetic (tests/search_grid.py reads these constants from this file and mirrors scan_plan of mcq_api.hip)
+// ---- launch arithmetic (tests/search_grid.py reads these constants from this file and mirrors tile_plan and scan_plan of
+// mcq_api.hip)
 constexpr int kTabRows = 64;              // k_search_tables: table rows (n*K + k) per workgroup
 constexpr int kTabQueries = 16;           //                  queries per workgroup
 constexpr int kTabChunk = 32;             //                  features staged per step
@@ -178,23 +180,114 @@ struct CodeChunk {
     __device__ __forceinline__ int digit(int n, int kmask) const { return (int)(w[n >> 2] >> (8 * (n & 3))) & kmask; }
 };
 
+// ---- the tile scorer: everything k_search_scan and k_range_sweep (mcq_range_kernels.h) share -- the staging of the tables,
+// the digit stream with its loads one step ahead, the N additions of rule 3 and the metric's last operation.  They exist
+// HERE and nowhere else, so the two kernels cannot disagree about a score; a kernel decides only which steps a wave owns
+// and what becomes of a step's QT scores.
+
+// the finishing operation of rule 3 / 3'.  The scan passes its template parameter M (the switch folds away), the sweep a
+// wave-uniform runtime value.
+__device__ __forceinline__ float score_finish(float S, float w, int metric) {
+    return metric == kMetricL2 ? S + w : (metric == kMetricCos ? S * w : S);
+}
+
+// the tile's tables -> LDS, interleaved by query: Tl[(n*K + k) * QT + q]; a query past the end of the call reads as zeros
+template <int QT, int THREADS>
+__device__ __forceinline__ void tile_stage(float *Tl, const float *__restrict__ tables, int Q, int q0, int NK, int tid) {
+    for (int e = tid; e < NK * QT; e += THREADS) {
+        const int q = e % QT, j = e / QT;
+        Tl[e] = (q0 + q < Q) ? tables[(long)(q0 + q) * NK + j] : 0.f;
+    }
+    __syncthreads();
+}
+
+// candidates [begin, end) of the store, in `steps` steps of 64 (one candidate per lane)
+struct Slice {
+    long begin, end, steps;
+};
+__device__ __forceinline__ Slice slice_of(int slice, long per_slice, long B) {
+    const long begin = (long)slice * per_slice;
+    const long end = (begin + per_slice < B) ? begin + per_slice : B;
+    return {begin, end, (end - begin + 63) / 64};
+}
+
+// the candidate of this lane in step `step` of the slice; lanes past the end of the slice re-read its last candidate (in
+// bounds) and offer nothing
+__device__ __forceinline__ long step_at(const Slice &sl, long step, int lane) {
+    const long b = sl.begin + step * 64 + lane;
+    return b < sl.end ? b : sl.end - 1;
+}
+
+// What a step needs from HBM travels one step ahead, in two plain locals of the kernel: `cur`, its first CH digits, and its
+// w (t[b] under L2, r[b] under the cosine, never read under kMetricIP).  tile_first loads those of a wave's first step (none
+// when it has no step: first >= stop).  `metric` and N may be compile-time values of the caller here and in tile_step.
+template <int CH>
+__device__ __forceinline__ void tile_first(CodeChunk<CH> &cur, float &t, const uint8_t *__restrict__ codes,
+                                           const float *__restrict__ w, int metric, int N, const Slice &sl, long first, long stop,
+                                           int lane) {
+    if (first < stop) {
+        cur.load(codes + step_at(sl, first, lane) * N);
+        if (metric != kMetricIP) t = w[step_at(sl, first, lane)];
+    } else {
+        cur.w[0] = 0;
+        if constexpr (CH == 8) cur.w[1] = 0;
+    }
+}
+
+// One step of one wave against the QT queries of the staged tile: acc[q] = the N table additions of rule 3 in codebook order,
+// the digits arriving in N / CH chunks of CH codebooks.  b is the lane's candidate of this step and bnext that of the wave's
+// next step (b again in its last), both from step_at: the kernel says which step comes next.  `cur` holds the digits of b on
+// entry and those of bnext on return; w[bnext] goes to tn (untouched under kMetricIP).
+// NCONST: N where the caller has it as a template parameter (the scan), 0 where N is a runtime value (the sweep).  The chunk
+// count has to be a constant BEFORE inlining: without it the scans of two chunks (N = 16) under kMetricIP compile to a branch
+// where the loop had a select, and take up to 13 VGPRs more.
+template <int QT, int CH, int NCONST = 0>
+__device__ __forceinline__ void tile_step(float (&acc)[QT], CodeChunk<CH> &cur, float &tn, const float *Tl,
+                                          const uint8_t *__restrict__ codes, const float *__restrict__ w, int metric, int N, int K,
+                                          long b, long bnext) {
+    const int kmask = K - 1, nch = NCONST ? NCONST / CH : N / CH;
+    const uint8_t *p = codes + b * N;
+#pragma unroll
+    for (int q = 0; q < QT; ++q) acc[q] = -0.f;              // (-0) + x == x for every x, signed zeros included
+#pragma unroll 1
+    for (int c = 0; c < nch; ++c) {
+        CodeChunk<CH> nxt;                                   // the next step's digits travel while this one gathers
+        if (c + 1 < nch) {
+            nxt.load(p + (c + 1) * CH);
+        } else {
+            nxt.load(codes + bnext * N);
+            if (metric != kMetricIP) tn = w[bnext];
+        }
+#pragma unroll
+        for (int n = 0; n < CH; ++n) {
+            const float *row = Tl + ((c * CH + n) * K + cur.digit(n, kmask)) * QT;
+            if constexpr (QT >= 4) {
+#pragma unroll
+                for (int q4 = 0; q4 < QT / 4; ++q4) {
+                    const f32x4 v = reinterpret_cast<const f32x4 *>(row)[q4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc[4 * q4 + i] = acc[4 * q4 + i] + v[i];
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < QT; ++q) acc[q] = acc[q] + row[q];
+            }
+        }
+        cur = nxt;
+    }
+}
+
 // M: what finishes a score (rule 3).  w is t[b] (L2) or r[b] (cosine); the inner-product scan has no w and loads none.
 template <int QT, int N, int M>
 __global__ void __launch_bounds__(64 * kScanWaves)
 k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w,
               long B, int K, int k, int S, long per_slice, float *__restrict__ ws_s, int *__restrict__ ws_i) {
     extern __shared__ __attribute__((aligned(16))) char search_smem[];
-    float *Tl = reinterpret_cast<float *>(search_smem);
-    constexpr int CH = N < 8 ? N : 8, NCH = N / CH;          // a candidate's digits arrive in NCH chunks of CH
+    constexpr int CH = N < 8 ? N : 8;                        // a candidate's digits arrive in N / CH chunks of CH
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tile = blockIdx.x / S, slice = blockIdx.x % S;
-    const int q0 = tile * QT, NK = N * K, kmask = K - 1;
-
-    for (int e = tid; e < NK * QT; e += 64 * kScanWaves) {
-        const int q = e % QT, j = e / QT;
-        Tl[e] = (q0 + q < Q) ? tables[(long)(q0 + q) * NK + j] : 0.f;
-    }
-    __syncthreads();
+    const int q0 = tile * QT;
+    tile_stage<QT, 64 * kScanWaves>(reinterpret_cast<float *>(search_smem), tables, Q, q0, N * K, tid);
 
     float ls[QT], ts[QT];
     int li[QT], tb[QT];
@@ -204,61 +297,21 @@ k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict
         li[q] = tb[q] = kNoIndex;
     }
 
-    const long begin = (long)slice * per_slice;
-    const long end = (begin + per_slice < B) ? begin + per_slice : B;
-    const long nblk = (end - begin + 63) / 64;
-    // lanes past the end of the slice re-read its last candidate (in bounds) and offer nothing
-    auto at = [&](long blk) { const long b = begin + blk * 64 + lane; return b < end ? b : end - 1; };
+    // the waves of a workgroup take the steps of its slice in turn: wave v owns v, v + kScanWaves, ...
+    const Slice sl = slice_of(slice, per_slice, B);
+    const float *Tl = reinterpret_cast<const float *>(search_smem);
     CodeChunk<CH> cur;
     float t = 0.f;
-    if (wave < nblk) {
-        cur.load(codes + at(wave) * N);
-        if constexpr (M != kMetricIP) t = w[at(wave)];
-    } else {
-        cur.w[0] = 0;
-        if constexpr (CH == 8) cur.w[1] = 0;
-    }
-    for (long blk = wave; blk < nblk; blk += kScanWaves) {
-        const long bl = begin + blk * 64 + lane;
-        const uint8_t *p = codes + at(blk) * N;
-        const long bnext = (blk + kScanWaves < nblk) ? at(blk + kScanWaves) : at(blk);
+    tile_first(cur, t, codes, w, M, N, sl, wave, sl.steps, lane);
+    for (long blk = wave; blk < sl.steps; blk += kScanWaves) {
+        const long bl = sl.begin + blk * 64 + lane;
+        const long bnext = blk + kScanWaves < sl.steps ? step_at(sl, blk + kScanWaves, lane) : step_at(sl, blk, lane);
         float tn = t;
         float acc[QT];
+        tile_step<QT, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, step_at(sl, blk, lane), bnext);
 #pragma unroll
-        for (int q = 0; q < QT; ++q) acc[q] = -0.f;          // (-0) + x == x for every x, signed zeros included
-#pragma unroll 1
-        for (int c = 0; c < NCH; ++c) {
-            CodeChunk<CH> nxt;                               // the next step's digits travel while this one gathers
-            if (c + 1 < NCH) {
-                nxt.load(p + (c + 1) * CH);
-            } else {
-                nxt.load(codes + bnext * N);
-                if constexpr (M != kMetricIP) tn = w[bnext];
-            }
-#pragma unroll
-            for (int n = 0; n < CH; ++n) {
-                const float *row = Tl + ((c * CH + n) * K + cur.digit(n, kmask)) * QT;
-                if constexpr (QT >= 4) {
-#pragma unroll
-                    for (int q4 = 0; q4 < QT / 4; ++q4) {
-                        const f32x4 v = reinterpret_cast<const f32x4 *>(row)[q4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[4 * q4 + i] = acc[4 * q4 + i] + v[i];
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < QT; ++q) acc[q] = acc[q] + row[q];
-                }
-            }
-            cur = nxt;
-        }
-        const int bi = (int)bl;
-        const bool valid = bl < end;
-#pragma unroll
-        for (int q = 0; q < QT; ++q) {
-            const float s = M == kMetricL2 ? acc[q] + t : (M == kMetricCos ? acc[q] * t : acc[q]);
-            list_insert(ls[q], li[q], ts[q], tb[q], s, bi, valid, k, lane);
-        }
+        for (int q = 0; q < QT; ++q)
+            list_insert(ls[q], li[q], ts[q], tb[q], score_finish(acc[q], t, M), (int)bl, bl < sl.end, k, lane);
         t = tn;
     }
 

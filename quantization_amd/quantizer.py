@@ -516,31 +516,27 @@ class Quantizer(nn.Module):
         _lib.check(rc, "mcq_search_tables")
         return out
 
-    def code_norms(self, codes: Tensor) -> Tensor:
-        """codes (*, num_codebooks) uint8 (or packed, codebook_size 16) -> fp32 (B,): |decode(codes[b])|^2 (mcq_code_norms).
-        Formed once per store of codes and handed to search(norms=...)."""
+    def _code_norms(self, codes: Tensor, entry: str) -> Tensor:
+        """code_norms and code_rnorms: `entry` names the library call (mcq_code_norms, mcq_code_rnorms)"""
         N, K, D = self.num_codebooks, self.codebook_size, self.dim
         flat = self._unpacked_codes(codes)
         B, dev = flat.shape[0], flat.device
         with torch.no_grad(), torch.cuda.device(dev):
             L, blob, st = self._search_state(dev)
             out = torch.empty((B,), dtype=torch.float32, device=dev)
-            rc = L.mcq_code_norms(flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
-        _lib.check(rc, "mcq_code_norms")
+            rc = getattr(L, entry)(flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
+        _lib.check(rc, entry)
         return out
+
+    def code_norms(self, codes: Tensor) -> Tensor:
+        """codes (*, num_codebooks) uint8 (or packed, codebook_size 16) -> fp32 (B,): |decode(codes[b])|^2 (mcq_code_norms).
+        Formed once per store of codes and handed to search(norms=...)."""
+        return self._code_norms(codes, "mcq_code_norms")
 
     def code_rnorms(self, codes: Tensor) -> Tensor:
         """codes as for code_norms -> fp32 (B,): 1 / sqrt(code_norms(codes)), 0 for an all-zero reconstruction (mcq_code_rnorms).
         What the cosine search multiplies by: formed once per store and handed to search(metric="cosine", rnorms=...)."""
-        N, K, D = self.num_codebooks, self.codebook_size, self.dim
-        flat = self._unpacked_codes(codes)
-        B, dev = flat.shape[0], flat.device
-        with torch.no_grad(), torch.cuda.device(dev):
-            L, blob, st = self._search_state(dev)
-            out = torch.empty((B,), dtype=torch.float32, device=dev)
-            rc = L.mcq_code_rnorms(flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
-        _lib.check(rc, "mcq_code_rnorms")
-        return out
+        return self._code_norms(codes, "mcq_code_rnorms")
 
     def rnorms_from_norms(self, norms: Tensor) -> Tensor:
         """norms fp32 (B,) as code_norms returned them -> fp32 (B,): the same values code_rnorms gives, without a gather
@@ -558,29 +554,47 @@ class Quantizer(nn.Module):
 
     _METRICS = {"l2": _lib.MCQ_SEARCH_L2, "ip": _lib.MCQ_SEARCH_IP, "cosine": _lib.MCQ_SEARCH_COS}
 
+    def _search_inputs(self, tables: Tensor, codes: Tensor, w: Tensor, metric: str, *more: Tensor):
+        """What _search_scan and _search_range check and normalise alike: the metric, the per-candidate array it needs, that
+        every tensor (those of `more` too) is on the device -> (tables, codes, w, the ABI's metric value, Q, B, dev)."""
+        N, K = self.num_codebooks, self.codebook_size
+        if metric not in self._METRICS:
+            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
+        if metric == "ip":
+            w = None
+        elif w is None:
+            raise ValueError(f"metric {metric!r} needs the per-candidate array")
+        if not all(t.is_cuda for t in (tables, codes, *more) + (() if w is None else (w,))):
+            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
+        tables = tables.detach().to(torch.float32).contiguous()
+        if w is not None:
+            w = w.detach().to(torch.float32).contiguous()
+        codes = codes.contiguous()
+        if codes.data_ptr() % 16:
+            codes = codes.clone()
+        Q, B, dev = tables.shape[0], codes.shape[0], tables.device
+        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and codes.dtype == torch.uint8
+        assert w is None or tuple(w.shape) == (B,)
+        return tables, codes, w, self._METRICS[metric], Q, B, dev
+
+    def _metric_array(self, metric: str, flat: Tensor, norms, rnorms):
+        """the per-candidate array of a metric, from what the caller handed in or else from the codes: norms (l2), none (ip),
+        reciprocal roots (cosine: rnorms, or norms converted on the device, or code_rnorms)"""
+        if metric == "ip":
+            return None
+        if metric == "l2":
+            return self.code_norms(flat) if norms is None else norms.reshape(-1)
+        if rnorms is not None:
+            return rnorms.reshape(-1)
+        return self.code_rnorms(flat) if norms is None else self.rnorms_from_norms(norms)
+
     def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int, metric: str = "l2"):
         """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, norms fp32 (B,) -> (scores fp32 (Q, k), indexes int64 (Q, k)):
         the k smallest score[q][b] = sum_n tables[q][n][codes[b][n]] + norms[b] under (score, b) ascending (mcq_search_scan).
         metric "ip": the score is the sum alone and `norms` is not looked at (None will do); "cosine": `norms` holds the
         reciprocal roots (code_rnorms) and the score is the sum times norms[b] (mcq_search_scan_metric)."""
         N, K = self.num_codebooks, self.codebook_size
-        if metric not in self._METRICS:
-            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
-        if metric == "ip":
-            norms = None
-        elif norms is None:
-            raise ValueError(f"metric {metric!r} needs the per-candidate array")
-        if not (tables.is_cuda and codes.is_cuda and (norms is None or norms.is_cuda)):
-            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
-        tables = tables.detach().to(torch.float32).contiguous()
-        if norms is not None:
-            norms = norms.detach().to(torch.float32).contiguous()
-        codes = codes.contiguous()
-        if codes.data_ptr() % 16:
-            codes = codes.clone()
-        Q, B, dev = tables.shape[0], codes.shape[0], tables.device
-        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and codes.dtype == torch.uint8
-        assert norms is None or tuple(norms.shape) == (B,)
+        tables, codes, norms, m, Q, B, dev = self._search_inputs(tables, codes, norms, metric)
         L = _lib.lib()
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
@@ -592,7 +606,7 @@ class Quantizer(nn.Module):
                                        scores.data_ptr(), indexes.data_ptr(), ws.data_ptr(), ws.numel(), st)
             else:
                 rc = L.mcq_search_scan_metric(tables.data_ptr(), Q, codes.data_ptr(), None if norms is None else norms.data_ptr(),
-                                              B, N, K, int(k), self._METRICS[metric], scores.data_ptr(), indexes.data_ptr(),
+                                              B, N, K, int(k), m, scores.data_ptr(), indexes.data_ptr(),
                                               ws.data_ptr(), ws.numel(), st)
         _lib.check(rc, "mcq_search_scan" if metric == "l2" else "mcq_search_scan_metric")
         return scores, indexes
@@ -615,10 +629,9 @@ class Quantizer(nn.Module):
             return self._search_similarity(queries, codes, k, norms, metric, rnorms)
         with torch.no_grad():
             flat = self._unpacked_codes(codes)
-            if norms is None:
-                norms = self.code_norms(flat)
+            w = self._metric_array("l2", flat, norms, None)
             tables = self.search_tables(queries)
-            scores, indexes = self._search_scan(tables, flat, norms.reshape(-1), k)
+            scores, indexes = self._search_scan(tables, flat, w, k)
             q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
             dist = (scores + (q2d * q2d).sum(dim=1, keepdim=True)).clamp_(min=0.0)
         lead = queries.shape[:-1]
@@ -628,14 +641,7 @@ class Quantizer(nn.Module):
         """search() under "ip" and "cosine": the scan's scores are -2 <q, x^> and -2 |q| cos; halving is exact"""
         with torch.no_grad():
             flat = self._unpacked_codes(codes)
-            w = None
-            if metric == "cosine":
-                if rnorms is not None:
-                    w = rnorms.reshape(-1)
-                elif norms is not None:
-                    w = self.rnorms_from_norms(norms)
-                else:
-                    w = self.code_rnorms(flat)
+            w = self._metric_array(metric, flat, norms, rnorms)
             tables = self.search_tables(queries)
             scores, indexes = self._search_scan(tables, flat, w, k, metric=metric)
             sim = scores * -0.5
@@ -654,33 +660,18 @@ class Quantizer(nn.Module):
         score[q][b] <= thr[q], the entries of query q at [lims[q], lims[q+1]) in ascending position (mcq_search_range_count,
         one host synchronisation to read lims[Q], mcq_search_range_fill).  More than max_results entries: McqError."""
         N, K = self.num_codebooks, self.codebook_size
-        if metric not in self._METRICS:
-            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
-        if metric == "ip":
-            w = None
-        elif w is None:
-            raise ValueError(f"metric {metric!r} needs the per-candidate array")
-        if not (tables.is_cuda and codes.is_cuda and thr.is_cuda and (w is None or w.is_cuda)):
-            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
+        tables, codes, w, m, Q, B, dev = self._search_inputs(tables, codes, w, metric, thr)
         L = _lib.lib()
         if not hasattr(L, "mcq_search_range_count"):
             raise _lib.McqError(f"{_lib.LIB_PATH} has no range search (mcq_search_range_count)")
-        tables = tables.detach().to(torch.float32).contiguous()
         thr = thr.detach().reshape(-1).to(torch.float32).contiguous()
-        if w is not None:
-            w = w.detach().to(torch.float32).contiguous()
-        codes = codes.contiguous()
-        if codes.data_ptr() % 16:
-            codes = codes.clone()
-        Q, B, dev = tables.shape[0], codes.shape[0], tables.device
-        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and codes.dtype == torch.uint8
-        assert (w is None or tuple(w.shape) == (B,)) and tuple(thr.shape) == (Q,)
+        assert tuple(thr.shape) == (Q,)
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             lims = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
             ws = torch.empty(L.mcq_search_range_workspace_bytes(Q, B, N, K), dtype=torch.uint8, device=dev)
-            args = (tables.data_ptr(), Q, codes.data_ptr(), None if w is None else w.data_ptr(), B, N, K, self._METRICS[metric],
-                    thr.data_ptr(), lims.data_ptr())
+            args = (tables.data_ptr(), Q, codes.data_ptr(), None if w is None else w.data_ptr(), B, N, K, m, thr.data_ptr(),
+                    lims.data_ptr())
             _lib.check(L.mcq_search_range_count(*args, ws.data_ptr(), ws.numel(), st), "mcq_search_range_count")
             total = int(lims[Q])                                  # the one host synchronisation: the result is allocated next
             if max_results is not None and total > max_results:
@@ -719,19 +710,13 @@ class Quantizer(nn.Module):
                 rad = torch.full((Q,), float(radius), dtype=torch.float32, device=dev)
             q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
             qq = (q2d * q2d).sum(dim=1, keepdim=True)
-            w = qn = None
+            w = self._metric_array(metric, flat, norms, rnorms)
+            qn = None
             if metric == "l2":
-                w = self.code_norms(flat) if norms is None else norms.reshape(-1)
                 thr = rad - qq[:, 0]
             elif metric == "ip":
                 thr = rad * -2.0
             else:
-                if rnorms is not None:
-                    w = rnorms.reshape(-1)
-                elif norms is not None:
-                    w = self.rnorms_from_norms(norms)
-                else:
-                    w = self.code_rnorms(flat)
                 qn = qq.sqrt()
                 thr = rad * -2.0 * qn[:, 0]
                 zero = qn[:, 0] == 0                               # every similarity of a zero query is 0

@@ -1,6 +1,6 @@
-"""Host mirror of the launch arithmetic of the search over stored codes (scan_plan in quantization_amd/csrc/mcq_api.hip, the
-constants of mcq_search_kernels.h), the numpy restatement of rules 3 and 4 of its contract (include/mcq.h), and the case table
-of tests/test_gpu_search.py.
+"""Host mirror of the launch arithmetic of the search over stored codes (tile_plan and scan_plan in
+quantization_amd/csrc/mcq_api.hip, the constants of mcq_search_kernels.h), the numpy restatement of rules 3 and 4 of its
+contract (include/mcq.h), and the case table of tests/test_gpu_search.py.
 
 The constants are read from the source, so that a moved tile size or cap makes tests/test_search_host.py fail instead of
 leaving the GPU cases covering nothing: each case below CLAIMS which paths it reaches (more than one query tile, more than
@@ -52,8 +52,8 @@ class Plan:
         return any((min(B, (s + 1) * self.per_slice) - s * self.per_slice) % 64 != 0 for s in range(self.slices))
 
 
-def scan_plan(Q, B, N, K, k, c=None):
-    c = c or constants()
+def tile_plan(Q, B, N, K, waves, c):
+    """tile_plan of mcq_api.hip, shared by the scan and by the sweeps of the range search -> (qt, qtiles, slices, per_slice)"""
     cap = c["kScanQTMax"]
     while cap > 1 and cap * N * K * 4 > c["kScanTableLds"]:
         cap //= 2
@@ -63,9 +63,14 @@ def scan_plan(Q, B, N, K, k, c=None):
     qtiles = (Q + qt - 1) // qt
     cap_slices = min(max(c["kScanTargetBlocks"] // max(qtiles, 1), 1), c["kScanMaxSlices"])
     steps = (B + 63) // 64
-    want = min(max((steps + c["kScanWaves"] - 1) // c["kScanWaves"], 1), cap_slices)
+    want = min(max((steps + waves - 1) // waves, 1), cap_slices)
     per = max((((B + want - 1) // want) + 63) // 64 * 64, 64)
-    slices = (B + per - 1) // per
+    return qt, qtiles, (B + per - 1) // per, per
+
+
+def scan_plan(Q, B, N, K, k, c=None):
+    c = c or constants()
+    qt, qtiles, slices, per = tile_plan(Q, B, N, K, c["kScanWaves"], c)
     lds = max(qt * N * K * 4, qt * c["kScanWaves"] * 64 * 8)
     return Plan(qt, qtiles, slices, per, lds, 2 * align256(Q * slices * k * 4))
 

@@ -70,18 +70,7 @@ class Plan:
 def range_plan(Q, B, N, K, c=None):
     c = c or constants()
     W = c["kRangeWaves"]
-    cap = c["kScanQTMax"]
-    while cap > 1 and cap * N * K * 4 > c["kScanTableLds"]:
-        cap //= 2
-    qt = 1
-    while qt < cap and qt < Q:
-        qt *= 2
-    qtiles = (Q + qt - 1) // qt
-    cap_slices = min(max(c["kScanTargetBlocks"] // max(qtiles, 1), 1), c["kScanMaxSlices"])
-    steps = (B + 63) // 64
-    want = min(max((steps + W - 1) // W, 1), cap_slices)
-    per = max((((B + want - 1) // want) + 63) // 64 * 64, 64)
-    slices = (B + per - 1) // per
+    qt, qtiles, slices, per = sg.tile_plan(Q, B, N, K, W, c)
     return Plan(qt, qtiles, slices, per, W, qt * N * K * 4 + W * qt * 8, sg.align256(Q * slices * W * 8))
 
 
