@@ -1,5 +1,6 @@
-// mcq_api.hip -- C ABI (include/mcq.h) over the gfx950 kernels of mcq_kernels.h.
-// Host side only enqueues kernels on the caller's stream; see mcq.h for the contract.
+// mcq_api.hip -- C ABI (include/mcq.h) over the gfx950 kernels of the mcq_*_kernels.h headers below: prepare, encode, decode, the
+// trainer's loss and update kernels, search and range search over stored codes.  Host side only: argument checks, launch
+// arithmetic, kernel selection; every entry point enqueues on the caller's stream and returns (mcq.h has the contract).
 #include "../../include/mcq.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
@@ -31,7 +32,7 @@ int k_cutoff(int K, int L) {
 }
 
 struct Prepared {
-    const float *C, *Q, *bias, *scales, *G, *mean, *wmu;
+    const float *C, *Q, *bias, *scales, *G, *mean, *wmu, *cmean;
     const int8_t *Cf, *Wf;      // limb planes of the scaled centers / of to_logits.weight (mcq_fix_kernels.h)
     const int *Ce, *We;         // their row exponents
 };
@@ -68,13 +69,14 @@ PreparedLayout prepared_layout(int N, int K, int D) {
 Prepared prepared_view(const void *p, int N, int K, int D) {
     const PreparedLayout l = prepared_layout(N, K, D);
     const char *b = static_cast<const char *>(p);
-    return Prepared{reinterpret_cast<const float *>(b + l.offC), reinterpret_cast<const float *>(b + l.offQ),
-                    reinterpret_cast<const float *>(b + l.offBias), reinterpret_cast<const float *>(b + l.offScales),
-                    reinterpret_cast<const float *>(b + l.offG), reinterpret_cast<const float *>(b + l.offMean),
-                    reinterpret_cast<const float *>(b + l.offWmu),
+    auto f = [b](size_t off) { return reinterpret_cast<const float *>(b + off); };
+    return Prepared{f(l.offC), f(l.offQ), f(l.offBias), f(l.offScales), f(l.offG), f(l.offMean), f(l.offWmu), f(l.offCMean),
                     reinterpret_cast<const int8_t *>(b + l.offCf), reinterpret_cast<const int8_t *>(b + l.offWf),
                     reinterpret_cast<const int *>(b + l.offCe), reinterpret_cast<const int *>(b + l.offWe)};
 }
+
+template <typename T>
+T *writable(const T *p) { return const_cast<T *>(p); }      // mcq_prepare* fill the blob through the view its readers use
 
 // CT: how a codebook entry is held (mcq_tf_kernels.h: one byte up to 256 entries per codebook, two above)
 template <typename CT>
@@ -222,6 +224,35 @@ thread_local int g_last_launches = 0;
         ++g_last_launches;                               \
     } while (0)
 
+// what a launch left behind, as the entry points return it: uncounted, and counted as MCQ_LAUNCH_CHECK counts
+inline int launch_rc() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+inline int counted_launch_rc() { MCQ_LAUNCH_CHECK(); return 0; }
+
+// Allow `kernel` up to `bytes` of dynamic LDS, once per device (a process may drive several).  `allowed` is the calling
+// launcher's static flag array: one per kernel instantiation.
+int allow_dynamic_lds(bool (&allowed)[64], const void *kernel, int bytes) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
+    if (!allowed[dev] || dev == 63) {
+        const hipError_t attr = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (attr != hipSuccess) return (int)attr;
+        allowed[dev] = true;
+    }
+    return 0;
+}
+
+// The launches of its scope as one interval of category `cat` of the profiler, if there is one: `{ Timed t(prof, CAT); launch }`
+struct Timed {
+    Prof *const prof;
+    const int cat;
+    Timed(Prof *p, int c) : prof(p), cat(c) { if (prof) prof->begin(cat); }
+    ~Timed() { if (prof) prof->end(cat); }
+    Timed(const Timed &) = delete;
+};
+
 // rows -> limb planes + exponents (+ |row|^2): the operands of every product of the path
 FixRowsArgs fix_rows_args(const float *src, int xh, long R, int D, long ld, int8_t *planes, int *exps, float *xx,
                           const float *bias_src = nullptr, float *bias_dst = nullptr, const float *sub = nullptr,
@@ -238,39 +269,28 @@ int launch_fix_rows(const float *src, int xh, long R, int D, long ld, int8_t *pl
     // four rows per workgroup, one per wave (16 rows per workgroup and 256-byte runs into the planes measured slower:
     // 0.086 vs 0.071 ms at 65,536 x 512)
     hipLaunchKernelGGL(k_fix_rows<4>, dim3((unsigned)(a.Rp / 4)), dim3(256), 0, st, a);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 int launch_fix_rows2(const FixRowsArgs &a, const FixRowsArgs &b, hipStream_t st) {
     const unsigned na = (unsigned)(a.Rp / 4), nb = (unsigned)(b.Rp / 4);
     hipLaunchKernelGGL(k_fix_rows2<4>, dim3(na + nb), dim3(256), 0, st, a, b, na);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 // the fixed-point GEMM: persistent workgroups of eight waves, one per CU
 template <int MODE>
 int launch_fgemm(FixGemm g, hipStream_t st) {
-    // the kernel's 132 KB of dynamic LDS has to be allowed once per device (a process may drive several)
-    static bool allowed[64] = {};
+    static bool allowed[64] = {};                      // (the kernel's 132 KB of dynamic LDS)
     constexpr int lds = MODE == FG_SCREEN ? kFixLdsScreen : kFixLds;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
-    if (!allowed[dev] || dev == 63) {
-        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fgemm<MODE>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (attr != hipSuccess) return (int)attr;
-        allowed[dev] = true;
-    }
+    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_fgemm<MODE>), lds)) return rc;
     const long MT = g.RA / kFixTile, NT = g.RB / kFixTile;
     const int H = (MODE != FG_STORE && g.K > kFixTile) ? g.K / kFixTile : 1;
     const long big = g.walk_rows ? NT : MT, small_units = (g.walk_rows ? MT : NT) / H;
     long units = (big + 7) / 8 * small_units;          // per XCD
     if (units > 32) units = 32;                        // 32 CUs per XCD, one workgroup each
     hipLaunchKernelGGL((k_fgemm<MODE>), dim3((unsigned)(8 * units)), dim3(512), lds, st, g);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 // XC[b][r] = fixdot(x_b, C_r) (or the Gram matrix with the centers as "frames"): frames stream, the centers are the table.
@@ -318,8 +338,7 @@ int launch_logits(const int8_t *xf, const int *xe, long B, const Prepared &P, in
     r.idx = idx; r.idx_wide = g.idx_wide; r.K = K; r.ncb = N; r.cnt = und_cnt; r.list = und_list; r.cap = g.und_cap;
     const long waves = B * N;          // a wave per pair at most, 4,096 waves (16 per CU) striding over the list at the most
     hipLaunchKernelGGL(k_fscreen_recheck, dim3((unsigned)(waves < 4096 ? (waves + 3) / 4 : 1024)), dim3(256), 0, st, r);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 // ---------------------------------------------------------------- the refinement pass
@@ -345,8 +364,7 @@ int launch_tf_stage0_k(int N, const float *G, const float *XC, const tf_code_of<
         default: return MCQ_EUNSUPPORTED;
     }
 #undef MCQ_S0_CASE
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 int launch_tf_stage0(int K, int N, const float *G, const float *XC, const uint16_t *idx, const float *R, const float *Q,
@@ -404,8 +422,7 @@ int launch_tf_er(int N, const float *G, const float *XC, const CT *idx, const fl
         default: return MCQ_EUNSUPPORTED;
     }
 #undef MCQ_ER_CASE
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 // group tables of level u >= 2 from those of level u - 1 (list lengths kh -> kc)
@@ -491,7 +508,7 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
         const int keep = (N == 2) ? 1 : L.kc[1];
         CT *fin = (N == 2) ? idx_new : nullptr;
         const dim3 grid((unsigned)(B * (N / 2)));
-        if (prof) prof->begin(CAT_LEVEL0);
+        Timed t(prof, CAT_LEVEL0);
         bool done0 = false;
         if constexpr (sizeof(CT) == 1) {
             // lists of 16 one-byte entries: the slot-major kernel (a 16-lane group of a gather = one table row: a fifth faster than
@@ -507,7 +524,6 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
         }
         if (!done0) MCQ_TF_LAUNCH2((k_tf_pair0<8, CT>), (k_tf_pair0<16, CT>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, fin, nact);
         MCQ_LAUNCH_CHECK();
-        if (prof) prof->end(CAT_LEVEL0);
     }
     // the level-1 combines and the cousin tables of level 2 share a launch (k_tf_level1): same workgroup-to-XCD mapping as the two
     // launches, one boundary and one tail less (5.95 -> 5.86 ms per encode of 65,536 vectors, 0.55 -> 0.51 ms at 4,096)
@@ -523,7 +539,7 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
         const int ntab3 = fuse_l3 ? 16 : 1, per3 = fuse_l3 ? 4 : 1;
         const unsigned vgrid = pair_blocks + tab_blocks + (fuse_l3 ? (unsigned)(B * ntab3) : 0u);
         const dim3 grid(pass_grid(vgrid, capped, kCapWave));
-        if (prof) prof->begin(CAT_LEVEL1_FUSED);
+        Timed t(prof, CAT_LEVEL1_FUSED);
         if (capped)
             MCQ_TF_LAUNCH2((k_tf_level1<8, 8, CT, true>), (k_tf_level1<16, 16, CT, true>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, ntab1,
                            per1, w.tabs[0], nact, pair_blocks, tab_blocks, ntab3, per3, w.tabs[1], vgrid);
@@ -531,15 +547,13 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
             MCQ_TF_LAUNCH2((k_tf_level1<8, 8, CT>), (k_tf_level1<16, 16, CT>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, ntab1, per1, w.tabs[0],
                            nact, pair_blocks, tab_blocks, ntab3, per3, w.tabs[1], vgrid);
         MCQ_LAUNCH_CHECK();
-        if (prof) prof->end(CAT_LEVEL1_FUSED);
     } else if (N >= 4) {   // level 1: pairs of codebooks
         const int keep = (N == 4) ? 1 : L.kc[2];
         CT *fin = (N == 4) ? idx_new : nullptr;
         const dim3 grid((unsigned)(B * (N / 4)));
-        if (prof) prof->begin(CAT_LEVEL1);
+        Timed t(prof, CAT_LEVEL1);
         MCQ_TF_LAUNCH2((k_tf_pair1<8, 8, CT>), (k_tf_pair1<16, 16, CT>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, fin, nact);
         MCQ_LAUNCH_CHECK();
-        if (prof) prof->end(CAT_LEVEL1);
     }
     for (int v = 2; v < nlev; ++v) {   // level v: level-1 tables of the cousins below, raised level by level, then the combine
         const int groups = N >> (v + 1);
@@ -549,37 +563,196 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
         const int per1 = 1 << (v - 1), ntab1 = groups * per1 * per1;
         const int cat_tab = (v == 2) ? CAT_TABLES : CAT_TABLES_UP, cat_comb = (v == 2) ? CAT_COMBINE : CAT_COMBINE_UP;
         if (!(fuse_l1 && v == 2) && !(fuse_l3 && v == 3)) {     // (these tables came with the level-1 combines)
-            if (prof) prof->begin(cat_tab);
+            Timed t(prof, cat_tab);
             MCQ_TF_LAUNCH2((k_tf_table1<8, 8, CT>), (k_tf_table1<16, 16, CT>), dim3((unsigned)(B * ntab1)), dim3(64), G, idx_cur, L, B, N, K, ntab1, per1,
                            w.tabs[0], nact);
             MCQ_LAUNCH_CHECK();
-            if (prof) prof->end(cat_tab);
         }
         if (N == 16 && v == 3) {       // two groups of eight: levels 2 and 3 in one kernel, tables in LDS
-            if (prof) prof->begin(cat_comb);
+            Timed t(prof, cat_comb);
             const float *t3 = fuse_l3 ? w.tabs[1] : w.tabs[0];
             MCQ_TF_LAUNCH2((k_tf_comb3<8, 16, 16, CT>), (k_tf_comb3<16, 32, 32, CT>), dim3((unsigned)B), dim3(256), idx_cur, w.E, L, B, N, t3, idx_new, nact);
             MCQ_LAUNCH_CHECK();
-            if (prof) prof->end(cat_comb);
             continue;
         }
         int cur = 0;
         for (int u = 2; u < v; ++u) {
             const int per = 1 << (v - u), ntab = groups * per * per;
-            if (prof) prof->begin(cat_tab);
-            const int rc = launch_tf_up(L.kc[u - 1], L.kc[u], L, B, N, u, ntab, per, w.tabs[cur], w.tabs[cur ^ 1], nact, st);
-            if (rc) return rc;
-            if (prof) prof->end(cat_tab);
+            Timed t(prof, cat_tab);
+            if (const int rc = launch_tf_up(L.kc[u - 1], L.kc[u], L, B, N, u, ntab, per, w.tabs[cur], w.tabs[cur ^ 1], nact, st)) return rc;
             cur ^= 1;
         }
-        if (prof) prof->begin(cat_comb);
-        const int rc = launch_tf_comb<CT>(L.kc[v - 1], L.kc[v], w.E, L, B, N, v, keep, w.tabs[cur], fin, nact, st, capped);
-        if (rc) return rc;
-        if (prof) prof->end(cat_comb);
+        Timed t(prof, cat_comb);
+        if (const int rc = launch_tf_comb<CT>(L.kc[v - 1], L.kc[v], w.E, L, B, N, v, keep, w.tabs[cur], fin, nact, st, capped)) return rc;
     }
     return 0;
 }
 #undef MCQ_TF_LAUNCH2
+
+// ---------------------------------------------------------------- the encode: checks, then per chunk start / pass16 or passes / tail
+struct EncodeCall {     // what every chunk of one call shares
+    Prepared P;
+    float lscale;
+    int N, K, D, iters;
+    unsigned flags;
+    hipStream_t st;
+    Prof *prof;
+};
+
+// Where a chunk's codes go: the caller's arrays at the chunk's first vector (null where the caller gave none)
+struct ChunkOut {
+    uint8_t *u8;            // out_u8: `pack` codes per byte
+    int64_t *i64;
+    uint8_t *also;          // codes_also: with i64, the same indexes as unpacked bytes [B][N]
+    int pack;
+    uint8_t *bytes() const { return u8 ? u8 : also; }        // the byte array of a kernel that writes one: out_u8, else codes_also
+    int bytes_pack() const { return u8 ? pack : 1; }         // (codes_also is never packed)
+};
+
+// The start of a chunk: its frames as limb planes, centered (x - mean: both products of the call read them; |x - mean|^2 rides
+// along), the initial codes -- imported, or the arg max of the logits -- and the x.C products the passes read
+template <typename CT>
+int launch_chunk_start(const EncodeCall &c, const WorkspaceT<CT> &w, const float *xc, long Bc, const int64_t *init_idx,
+                       float *logits_out) {
+    const int N = c.N, K = c.K, D = c.D;
+    // codes only: the initial arg max from six of the ten limb products, the pairs they leave open redone exactly (same
+    // codes).  The list lies in the x.C products, which the launch after the recheck writes; its counter is the last
+    // of the 64 pass counters (passes use the first 60), cleared by the frames' limb kernel
+    const bool screen = init_idx == nullptr && logits_out == nullptr && (c.flags & MCQ_ENCODE_EXACT_LOGITS) == 0 &&
+                        !exact_logits_forced() && (size_t)Bc * N < ((size_t)1 << 31);
+    unsigned *const und_cnt = reinterpret_cast<unsigned *>(w.cnt + 63), *const und_list = reinterpret_cast<unsigned *>(w.XC);
+    if (init_idx == nullptr || c.iters > 0) {
+        Timed t(c.prof, CAT_XX);
+        const int xh = (c.flags & MCQ_ENCODE_X_FP16) ? 1 : 0;   // rows of 2-byte elements
+        if (const int rc = launch_fix_rows(xc, xh, Bc, D, D, w.xf, w.xe, w.xx, c.st, c.P.mean, screen ? und_cnt : nullptr)) return rc;
+    }
+    if (init_idx != nullptr) {
+        hipLaunchKernelGGL(k_import_indexes<CT>, dim3((unsigned)((Bc * N + 255) / 256)), dim3(256), 0, c.st, init_idx, Bc * N, K, w.idx);
+        MCQ_LAUNCH_CHECK();
+        if (c.prof) c.prof->untimed();
+    } else {
+        Timed t(c.prof, CAT_LOGITS);
+        if (const int rc = launch_logits(w.xf, w.xe, Bc, c.P, N, K, D, c.lscale,
+                                         (c.flags & MCQ_ENCODE_LSCALE_FROM_PREPARED) ? c.P.scales + 1 : nullptr, logits_out, w.idx, c.st,
+                                         screen ? und_cnt : nullptr, und_list))
+            return rc;
+    }
+    if (c.iters > 0) {   // what the passes read per vector: the x.C products, once per call
+        Timed t(c.prof, CAT_XC);
+        if (const int rc = launch_xc(w.xf, w.xe, Bc, c.P.Cf, c.P.Ce, (long)N * K, D, w.XC, c.st)) return rc;
+    }
+    return 0;
+}
+
+// 16 or 8 codebooks of 16 entries (the trainer's first phase at 8 / 4 bytes per frame): ALL passes of the call in one launch of
+// persistent workgroups that hold the Gram matrix in LDS (mcq_pass16_kernels.h); a wave leaves a vector at its fixed point
+// by itself, without compaction.  Not under the profiler, whose categories are the separate launches.  The kernel writes the
+// caller's arrays itself where codes are not packed (out.pack == 1); packed nibbles leave through k_finalize, from w.idx
+int launch_pass16(const EncodeCall &c, const WorkspaceT<uint8_t> &w, long Bc, const ChunkOut &out) {
+    // the first pass16 call on a device opts BOTH shapes in: the other shape's first call may come inside a captured stream
+    static bool allowed16[64] = {}, allowed8[64] = {};
+    int rc = allow_dynamic_lds(allowed16, reinterpret_cast<const void *>(&k_tf_pass16<16>), p16_lds_bytes<16>());
+    if (rc == 0) rc = allow_dynamic_lds(allowed8, reinterpret_cast<const void *>(&k_tf_pass16<8>), p16_lds_bytes<8>());
+    if (rc) return rc;
+    Pass16Args a;
+    a.G = c.P.G; a.XC = w.XC; a.xx = w.xx; a.Q = c.P.Q; a.idx = w.idx; a.B = Bc; a.iters = c.iters;
+    a.out_i64 = out.pack == 1 ? out.i64 : nullptr;
+    a.out_u8 = out.pack == 1 ? out.bytes() : nullptr;
+    const long wgs = (Bc + kP16Waves - 1) / kP16Waves;
+    if (c.N == 16)   // one workgroup per CU (157,696 B of LDS), two with eight codebooks (62,464 B)
+        hipLaunchKernelGGL(k_tf_pass16<16>, dim3((unsigned)(wgs < 256 ? wgs : 256)), dim3(64 * kP16Waves), p16_lds_bytes<16>(), c.st, a);
+    else
+        hipLaunchKernelGGL(k_tf_pass16<8>, dim3((unsigned)(wgs < 512 ? wgs : 512)), dim3(64 * kP16Waves), p16_lds_bytes<8>(), c.st, a);
+    return counted_launch_rc();
+}
+
+// What moves from pass to pass.  Without skipping the indexes are refined in place in w.idx and nothing rotates.  Under skipping
+// k_compact packs the vectors still active after a pass to the front: slot s is the caller's row map[s], *nact slots are in use
+template <typename CT>
+struct PassState {
+    CT *idx_cur, *idx_new, *idx_pk;           // the indexes a pass reads / writes, and where k_compact packs the active ones
+    int *map_cur = nullptr, *map_nxt, *map_spare, *cnt;
+    const int *nact = nullptr;
+    // E / R of the active slots; under skipping with E / R formed in the emit they move with the indexes into the packed
+    // slots, between w.E / w.R and a second pair in the Gram-terms buffer (which only the first pass's k_tf_gram_terms uses)
+    float *E_cur, *R_cur, *E_alt, *R_alt;
+
+    PassState(const WorkspaceT<CT> &w, long Bc, bool skip)
+        : idx_cur(w.idx), idx_new(skip ? w.idxB : w.idx), idx_pk(w.idxC), map_nxt(w.map[0]), map_spare(w.map[1]), cnt(w.cnt),
+          E_cur(w.E), R_cur(w.R), E_alt(w.gterms), R_alt(w.gterms + ((Bc + 3) & ~3L)) {}
+
+    // after k_compact of pass `it`: the packed list becomes the current one, its map the current map (the first pass has none
+    // to hand back: the spare takes its place), its count the active count; E / R follow the indexes when the emit formed them
+    void rotate(int it, bool er_ready) {
+        std::swap(idx_cur, idx_pk);
+        std::swap(map_cur, map_nxt);
+        if (map_nxt == nullptr) map_nxt = map_spare;
+        nact = cnt + it;
+        if (er_ready) { std::swap(E_cur, E_alt); std::swap(R_cur, R_alt); }
+    }
+};
+
+// The refinement passes of a chunk as separate launches.  With two codebooks or more the last pass's winners go straight to
+// the caller's arrays (tf_emit; under skipping to row map[slot]); a single codebook's stay in w.idx for k_finalize.  skip: after
+// every pass but an emitting one k_compact retires the vectors the pass left unchanged (to the caller's arrays) and packs the rest
+template <typename CT>
+int run_passes(const EncodeCall &c, const WorkspaceT<CT> &w, long Bc, bool skip, const ChunkOut &out) {
+    const int N = c.N, K = c.K;
+    const Prepared &P = c.P;
+    PassState<CT> s(w, Bc, skip);
+    if (skip) {     // (a kernel, not hipMemsetAsync: replays of a captured encode have to clear them too, LAB_NOTEBOOK.md)
+        hipLaunchKernelGGL(k_zero_counts, dim3(1), dim3(64), 0, c.st, w.cnt, 64);
+        MCQ_LAUNCH_CHECK();
+        if (c.prof) c.prof->untimed();
+    }
+    // E / R of pass it + 1 can be formed by the wave that emits the indexes of pass it (tf_emit), which saves that pass
+    // its two E / R launches (4, 8 or 16 codebooks); under skipping k_compact moves them into the packed slots
+    const bool er_in_emit = (N == 4 || N == 8 || N == 16);
+    bool er_ready = false;
+    for (int it = 0; it < c.iters; ++it) {
+        const bool last_pass = (it + 1 == c.iters);
+        // capped grids over the active vectors from the fourth pass on (passes 1-3 hold nearly every vector of an
+        // untrained batch, and the strided kernels cost the dense passes a few per cent: DESIGN.md section 4)
+        const bool capped = skip && it >= 3;
+        if (!er_ready) {
+            Timed t(c.prof, CAT_ER);
+            if (const int rc = launch_tf_er<CT>(N, P.G, w.XC, s.idx_cur, w.xx, Bc, K, s.E_cur, s.R_cur, w.gterms, s.nact, s.map_cur, c.st))
+                return rc;
+        }
+        er_ready = false;
+        {
+            Timed t(c.prof, CAT_STAGE0);
+            if (const int rc = launch_tf_stage0(K, N, P.G, w.XC, s.idx_cur, s.R_cur, P.Q, Bc, (N == 1) ? 1 : w.tf.kc[0],
+                                                reinterpret_cast<CT *>(w.tf.ent), w.tf.S[0], (N == 1) ? s.idx_new : static_cast<CT *>(nullptr),
+                                                s.nact, s.map_cur, c.st, capped))
+                return rc;
+        }
+        const bool emits = N >= 2 && last_pass;
+        if (N >= 2) {
+            TfLists L = w.tf;
+            L.map = s.map_cur;
+            if (er_in_emit && !last_pass) {
+                L.erG = P.G; L.erXC = w.XC; L.erxx = w.xx; L.erE = s.E_cur; L.erR = s.R_cur; L.erK = K;
+                er_ready = true;
+            }
+            if (emits) { L.out_i64 = out.i64; L.out_u8 = out.bytes(); L.out_pack = out.bytes_pack(); }
+            WorkspaceT<CT> wc = w;
+            wc.E = s.E_cur; wc.R = s.R_cur;
+            if (const int rc = run_tf_combines<CT>(P.G, s.idx_cur, s.idx_new, wc, L, Bc, N, K, s.nact, c.st, c.prof, capped)) return rc;
+        }
+        if (skip && !emits) {
+            {
+                Timed t(c.prof, CAT_TAIL);
+                hipLaunchKernelGGL(k_compact<CT>, dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, c.st, s.idx_cur, s.idx_new, s.map_cur,
+                                   s.nact, Bc, N, last_pass ? 1 : 0, s.idx_pk, s.map_nxt, w.cnt + it, er_ready ? s.E_cur : nullptr,
+                                   er_ready ? s.R_cur : nullptr, s.E_alt, s.R_alt, out.pack, out.u8, out.i64, out.also);
+                MCQ_LAUNCH_CHECK();
+            }
+            s.rotate(it, er_ready);
+        }
+    }
+    return 0;
+}
 
 template <typename CT>
 int run_encode_t(const float *x, long B, const void *prepared, float lscale, int N, int K, int D, int iters,
@@ -599,173 +772,43 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
     if (chunk > B) chunk = B;
     if (chunk < B && chunk < 128) return MCQ_EWORKSPACE;
     if (chunk < B) chunk &= ~127L;
-    const Prepared P = prepared_view(prepared, N, K, D);
+    const EncodeCall c{prepared_view(prepared, N, K, D), lscale, N, K, D, iters, flags, st, prof};
     const int pack = (out_u8 != nullptr && K == 16 && N >= 2) ? 2 : 1;
     // fixed-point skipping (the default; MCQ_ENCODE_ALL_PASSES turns it off): vectors whose indexes a pass leaves unchanged
     // drop out of the later passes (k_compact) and their codes go straight to the caller's arrays; results are identical, the
     // cost becomes data dependent.  Below skip_min_batch() vectors per chunk the passes are bound by the launch chain, and the
     // compactions would only add launches to it
     const bool want_skip = (flags & MCQ_ENCODE_ALL_PASSES) == 0 && iters >= 3;     // (with two passes the second one holds ~every vector)
+    const bool use_p16 = sizeof(CT) == 1 && K == 16 && (N == 16 || N == 8) && iters > 0 && prof == nullptr && pass16_enabled();
 
     for (long lo = 0; lo < B; lo += chunk) {
         const long Bc = (B - lo < chunk) ? (B - lo) : chunk;
         const WorkspaceT<CT> w = carve<CT>(workspace, Bc, N, K, D);
-        const int xh = (flags & MCQ_ENCODE_X_FP16) ? 1 : 0;   // rows of 2-byte elements
-        const float *xc = xh ? reinterpret_cast<const float *>(reinterpret_cast<const uint16_t *>(x) + lo * D) : x + lo * D;
-        int rc;
-        // codes only: the initial arg max from six of the ten limb products, the pairs they leave open redone exactly (same
-        // codes).  The list lies in the x.C products, which the launch after the recheck writes; its counter is the last
-        // of the 64 pass counters (passes use the first 60), cleared by the frames' limb kernel
-        const bool screen = init_idx == nullptr && logits_out == nullptr && (flags & MCQ_ENCODE_EXACT_LOGITS) == 0 &&
-                            !exact_logits_forced() && (size_t)Bc * N < ((size_t)1 << 31);
-        unsigned *const und_cnt = reinterpret_cast<unsigned *>(w.cnt + 63), *const und_list = reinterpret_cast<unsigned *>(w.XC);
-        // the frames as limb planes, centered (x - mean: both products of the call read them; |x - mean|^2 rides along)
-        if (init_idx == nullptr || iters > 0) {
-            if (prof) prof->begin(CAT_XX);
-            rc = launch_fix_rows(xc, xh, Bc, D, D, w.xf, w.xe, w.xx, st, P.mean, screen ? und_cnt : nullptr);
-            if (rc) return rc;
-            if (prof) prof->end(CAT_XX);
-        }
-        if (init_idx != nullptr) {
-            hipLaunchKernelGGL(k_import_indexes<CT>, dim3((unsigned)((Bc * N + 255) / 256)), dim3(256), 0, st,
-                               init_idx + lo * N, Bc * N, K, w.idx);
-            MCQ_LAUNCH_CHECK();
-            if (prof) prof->untimed();
-        } else {
-            if (prof) prof->begin(CAT_LOGITS);
-            rc = launch_logits(w.xf, w.xe, Bc, P, N, K, D, lscale,
-                               (flags & MCQ_ENCODE_LSCALE_FROM_PREPARED) ? P.scales + 1 : nullptr,
-                               logits_out ? logits_out + lo * N * K : nullptr, w.idx, st, screen ? und_cnt : nullptr, und_list);
-            if (rc) return rc;
-            if (prof) prof->end(CAT_LOGITS);
-        }
-        if (iters > 0) {   // what the passes read per vector: the x.C products, once per call
-            if (prof) prof->begin(CAT_XC);
-            rc = launch_xc(w.xf, w.xe, Bc, P.Cf, P.Ce, (long)N * K, D, w.XC, st);
-            if (rc) return rc;
-            if (prof) prof->end(CAT_XC);
-        }
-        // 16 or 8 codebooks of 16 entries (the trainer's first phase at 8 / 4 bytes per frame): ALL passes of the call in one launch of
-        // persistent workgroups that hold the Gram matrix in LDS (mcq_pass16_kernels.h); a wave leaves a vector at its fixed point
-        // by itself, without compaction.  Not under the profiler, whose categories are the separate launches
-        const bool use_p16 = sizeof(CT) == 1 && K == 16 && (N == 16 || N == 8) && iters > 0 && prof == nullptr && pass16_enabled();
-        const bool skip = want_skip && !use_p16 && Bc >= skip_min_batch();
-        int iters_left = iters;
-        // without skipping: indexes are refined in place in w.idx, nothing is packed
-        CT *idx_cur = w.idx, *idx_new = skip ? w.idxB : w.idx, *idx_pk = w.idxC;
-        const int *map_cur = nullptr, *nact = nullptr;
-        int *map_nxt = w.map[0], *map_spare = w.map[1];
-        // E / R of the active slots; under skipping with E / R formed in the emit they move with the indexes into the packed
-        // slots, between w.E / w.R and a second pair in the Gram-terms buffer (which only the first pass's k_tf_gram_terms uses)
-        float *E_cur = w.E, *R_cur = w.R, *E_alt = w.gterms, *R_alt = w.gterms + ((Bc + 3) & ~3L);
-        if (skip) {     // (a kernel, not hipMemsetAsync: replays of a captured encode have to clear them too, LAB_NOTEBOOK.md)
-            hipLaunchKernelGGL(k_zero_counts, dim3(1), dim3(64), 0, st, w.cnt, 64);
-            MCQ_LAUNCH_CHECK();
-            if (prof) prof->untimed();
-        }
-        bool wrote_direct = false;
+        const ChunkOut out{out_u8 ? out_u8 + lo * (N / pack) : nullptr, out_i64 ? out_i64 + lo * N : nullptr,
+                           codes_also ? codes_also + lo * N : nullptr, pack};
+        const float *xc = (flags & MCQ_ENCODE_X_FP16) ? reinterpret_cast<const float *>(reinterpret_cast<const uint16_t *>(x) + lo * D)
+                                                      : x + lo * D;
+        if (const int rc = launch_chunk_start<CT>(c, w, xc, Bc, init_idx ? init_idx + lo * N : nullptr,
+                                                  logits_out ? logits_out + lo * N * K : nullptr))
+            return rc;
+        bool left = false;      // the codes are in the caller's arrays already; otherwise in w.idx, for k_finalize
         if constexpr (sizeof(CT) == 1) {
             if (use_p16) {
-                // (the dynamic LDS above 64 KB has to be allowed once per DEVICE: a process may drive several)
-                static bool allowed16[64] = {};
-                int dev = 0;
-                if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
-                if (!allowed16[dev] || dev == 63) {
-                    hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tf_pass16<16>),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, p16_lds_bytes<16>());
-                    if (attr == hipSuccess)
-                        attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tf_pass16<8>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, p16_lds_bytes<8>());
-                    if (attr != hipSuccess) return (int)attr;
-                    allowed16[dev] = true;
-                }
-                Pass16Args a;
-                a.G = P.G; a.XC = w.XC; a.xx = w.xx; a.Q = P.Q; a.idx = w.idx; a.B = Bc; a.iters = iters;
-                const bool direct_out = pack == 1;
-                a.out_i64 = (direct_out && out_i64) ? out_i64 + lo * N : nullptr;
-                a.out_u8 = direct_out ? (out_u8 ? out_u8 + lo * N : (codes_also ? codes_also + lo * N : nullptr)) : nullptr;
-                const long wgs = (Bc + kP16Waves - 1) / kP16Waves;
-                if (N == 16)   // one workgroup per CU (157,696 B of LDS), two with eight codebooks (62,464 B)
-                    hipLaunchKernelGGL(k_tf_pass16<16>, dim3((unsigned)(wgs < 256 ? wgs : 256)), dim3(64 * kP16Waves), p16_lds_bytes<16>(), st, a);
-                else
-                    hipLaunchKernelGGL(k_tf_pass16<8>, dim3((unsigned)(wgs < 512 ? wgs : 512)), dim3(64 * kP16Waves), p16_lds_bytes<8>(), st, a);
-                MCQ_LAUNCH_CHECK();
-                if (direct_out) continue;
-                iters_left = 0;
+                if (const int rc = launch_pass16(c, w, Bc, out)) return rc;
+                left = out.pack == 1;
             }
         }
-        // E / R of pass it + 1 can be formed by the wave that emits the indexes of pass it (tf_emit), which saves that pass
-        // its two E / R launches (4, 8 or 16 codebooks); under skipping k_compact moves them into the packed slots
-        const bool er_in_emit = (N == 4 || N == 8 || N == 16);
-        bool er_ready = false;
-        for (int it = 0; it < iters_left; ++it) {
-            const bool last_pass = (it + 1 == iters);
-            // capped grids over the active vectors from the fourth pass on (passes 1-3 hold nearly every vector of an
-            // untrained batch, and the strided kernels cost the dense passes a few per cent: DESIGN.md section 4)
-            const bool capped = skip && it >= 3;
-            if (!er_ready) {
-                if (prof) prof->begin(CAT_ER);
-                rc = launch_tf_er<CT>(N, P.G, w.XC, idx_cur, w.xx, Bc, K, E_cur, R_cur, w.gterms, nact, map_cur, st);
-                if (rc) return rc;
-                if (prof) prof->end(CAT_ER);
-            }
-            er_ready = false;
-            if (prof) prof->begin(CAT_STAGE0);
-            rc = launch_tf_stage0(K, N, P.G, w.XC, idx_cur, R_cur, P.Q, Bc, (N == 1) ? 1 : w.tf.kc[0], reinterpret_cast<CT *>(w.tf.ent),
-                                  w.tf.S[0], (N == 1) ? idx_new : static_cast<CT *>(nullptr), nact, map_cur, st, capped);
-            if (rc) return rc;
-            if (prof) prof->end(CAT_STAGE0);
-            bool direct_out = false;
-            if (N >= 2) {
-                // last pass: the winners go straight to the caller's arrays (tf_emit; under skipping to row map[slot])
-                TfLists L = w.tf;
-                L.map = map_cur;
-                if (er_in_emit && !last_pass) {
-                    L.erG = P.G; L.erXC = w.XC; L.erxx = w.xx; L.erE = E_cur; L.erR = R_cur; L.erK = K;
-                    er_ready = true;
-                }
-                direct_out = last_pass;
-                if (direct_out) {
-                    L.out_i64 = out_i64 ? out_i64 + lo * N : nullptr;
-                    L.out_u8 = out_u8 ? out_u8 + lo * (N / pack) : (codes_also ? codes_also + lo * N : nullptr);
-                    L.out_pack = out_u8 ? pack : 1;
-                    wrote_direct = true;
-                }
-                WorkspaceT<CT> wc = w;
-                wc.E = E_cur;
-                wc.R = R_cur;
-                rc = run_tf_combines<CT>(P.G, idx_cur, idx_new, wc, L, Bc, N, K, nact, st, prof, capped);
-                if (rc) return rc;
-            }
-            if (skip && !direct_out) {
-                if (prof) prof->begin(CAT_TAIL);
-                hipLaunchKernelGGL(k_compact<CT>, dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, idx_cur, idx_new,
-                                   map_cur, nact, Bc, N, last_pass ? 1 : 0, idx_pk, map_nxt, w.cnt + it,
-                                   er_ready ? E_cur : nullptr, er_ready ? R_cur : nullptr, E_alt, R_alt, pack,
-                                   out_u8 ? out_u8 + lo * (N / pack) : nullptr, out_i64 ? out_i64 + lo * N : nullptr,
-                                   codes_also ? codes_also + lo * N : nullptr);
-                MCQ_LAUNCH_CHECK();
-                if (prof) prof->end(CAT_TAIL);
-                // rotate: the packed list becomes the current one
-                CT *t = idx_cur; idx_cur = idx_pk; idx_pk = t;
-                int *old_map = const_cast<int *>(map_cur);
-                map_cur = map_nxt;
-                map_nxt = old_map ? old_map : map_spare;
-                nact = w.cnt + it;
-                if (er_ready) {
-                    std::swap(E_cur, E_alt);
-                    std::swap(R_cur, R_alt);
-                }
-            }
+        if (!use_p16) {
+            const bool skip = want_skip && Bc >= skip_min_batch();
+            if (const int rc = run_passes<CT>(c, w, Bc, skip, out)) return rc;
+            left = skip || (iters > 0 && N >= 2);      // every vector left through k_compact or the last emit / the last emit
         }
-        if (wrote_direct || skip) continue;      // (skipping: every vector left through k_compact or the last emit)
-        const long outn = (out_i64 != nullptr) ? Bc * N : Bc * (N / pack);
-        if (prof) prof->begin(CAT_TAIL);
-        hipLaunchKernelGGL(k_finalize<CT>, dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, st, w.idx, Bc, N, pack,
-                           out_u8 ? out_u8 + lo * (N / pack) : nullptr, out_i64 ? out_i64 + lo * N : nullptr,
-                           codes_also ? codes_also + lo * N : nullptr);
+        if (left) continue;
+        const long outn = out.i64 ? Bc * N : Bc * (N / pack);
+        Timed t(prof, CAT_TAIL);
+        hipLaunchKernelGGL(k_finalize<CT>, dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, st, w.idx, Bc, N, pack, out.u8, out.i64,
+                           out.also);
         MCQ_LAUNCH_CHECK();
-        if (prof) prof->end(CAT_TAIL);
     }
     return 0;
 }
@@ -811,8 +854,7 @@ int launch_decode_backward(const float *g, const IdxT *idx, long B, int N, int K
     if (cw == 4) hipLaunchKernelGGL((k_decode_backward<IdxT, 4>), grid, block, 0, st, g, idx, B, N, K, D, chunks, out, gsb, gsn, idx_stride, sa, sb, sc, dotw, dot_part);
     else if (cw == 2) hipLaunchKernelGGL((k_decode_backward<IdxT, 2>), grid, block, 0, st, g, idx, B, N, K, D, chunks, out, gsb, gsn, idx_stride, sa, sb, sc, dotw, dot_part);
     else hipLaunchKernelGGL((k_decode_backward<IdxT, 1>), grid, block, 0, st, g, idx, B, N, K, D, chunks, out, gsb, gsn, idx_stride, sa, sb, sc, dotw, dot_part);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 }  // namespace
 
@@ -842,25 +884,6 @@ int search_check(const float *tables, long Q, const uint8_t *codes, const float 
     if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;                  // (the inner product never reads w)
     const int need = N >= 16 ? 16 : N;                                    // a candidate's codes are loaded as one vector
     if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
-    return 0;
-}
-
-// what a launch left behind, as the entry points return it (not MCQ_LAUNCH_CHECK: that one counts encode launches)
-inline int launch_rc() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
-// Allow `kernel` up to `bytes` of dynamic LDS, once per device.  `allowed` is the calling launcher's static flag array: one
-// per kernel instantiation.
-int allow_dynamic_lds(bool (&allowed)[64], const void *kernel, int bytes) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
-    if (!allowed[dev] || dev == 63) {
-        const hipError_t attr = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (attr != hipSuccess) return (int)attr;
-        allowed[dev] = true;
-    }
     return 0;
 }
 
@@ -1037,6 +1060,131 @@ int range_check(const float *tables, long Q, const uint8_t *codes, const float *
 
 }  // namespace
 
+// ---- mcq_decode: a predicate and a launcher per path.  The paths are tried in the order below; the generic kernel takes the rest
+namespace {
+struct DecodeArgs {
+    const void *codes;
+    int code_bytes, codes_per_row, rep;       // rep = N / codes_per_row: codebooks that share a code (the generic kernel only)
+    long B;
+    const float *C;                           // the scaled centers [N * K][Dp]
+    int N, K, D, Dp;
+    float *out;
+    hipStream_t st;
+    // hooks: MCQ_DECODE_SLICED=0 (latched on first use) leaves the per-vector kernels only; MCQ_DECODE_BLK=0 skips the block-staged
+    // kernel; MCQ_DECODE_LDS_MIN=<n> moves the batch size from which a codebook slice is staged in LDS (both read per call)
+    bool sliced_ok, blk_on;
+    long lds_min_b;
+};
+
+// block-staged LDS-resident kernel (k_decode_blk): packed byte codes, 4, 8 or 16 per vector, 64-byte slices when they fit the
+// LDS beside the two code buffers, 32-byte slices otherwise (16 x 256)
+constexpr size_t kDecBlkLdsMax = 160 * 1024, kDecBlkCodeBytes = 2 * 16384;
+int decode_blk_lpv(int N, int K) {        // lanes per vector: 4 (64-byte slices), 2 (32-byte slices), 0: neither fits
+    if ((size_t)N * K * 64 + kDecBlkCodeBytes <= kDecBlkLdsMax) return 4;
+    return (size_t)N * K * 32 + kDecBlkCodeBytes <= kDecBlkLdsMax ? 2 : 0;
+}
+bool decode_blk_applies(const DecodeArgs &a) {
+    return a.blk_on && a.sliced_ok && a.rep == 1 && a.code_bytes == 1 && a.B >= a.lds_min_b && a.K >= 32 && (a.D & 3) == 0 &&
+           decode_blk_lpv(a.N, a.K) != 0 && (a.N == 4 || a.N == 8 || a.N == 16) &&
+           ((reinterpret_cast<uintptr_t>(a.codes) & 15) == 0) && ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0);
+}
+template <int NN, int LL>
+int launch_decode_blk_t(const DecodeArgs &a) {
+    static bool allowed[64] = {};
+    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_decode_blk<NN, LL>), (int)kDecBlkLdsMax)) return rc;
+    const int W = 4 * LL, ns = a.Dp / W, per_xcd = (ns + 7) / 8;
+    int groups = 256 / (8 * per_xcd);            // one workgroup per CU
+    groups = groups < 1 ? 1 : groups;
+    const long per = (((a.B + groups - 1) / groups) + 255) / 256 * 256;
+    hipLaunchKernelGGL((k_decode_blk<NN, LL>), dim3((unsigned)(8 * per_xcd * groups)), dim3(1024),
+                       (size_t)a.N * a.K * W * 4 + kDecBlkCodeBytes, a.st, static_cast<const uint8_t *>(a.codes), a.B, a.C, a.K, a.D,
+                       a.Dp, groups, per, a.out);
+    return launch_rc();
+}
+int launch_decode_blk(const DecodeArgs &a) {
+    const bool wide = decode_blk_lpv(a.N, a.K) == 4;
+    if (a.N == 4) return wide ? launch_decode_blk_t<4, 4>(a) : launch_decode_blk_t<4, 2>(a);
+    if (a.N == 8) return wide ? launch_decode_blk_t<8, 4>(a) : launch_decode_blk_t<8, 2>(a);
+    return wide ? launch_decode_blk_t<16, 4>(a) : launch_decode_blk_t<16, 2>(a);
+}
+
+// LDS-resident kernel: batches of >= 16,384 vectors whose codebook slice (N*K*64 B) fits the LDS
+// (N >= 8: with fewer rows per vector the L2 gathers of the sliced kernel measured faster; 36.9 vs 52.2 us at 8 x 256, 65,536 vectors)
+bool decode_lds_applies(const DecodeArgs &a) {
+    return a.sliced_ok && a.rep == 1 && a.B >= a.lds_min_b && (size_t)a.N * a.K * 64 <= 144 * 1024 && a.K >= 32 && a.N >= 8;
+}
+template <typename T>
+int launch_decode_lds(const DecodeArgs &a) {
+    const int ns = a.Dp / 16, per_xcd = (ns + 7) / 8;
+    int groups = 256 / (8 * per_xcd);            // one workgroup per CU
+    groups = groups < 1 ? 1 : groups;
+    hipLaunchKernelGGL((k_decode_lds<T>), dim3((unsigned)(8 * per_xcd * groups)), dim3(1024), (size_t)a.N * a.K * 64, a.st,
+                       static_cast<const T *>(a.codes), a.B, a.C, a.N, a.K, a.D, a.Dp, groups, a.out);
+    return launch_rc();
+}
+
+// XCD-sliced kernel: unpacked codes, batches big enough to fill the chip (16-entry codebooks: the per-vector kernels measured
+// faster), rows that 8 slices x at most 64 lanes x 4 floats cover
+int decode_sliced_lpv(int Dp) {
+    int lpv = 4;
+    while (lpv * 32 < Dp) lpv *= 2;          // 8 slices x lpv lanes x 4 floats cover Dp
+    return lpv;
+}
+bool decode_sliced_applies(const DecodeArgs &a) {
+    return a.sliced_ok && a.rep == 1 && a.B >= 4096 && a.K >= 32 && decode_sliced_lpv(a.Dp) <= 64;
+}
+template <typename T, int CHH>
+int launch_decode_sliced_t(const DecodeArgs &a) {
+    const int lpv = decode_sliced_lpv(a.Dp), vpw = 64 / lpv;
+    const dim3 g((unsigned)(((a.B + 4 * vpw - 1) / (4 * vpw)) * 8));
+#define MCQ_DECS_LAUNCH(LL) \
+    hipLaunchKernelGGL((k_decode_sliced<T, CHH, LL>), g, dim3(256), 0, a.st, static_cast<const T *>(a.codes), a.B, a.C, a.N, a.K, a.D, a.Dp, a.out)
+    switch (lpv) {
+        case 4: MCQ_DECS_LAUNCH(4); break;
+        case 8: MCQ_DECS_LAUNCH(8); break;
+        case 16: MCQ_DECS_LAUNCH(16); break;
+        case 32: MCQ_DECS_LAUNCH(32); break;
+        default: MCQ_DECS_LAUNCH(64); break;
+    }
+#undef MCQ_DECS_LAUNCH
+    return launch_rc();
+}
+template <typename T>
+int launch_decode_sliced(const DecodeArgs &a) {
+    if (a.N <= 4) return launch_decode_sliced_t<T, 4>(a);
+    return a.N <= 8 ? launch_decode_sliced_t<T, 8>(a) : launch_decode_sliced_t<T, 16>(a);
+}
+
+// register kernel (k_decode_reg<N, J>): one-byte codes of 2, 4, 8 or 16 codebooks, J = float4s per lane of a row
+#define MCQ_DEC_REG_SHAPES(X) X(8, 2) X(8, 1) X(4, 1) X(4, 2) X(4, 4) X(16, 1) X(16, 2) X(2, 1) X(2, 2)
+bool decode_reg_applies(const DecodeArgs &a) {
+    const int J = (a.Dp / 4 + 63) / 64;
+#define MCQ_DEC_CASE(NN, JJ) || (a.N == NN && J == JJ)
+    return a.code_bytes == 1 && a.rep == 1 && (false MCQ_DEC_REG_SHAPES(MCQ_DEC_CASE));
+#undef MCQ_DEC_CASE
+}
+int launch_decode_reg(const DecodeArgs &a) {
+    const int J = (a.Dp / 4 + 63) / 64;
+#define MCQ_DEC_CASE(NN, JJ)                                                                                                  \
+    if (a.N == NN && J == JJ) {                                                                                               \
+        hipLaunchKernelGGL((k_decode_reg<NN, JJ>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, a.st,                         \
+                           static_cast<const uint8_t *>(a.codes), a.B, a.C, a.K, a.D, a.Dp, a.out);                             \
+        return launch_rc();                                                                                                   \
+    }
+    MCQ_DEC_REG_SHAPES(MCQ_DEC_CASE)
+#undef MCQ_DEC_CASE
+    return MCQ_EUNSUPPORTED;      // (not reached: decode_reg_applies)
+}
+#undef MCQ_DEC_REG_SHAPES
+
+template <typename T>
+int launch_decode_generic(const DecodeArgs &a) {
+    hipLaunchKernelGGL((k_decode<T>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, a.st, static_cast<const T *>(a.codes),
+                       a.codes_per_row, a.B, a.C, a.N, a.K, a.D, a.Dp, a.out);
+    return launch_rc();
+}
+}  // namespace
+
 
 extern "C" {
 
@@ -1055,42 +1203,27 @@ static int prepare_impl(const float *centers, float cscale_exp, const float *sca
     if (!domain_ok(N, K, D)) return domain_err(N, K, D);
     if (!centers || !prepared || ((weight == nullptr) != (bias == nullptr))) return MCQ_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const PreparedLayout l = prepared_layout(N, K, D);
-    char *b = static_cast<char *>(prepared);
+    const Prepared P = prepared_view(prepared, N, K, D);       // (filled here: writable() below)
     const long rows = (long)N * K;
     const int Dp = round_up16(D);
-    const unsigned grid = (unsigned)((rows + 3) / 4);
-    hipLaunchKernelGGL(k_prepare_rows, dim3(grid), dim3(256), 0, st, centers, cscale_exp, 1, rows, D, Dp,
-                       reinterpret_cast<float *>(b + l.offC), static_cast<float *>(nullptr) /* Q: of the centered rows, below */, scales_dev,
-                       (scales_dev || raw_cs) ? reinterpret_cast<float *>(b + l.offScales) : static_cast<float *>(nullptr), raw_cs,
-                       raw_ls, speed, scales_out2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_prepare_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, centers, cscale_exp, 1, rows, D, Dp,
+                       writable(P.C), static_cast<float *>(nullptr) /* Q: of the centered rows, below */, scales_dev,
+                       (scales_dev || raw_cs) ? writable(P.scales) : static_cast<float *>(nullptr), raw_cs, raw_ls, speed, scales_out2);
+    if (const int rc = launch_rc()) return rc;
     if (!weight) return 0;      // decode only: the scaled centers are all mcq_decode reads (mcq_prepared_decode_bytes)
-    const float *C = reinterpret_cast<const float *>(b + l.offC);
-    float *cmean = reinterpret_cast<float *>(b + l.offCMean);
-    hipLaunchKernelGGL(k_centers_mean, dim3((unsigned)(Dp / 16)), dim3(1024), 0, st, C, N, K, Dp,
-                       reinterpret_cast<float *>(b + l.offMean), cmean);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_centers_mean, dim3((unsigned)(Dp / 16)), dim3(1024), 0, st, P.C, N, K, Dp, writable(P.mean), writable(P.cmean));
+    if (const int rc = launch_rc()) return rc;
     // the scaled centers and the classifier rows as limb planes (the tables of the fixed-point products), one launch; the
     // bias rides along
     // (the centers enter every table of the search with their codebook's mean taken out -- oracle "TABLE FORM", centering; their
     // sums of squares Q come out of the same pass)
-    int rc = launch_fix_rows2(fix_rows_args(C, 0, rows, Dp, Dp, reinterpret_cast<int8_t *>(b + l.offCf), reinterpret_cast<int *>(b + l.offCe),
-                                            reinterpret_cast<float *>(b + l.offQ), nullptr, nullptr, cmean, K, Dp),
-                              fix_rows_args(weight, 0, rows, D, D, reinterpret_cast<int8_t *>(b + l.offWf), reinterpret_cast<int *>(b + l.offWe),
-                                            nullptr, bias, reinterpret_cast<float *>(b + l.offBias), nullptr, 0, 0,
-                                            reinterpret_cast<const float *>(b + l.offMean), reinterpret_cast<float *>(b + l.offWmu)), st);
-    if (rc) return rc;
-    {
-        // Gram matrix of the scaled centers: the x.C product with the centers themselves as the frames
-        rc = launch_xc(reinterpret_cast<const int8_t *>(b + l.offCf), reinterpret_cast<const int *>(b + l.offCe), rows,
-                       reinterpret_cast<const int8_t *>(b + l.offCf), reinterpret_cast<const int *>(b + l.offCe), rows, D,
-                       reinterpret_cast<float *>(b + l.offG), st);
-        if (rc) return rc;
-    }
-    return 0;
+    if (const int rc = launch_fix_rows2(
+            fix_rows_args(P.C, 0, rows, Dp, Dp, writable(P.Cf), writable(P.Ce), writable(P.Q), nullptr, nullptr, P.cmean, K, Dp),
+            fix_rows_args(weight, 0, rows, D, D, writable(P.Wf), writable(P.We), nullptr, bias, writable(P.bias), nullptr, 0, 0, P.mean,
+                          writable(P.wmu)), st))
+        return rc;
+    // Gram matrix of the scaled centers: the x.C product with the centers themselves as the frames
+    return launch_xc(P.Cf, P.Ce, rows, P.Cf, P.Ce, rows, D, writable(P.G), st);
 }
 
 size_t mcq_prepared_decode_bytes(int N, int K, int D) {
@@ -1158,124 +1291,16 @@ int mcq_decode(const void *codes, int code_bytes, int codes_per_row, long B, con
     if (code_bytes != 1 && code_bytes != 8) return MCQ_EINVAL;
     if (B == 0) return 0;
     if (!codes || !prepared || !out) return MCQ_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const Prepared P = prepared_view(prepared, N, K, D);
-    const int Dp = round_up16(D);
-    const unsigned grid = (unsigned)((B + 3) / 4);
-    const int J = (Dp / 4 + 63) / 64;
-    // XCD-sliced kernel (unpacked codes, batches big enough to fill the chip; MCQ_DECODE_SLICED=0 disables: tuning hook)
     static const bool sliced_ok = !(getenv("MCQ_DECODE_SLICED") && atoi(getenv("MCQ_DECODE_SLICED")) == 0);
-    // LDS-resident kernel: batches of >= 16,384 vectors whose codebook slice (N*K*64 B) fits the LDS
-    // (N >= 8: with fewer rows per vector the L2 gathers of the sliced kernel measured faster; 36.9 vs 52.2 us at 8 x 256, 65,536 vectors)
-    const char *lds_env = getenv("MCQ_DECODE_LDS_MIN");   // test / tuning hook, read per call
-    const long lds_min_b = lds_env ? atol(lds_env) : 16384;
-    // block-staged LDS-resident kernel (k_decode_blk): packed byte codes, 4, 8 or 16 per vector, 64-byte slices when they fit the
-    // LDS beside the two code buffers, 32-byte slices otherwise (16 x 256).  MCQ_DECODE_BLK=0: the other kernels (tuning hook)
-    {
-        const char *blk_env = getenv("MCQ_DECODE_BLK");
-        const int blk_mode = blk_env ? atoi(blk_env) : 1;
-        const size_t lds_max = 160 * 1024, cbytes = 2 * 16384;
-        int lpv = 0;
-        if ((size_t)N * K * 64 + cbytes <= lds_max) lpv = 4;
-        else if ((size_t)N * K * 32 + cbytes <= lds_max) lpv = 2;
-        if (blk_mode != 0 && sliced_ok && rep == 1 && code_bytes == 1 && B >= lds_min_b && K >= 32 && (D & 3) == 0 && lpv != 0 &&
-            (N == 4 || N == 8 || N == 16) && ((reinterpret_cast<uintptr_t>(codes) & 15) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0)) {
-            const int W = 4 * lpv, ns = Dp / W, per_xcd = (ns + 7) / 8;
-            int groups = 256 / (8 * per_xcd);            // one workgroup per CU
-            groups = groups < 1 ? 1 : groups;
-            const unsigned g = (unsigned)(8 * per_xcd * groups);
-            const long per = (((B + groups - 1) / groups) + 255) / 256 * 256;
-            const size_t lds = (size_t)N * K * W * 4 + cbytes;
-            const uint8_t *cp = static_cast<const uint8_t *>(codes);
-#define MCQ_DECB(NN, LL)                                                                                                    \
-    do {                                                                                                                    \
-        static bool allowed[64] = {};                                                                                       \
-        int dev = 0;                                                                                                        \
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;                                             \
-        if (!allowed[dev] || dev == 63) {                                                                                   \
-            const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode_blk<NN, LL>),              \
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);          \
-            if (attr != hipSuccess) return (int)attr;                                                                       \
-            allowed[dev] = true;                                                                                            \
-        }                                                                                                                   \
-        hipLaunchKernelGGL((k_decode_blk<NN, LL>), dim3(g), dim3(1024), lds, st, cp, B, P.C, K, D, Dp, groups, per, out);   \
-    } while (0)
-            if (N == 4) { if (lpv == 4) MCQ_DECB(4, 4); else MCQ_DECB(4, 2); }
-            else if (N == 8) { if (lpv == 4) MCQ_DECB(8, 4); else MCQ_DECB(8, 2); }
-            else { if (lpv == 4) MCQ_DECB(16, 4); else MCQ_DECB(16, 2); }
-#undef MCQ_DECB
-            hipError_t e6 = hipGetLastError();
-            return e6 == hipSuccess ? 0 : (int)e6;
-        }
-    }
-    if (sliced_ok && rep == 1 && B >= lds_min_b && (size_t)N * K * 64 <= 144 * 1024 && K >= 32 && N >= 8) {
-        const int ns = Dp / 16, per_xcd = (ns + 7) / 8;
-        int groups = 256 / (8 * per_xcd);            // one workgroup per CU
-        groups = groups < 1 ? 1 : groups;
-        const unsigned g = (unsigned)(8 * per_xcd * groups);
-        const size_t lds = (size_t)N * K * 64;
-        if (code_bytes == 1)
-            hipLaunchKernelGGL((k_decode_lds<uint8_t>), dim3(g), dim3(1024), lds, st, static_cast<const uint8_t *>(codes), B,
-                               P.C, N, K, D, Dp, groups, out);
-        else
-            hipLaunchKernelGGL((k_decode_lds<int64_t>), dim3(g), dim3(1024), lds, st, static_cast<const int64_t *>(codes), B,
-                               P.C, N, K, D, Dp, groups, out);
-        hipError_t e4 = hipGetLastError();
-        return e4 == hipSuccess ? 0 : (int)e4;
-    }
-    if (sliced_ok && rep == 1 && B >= 4096 && K >= 32) {   // (16-entry codebooks: the per-vector kernels measured faster)
-        int lpv = 4;
-        while (lpv * 32 < Dp) lpv *= 2;          // 8 slices x lpv lanes x 4 floats cover Dp
-        if (lpv <= 64) {
-            const int vpw = 64 / lpv;
-            const unsigned g = (unsigned)(((B + 4 * vpw - 1) / (4 * vpw)) * 8);
-#define MCQ_DECS_LAUNCH(T, CHH, LL)                                                                              \
-    hipLaunchKernelGGL((k_decode_sliced<T, CHH, LL>), dim3(g), dim3(256), 0, st, static_cast<const T *>(codes), B, P.C, N, \
-                       K, D, Dp, out)
-#define MCQ_DECS_LPV(T, CHH)                                                                                     \
-    switch (lpv) {                                                                                               \
-        case 4: MCQ_DECS_LAUNCH(T, CHH, 4); break;                                                               \
-        case 8: MCQ_DECS_LAUNCH(T, CHH, 8); break;                                                               \
-        case 16: MCQ_DECS_LAUNCH(T, CHH, 16); break;                                                             \
-        case 32: MCQ_DECS_LAUNCH(T, CHH, 32); break;                                                             \
-        default: MCQ_DECS_LAUNCH(T, CHH, 64); break;                                                             \
-    }
-            if (code_bytes == 1) {
-                if (N <= 4) { MCQ_DECS_LPV(uint8_t, 4) } else if (N <= 8) { MCQ_DECS_LPV(uint8_t, 8) } else { MCQ_DECS_LPV(uint8_t, 16) }
-            } else {
-                if (N <= 4) { MCQ_DECS_LPV(int64_t, 4) } else if (N <= 8) { MCQ_DECS_LPV(int64_t, 8) } else { MCQ_DECS_LPV(int64_t, 16) }
-            }
-#undef MCQ_DECS_LPV
-#undef MCQ_DECS_LAUNCH
-            hipError_t e3 = hipGetLastError();
-            return e3 == hipSuccess ? 0 : (int)e3;
-        }
-    }
-#define MCQ_DEC_CASE(NN, JJ)                                                                                    \
-    if (code_bytes == 1 && rep == 1 && N == NN && J == JJ) {                                                    \
-        hipLaunchKernelGGL((k_decode_reg<NN, JJ>), dim3(grid), dim3(256), 0, st, static_cast<const uint8_t *>(codes), \
-                           B, P.C, K, D, Dp, out);                                                              \
-        hipError_t e2 = hipGetLastError();                                                                      \
-        return e2 == hipSuccess ? 0 : (int)e2;                                                                  \
-    }
-    MCQ_DEC_CASE(8, 2)
-    MCQ_DEC_CASE(8, 1)
-    MCQ_DEC_CASE(4, 1)
-    MCQ_DEC_CASE(4, 2)
-    MCQ_DEC_CASE(4, 4)
-    MCQ_DEC_CASE(16, 1)
-    MCQ_DEC_CASE(16, 2)
-    MCQ_DEC_CASE(2, 1)
-    MCQ_DEC_CASE(2, 2)
-#undef MCQ_DEC_CASE
-    if (code_bytes == 1)
-        hipLaunchKernelGGL((k_decode<uint8_t>), dim3(grid), dim3(256), 0, st, static_cast<const uint8_t *>(codes),
-                           codes_per_row, B, P.C, N, K, D, Dp, out);
-    else
-        hipLaunchKernelGGL((k_decode<int64_t>), dim3(grid), dim3(256), 0, st, static_cast<const int64_t *>(codes),
-                           codes_per_row, B, P.C, N, K, D, Dp, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    const char *blk_env = getenv("MCQ_DECODE_BLK"), *lds_env = getenv("MCQ_DECODE_LDS_MIN");
+    const DecodeArgs a{codes, code_bytes, codes_per_row, rep, B, prepared_view(prepared, N, K, D).C, N, K, D, round_up16(D), out,
+                       static_cast<hipStream_t>(stream), sliced_ok, (blk_env ? atoi(blk_env) : 1) != 0, lds_env ? atol(lds_env) : 16384};
+    const bool u8 = code_bytes == 1;
+    if (decode_blk_applies(a)) return launch_decode_blk(a);
+    if (decode_lds_applies(a)) return u8 ? launch_decode_lds<uint8_t>(a) : launch_decode_lds<int64_t>(a);
+    if (decode_sliced_applies(a)) return u8 ? launch_decode_sliced<uint8_t>(a) : launch_decode_sliced<int64_t>(a);
+    if (decode_reg_applies(a)) return launch_decode_reg(a);
+    return u8 ? launch_decode_generic<uint8_t>(a) : launch_decode_generic<int64_t>(a);
 }
 
 int mcq_decode_backward(const float *grad_out, const int64_t *idx, long B, int N, int K, int D, float *gC,
@@ -1307,8 +1332,7 @@ int mcq_jcl_prefix_fwd(const float *hp, const float *emb, const int64_t *idx, lo
     if (!hp || !emb || !idx || !A) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_jcl_prefix_fwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), hp,
                        emb, idx, B, N, K, H, scale, A);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 
 int mcq_jcl_prefix_bwd(const float *A, const float *gA, long B, int N, int H, float scale, float *g_hp, float *gE,
@@ -1318,8 +1342,7 @@ int mcq_jcl_prefix_bwd(const float *A, const float *gA, long B, int N, int H, fl
     if (!A || !gA || !g_hp || !gE) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_jcl_prefix_bwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), A,
                        gA, B, N, H, scale, g_hp, gE);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 
 namespace {
@@ -1332,16 +1355,9 @@ struct LogitsWs {
 };
 LogitsWs logits_ws(void *ws, long B, int N, int D) {
     char *p = static_cast<char *>(ws);
-    LogitsWs w;
-    size_t off = 0;
-    w.idx8 = reinterpret_cast<uint8_t *>(p + off);
-    off = align256(off + (size_t)B * N);
-    w.xf = reinterpret_cast<int8_t *>(p + off);
-    off = align256(off + fix_plane_bytes(B, D));
-    w.xe = reinterpret_cast<int *>(p + off);
-    off = align256(off + (size_t)fix_round_rows(B) * 4);
-    w.total = off;
-    return w;
+    const size_t o1 = align256((size_t)B * N), o2 = align256(o1 + fix_plane_bytes(B, D));
+    return LogitsWs{reinterpret_cast<uint8_t *>(p), reinterpret_cast<int8_t *>(p + o1), reinterpret_cast<int *>(p + o2),
+                    align256(o2 + (size_t)fix_round_rows(B) * 4)};
 }
 }  // namespace
 
@@ -1350,18 +1366,23 @@ size_t mcq_logits_workspace_bytes(long B, int N, int D) {
     return logits_ws(nullptr, B, N, D).total;
 }
 
+// frames to limb planes, then the stored logits (and, with idx8, the arg max bytes): what the two entry points below share
+static int run_logits(const float *x, long B, const void *prepared, float lscale_exp, int N, int K, int D, float *out, uint8_t *idx8,
+                      const LogitsWs &w, hipStream_t st, unsigned flags) {
+    const Prepared P = prepared_view(prepared, N, K, D);
+    // (the logits product reads centered frames: FixGemm::wmu)
+    if (const int rc = launch_fix_rows(x, (flags & MCQ_ENCODE_X_FP16) ? 1 : 0, B, D, D, w.xf, w.xe, nullptr, st, P.mean)) return rc;
+    return launch_logits(w.xf, w.xe, B, P, N, K, D, lscale_exp, (flags & MCQ_ENCODE_LSCALE_FROM_PREPARED) ? P.scales + 1 : nullptr, out,
+                         idx8, st);
+}
+
 int mcq_logits(const float *x, long B, const void *prepared, float lscale_exp, int N, int K, int D, float *out,
                void *workspace, size_t workspace_bytes, void *stream) {
-    if (!domain_ok(N, K, D)) return MCQ_EUNSUPPORTED;
+    if (!domain_ok(N, K, D)) return MCQ_EUNSUPPORTED;        // (for ANY shape outside the domain, N = 3 included)
     if (B == 0) return 0;
     if (!x || !prepared || !out || B < 0 || !workspace) return MCQ_EINVAL;
     if (workspace_bytes < mcq_logits_workspace_bytes(B, N, D)) return MCQ_EWORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const Prepared P = prepared_view(prepared, N, K, D);
-    const LogitsWs w = logits_ws(workspace, B, N, D);
-    int rc = launch_fix_rows(x, 0, B, D, D, w.xf, w.xe, nullptr, st, P.mean);      // (the logits product reads centered frames: FixGemm::wmu)
-    if (rc) return rc;
-    return launch_logits(w.xf, w.xe, B, P, N, K, D, lscale_exp, nullptr, out, nullptr, st);
+    return run_logits(x, B, prepared, lscale_exp, N, K, D, out, nullptr, logits_ws(workspace, B, N, D), static_cast<hipStream_t>(stream), 0);
 }
 
 // ------------------------------------------------------------------ trainer pieces
@@ -1374,16 +1395,10 @@ int mcq_logits_argmax(const float *x, long B, const void *prepared, float lscale
     if (!x || !prepared || !logits_out || !argmax_out || !workspace) return MCQ_EINVAL;
     if (workspace_bytes < mcq_logits_workspace_bytes(B, N, D)) return MCQ_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Prepared P = prepared_view(prepared, N, K, D);
     const LogitsWs w = logits_ws(workspace, B, N, D);
-    int rc = launch_fix_rows(x, (flags & MCQ_ENCODE_X_FP16) ? 1 : 0, B, D, D, w.xf, w.xe, nullptr, st, P.mean);
-    if (rc) return rc;
-    rc = launch_logits(w.xf, w.xe, B, P, N, K, D, lscale_exp,
-                       (flags & MCQ_ENCODE_LSCALE_FROM_PREPARED) ? P.scales + 1 : nullptr, logits_out, w.idx8, st);
-    if (rc) return rc;
+    if (const int rc = run_logits(x, B, prepared, lscale_exp, N, K, D, logits_out, w.idx8, w, st, flags)) return rc;
     hipLaunchKernelGGL(k_export_indexes, dim3((unsigned)((B * N + 255) / 256)), dim3(256), 0, st, w.idx8, B * N, argmax_out);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 // logits (stored) + arg max + refinement passes in one call: the frames become limb planes once, the indexes stay bytes
@@ -1412,6 +1427,33 @@ long loss_rows_per_chunk(long B) {   // at most ~1024 chunks, at least 64 rows e
     return (r + 15) / 16 * 16;
 }
 long loss_chunks(long B) { const long r = loss_rows_per_chunk(B); return (B + r - 1) / r; }
+
+// the loss kernels' shapes; cap_n: one entropy pair per codebook in shared memory (s_hl / s_hi of loss_tail_body: 64)
+bool loss_domain_ok(int N, int K, bool cap_n) { return is_pow2(K) && K >= 16 && K <= 256 && N >= 1 && (!cap_n || N <= 64); }
+
+// workgroups of k_loss_bwd: kLossWaves waves, each on 64 / K rows of the [B * N][K] logits at a time (one row from K = 64 on)
+long loss_bwd_blocks(long B, int N, int K) {
+    const int rpw = K < 64 ? 64 / K : 1;
+    return (B * N + (long)kLossWaves * rpw - 1) / ((long)kLossWaves * rpw);
+}
+
+// mcq_loss_bwd, and mcq_loss_bwd_ex (ex: bias and dot_part are required; the kernel's own defaults for them are null)
+int launch_loss_bwd(const float *logits, const int64_t *idx, const float *lse, long B, int N, int K, const float *g_chosen,
+                    const float *g_prob, float *grad_logits, const float *bias, float *dot_part, bool ex, void *stream) {
+    if (!loss_domain_ok(N, K, false)) return MCQ_EUNSUPPORTED;
+    if (B <= 0) return MCQ_EINVAL;
+    if (!logits || !idx || !lse || !g_chosen || !g_prob || !grad_logits || (ex && (!bias || !dot_part))) return MCQ_EINVAL;
+    const dim3 grid((unsigned)loss_bwd_blocks(B, N, K)), block(64 * kLossWaves);
+#define MCQ_LOSS_CASE(KK)                                                                                             \
+    case KK: hipLaunchKernelGGL((k_loss_bwd<KK>), grid, block, 0, static_cast<hipStream_t>(stream), logits, idx, lse, B, N, g_chosen, \
+                                g_prob, grad_logits, bias, dot_part); break;
+    switch (K) {
+        MCQ_LOSS_CASE(16) MCQ_LOSS_CASE(32) MCQ_LOSS_CASE(64) MCQ_LOSS_CASE(128) MCQ_LOSS_CASE(256)
+        default: return MCQ_EUNSUPPORTED;
+    }
+#undef MCQ_LOSS_CASE
+    return counted_launch_rc();
+}
 }  // namespace
 
 size_t mcq_loss_workspace_bytes(long B, int N, int K) {
@@ -1421,7 +1463,7 @@ size_t mcq_loss_workspace_bytes(long B, int N, int K) {
 
 int mcq_loss_fwd(const float *logits, const int64_t *idx, long B, int N, int K, float *lse, float *chosen_sum,
                  float *prob_sum, float *count, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!is_pow2(K) || K < 16 || K > 256 || N < 1) return MCQ_EUNSUPPORTED;
+    if (!loss_domain_ok(N, K, false)) return MCQ_EUNSUPPORTED;
     if (B <= 0) return MCQ_EINVAL;
     if (!logits || !idx || !lse || !chosen_sum || !prob_sum || !count || !workspace) return MCQ_EINVAL;
     if (workspace_bytes < mcq_loss_workspace_bytes(B, N, K)) return MCQ_EWORKSPACE;
@@ -1441,38 +1483,21 @@ int mcq_loss_fwd(const float *logits, const int64_t *idx, long B, int N, int K, 
     MCQ_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_loss_reduce, dim3((unsigned)N), dim3(256), 0, st, pp, pc, ph, chunks, N, K, prob_sum, count,
                        chosen_sum);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 int mcq_loss_bwd(const float *logits, const int64_t *idx, const float *lse, long B, int N, int K, const float *g_chosen,
                  const float *g_prob, float *grad_logits, void *stream) {
-    if (!is_pow2(K) || K < 16 || K > 256 || N < 1) return MCQ_EUNSUPPORTED;
-    if (B <= 0) return MCQ_EINVAL;
-    if (!logits || !idx || !lse || !g_chosen || !g_prob || !grad_logits) return MCQ_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int rpw = K < 64 ? 64 / K : 1;
-    const long rows = B * N;
-    const dim3 grid((unsigned)((rows + (long)kLossWaves * rpw - 1) / ((long)kLossWaves * rpw))), block(64 * kLossWaves);
-#define MCQ_LOSS_CASE(KK)                                                                                             \
-    case KK: hipLaunchKernelGGL((k_loss_bwd<KK>), grid, block, 0, st, logits, idx, lse, B, N, g_chosen, g_prob, grad_logits); break;
-    switch (K) {
-        MCQ_LOSS_CASE(16) MCQ_LOSS_CASE(32) MCQ_LOSS_CASE(64) MCQ_LOSS_CASE(128) MCQ_LOSS_CASE(256)
-        default: return MCQ_EUNSUPPORTED;
-    }
-#undef MCQ_LOSS_CASE
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return launch_loss_bwd(logits, idx, lse, B, N, K, g_chosen, g_prob, grad_logits, nullptr, nullptr, false, stream);
 }
 
 int mcq_loss_tail(const float *sums, const float *prob_sum, const float *count, int N, int K, float entropy_scale,
                   float *losses, float *g, float *g_prob, void *stream) {
-    if (!is_pow2(K) || K < 16 || K > 256 || N < 1 || N > 64) return MCQ_EUNSUPPORTED;     // (s_hl / s_hi of loss_tail_body: 64)
+    if (!loss_domain_ok(N, K, true)) return MCQ_EUNSUPPORTED;
     if (!sums || !prob_sum || !count || !losses || !g || !g_prob) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_loss_tail, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), sums, prob_sum, count, N, K,
                        entropy_scale, losses, g, g_prob);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 int mcq_recon_fwd(const float *x, const int64_t *idx, long B, const void *prepared, const float *mean, int N, int K,
@@ -1483,8 +1508,7 @@ int mcq_recon_fwd(const float *x, const int64_t *idx, long B, const void *prepar
     const Prepared P = prepared_view(prepared, N, K, D);
     hipLaunchKernelGGL(k_recon_fwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, idx, B,
                        P.C, mean, N, K, D, round_up16(D), err, num_part, den_part);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 
@@ -1541,8 +1565,7 @@ int mcq_weight_grad(const float *G, const float *x, long B, int M, int D, const 
     const long MN = (long)M * D;
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((MN / 4 + 255) / 256)), dim3(256), 0, st, part, partb, splits, MN, M,
                        scale_dev, gW, gb);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 int mcq_adam_step(float *p, const float *g, float *m, float *v, long n, double lr, double beta1, double beta2, double eps,
@@ -1554,34 +1577,30 @@ int mcq_adam_step(float *p, const float *g, float *m, float *v, long n, double l
     hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, n,
                        (float)(lr / bias_correction1), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
                        (float)weight_decay, (float)bias_correction2_sqrt);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 int mcq_loss_head_tail(const float *num_part, const float *den_part, long nparts, const float *chosen_n, int N, float batch,
                        float *head, const float *prob_sum, const float *count, int K, float entropy_scale, float *losses,
                        float *g, float *g_prob, void *stream) {
-    if (!is_pow2(K) || K < 16 || K > 256 || N < 1 || N > 64) return MCQ_EUNSUPPORTED;     // (as mcq_loss_tail)
+    if (!loss_domain_ok(N, K, true)) return MCQ_EUNSUPPORTED;     // (as mcq_loss_tail)
     if (nparts <= 0 || !num_part || !den_part || !chosen_n || !head || !prob_sum || !count || !losses || !g || !g_prob) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_loss_head_tail, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), num_part, den_part, nparts,
                        chosen_n, N, batch, head, prob_sum, count, K, entropy_scale, losses, g, g_prob);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 int mcq_loss_head(const float *num_part, const float *den_part, long nparts, const float *chosen_n, int N, float batch,
                   float *head, void *stream) {
     if (nparts <= 0 || N <= 0 || !num_part || !den_part || !chosen_n || !head) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_loss_head, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), num_part, den_part, nparts, chosen_n,
                        N, batch, head);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 int mcq_scales_exp(const float *centers_scale, const float *logits_scale, float speed, float *out2, void *stream) {
     if (!centers_scale || !logits_scale || !out2) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_scales, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), centers_scale, logits_scale, speed, out2);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 // decode_backward_u8 with the trainer's epilogue: rows scaled by sa[0]*sb[0]*sc (device floats), and per-wave partials
@@ -1603,30 +1622,11 @@ int mcq_decode_backward_u8_ex(const float *grad_out, const uint8_t *codes, long 
     return 0;
 }
 
-long mcq_loss_bwd_waves(long B, int N, int K) {
-    const int rpw = K < 64 ? 64 / K : 1;
-    const long rows = B * N;
-    return ((rows + (long)kLossWaves * rpw - 1) / ((long)kLossWaves * rpw)) * kLossWaves;
-}
+long mcq_loss_bwd_waves(long B, int N, int K) { return loss_bwd_blocks(B, N, K) * kLossWaves; }
 
 int mcq_loss_bwd_ex(const float *logits, const int64_t *idx, const float *lse, long B, int N, int K, const float *g_chosen,
                     const float *g_prob, float *grad_logits, const float *bias, float *dot_part, void *stream) {
-    if (!is_pow2(K) || K < 16 || K > 256 || N < 1) return MCQ_EUNSUPPORTED;
-    if (B <= 0) return MCQ_EINVAL;
-    if (!logits || !idx || !lse || !g_chosen || !g_prob || !grad_logits || !bias || !dot_part) return MCQ_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int rpw = K < 64 ? 64 / K : 1;
-    const long rows = B * N;
-    const dim3 grid((unsigned)((rows + (long)kLossWaves * rpw - 1) / ((long)kLossWaves * rpw))), block(64 * kLossWaves);
-#define MCQ_LOSS_CASE(KK)                                                                                             \
-    case KK: hipLaunchKernelGGL((k_loss_bwd<KK>), grid, block, 0, st, logits, idx, lse, B, N, g_chosen, g_prob, grad_logits, bias, dot_part); break;
-    switch (K) {
-        MCQ_LOSS_CASE(16) MCQ_LOSS_CASE(32) MCQ_LOSS_CASE(64) MCQ_LOSS_CASE(128) MCQ_LOSS_CASE(256)
-        default: return MCQ_EUNSUPPORTED;
-    }
-#undef MCQ_LOSS_CASE
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return launch_loss_bwd(logits, idx, lse, B, N, K, g_chosen, g_prob, grad_logits, bias, dot_part, true, stream);
 }
 
 int mcq_grad_tail(const float *part_c, long n_c, const float *sa, const float *sb, float sc, const float *part_l, long n_l,
@@ -1634,8 +1634,7 @@ int mcq_grad_tail(const float *part_c, long n_c, const float *sa, const float *s
     if (n_c < 0 || n_l < 0 || (n_c > 0 && !part_c) || (n_l > 0 && !part_l)) return MCQ_EINVAL;
     hipLaunchKernelGGL(k_grad_tail, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), part_c, n_c, sa, sb, sc, part_l, n_l,
                        speed, out_c, out_l);
-    MCQ_LAUNCH_CHECK();
-    return 0;
+    return counted_launch_rc();
 }
 
 // ---- search over stored codes: mcq_search_kernels.h (the launch arithmetic is above, ahead of the C linkage block)
@@ -1762,8 +1761,7 @@ int mcq_test_select(const float *scores, int cases, int per_lane, int cnt, float
         case -1004: hipLaunchKernelGGL((k_test_select<4, kAnyOrder>), dim3(cases), dim3(64), 0, st, scores, cnt, out_v, out_p); break;
         default: return MCQ_EINVAL;
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_rc();
 }
 
 #ifdef MCQ_STAMPS

@@ -67,6 +67,101 @@ def test_argument_validation_without_launch():
     assert L.mcq_profile_encode(None, 4, None, 1.0, 8, 256, 64, 1, None, 0, None, None, None, 0) == m.MCQ_EINVAL     # no output array
 
 
+def test_rejections_of_the_decode_logits_trainer_and_encode_entry_points():
+    """Return codes that precede any launch, as commit e388410's library gives them.  Null pointers wherever the check under
+    test allows; `p` is a host buffer standing in for a pointer that must be non-null to REACH that check (the call returns
+    before anything is enqueued)."""
+    m = _lib()
+    L = m.lib()
+    EINVAL, EUNSUP = m.MCQ_EINVAL, m.MCQ_EUNSUPPORTED
+    buf = ctypes.create_string_buffer(256)
+    p = ctypes.addressof(buf)
+    # mcq_decode(codes, code_bytes, codes_per_row, B, prepared, N, K, D, out, stream)
+    assert L.mcq_decode(None, 1, 2, 4, None, 64, 16, 64, None, None) == EINVAL            # rep = 32
+    assert L.mcq_decode(None, 1, 8, 4, None, 8, 256, 64, None, None) == EINVAL            # rep = 1, null pointers
+    assert L.mcq_decode(None, 2, 8, 0, None, 8, 256, 64, None, None) == EINVAL            # code_bytes 2 (before B == 0)
+    assert L.mcq_decode(None, 4, 8, 0, None, 8, 256, 64, None, None) == EINVAL
+    assert L.mcq_decode(None, 1, 8, -1, None, 8, 256, 64, None, None) == EINVAL
+    assert L.mcq_decode(None, 1, 8, 0, None, 8, 256, 64, None, None) == 0
+    assert L.mcq_decode(None, 8, 1, 0, None, 16, 256, 64, None, None) == 0                # rep = 16, int64 codes
+    assert L.mcq_decode(None, 1, 8, 4, None, 8, 8, 64, None, None) == EUNSUP              # K below the domain, valid D
+    assert L.mcq_decode(None, 1, 8, 4, None, 8, 2048, 64, None, None) == EUNSUP
+    assert L.mcq_decode(None, 1, 8, 4, None, 8, 48, 64, None, None) == EINVAL             # K inside the range, no power of two
+    assert L.mcq_decode(None, 1, 8, 4, None, 8, 256, 20000, None, None) == EINVAL         # (its domain_err never sees D)
+    assert L.mcq_encode(None, 4, None, 1.0, 8, 256, 20000, 1, None, None, None, 0, None) == EUNSUP
+    # mcq_logits(x, B, prepared, lscale, N, K, D, out, ws, ws_bytes, stream): UNSUPPORTED for anything outside the domain
+    assert L.mcq_logits(None, 4, None, 1.0, 3, 256, 64, None, None, 0, None) == EUNSUP
+    assert L.mcq_logits(None, 4, None, 1.0, 8, 8, 64, None, None, 0, None) == EUNSUP
+    assert L.mcq_logits(None, 0, None, 1.0, 8, 256, 64, None, None, 0, None) == 0
+    assert L.mcq_logits(None, -1, None, 1.0, 8, 256, 64, None, None, 0, None) == EINVAL
+    assert L.mcq_logits(None, 4, None, 1.0, 8, 256, 64, None, None, 0, None) == EINVAL
+    # mcq_logits_argmax(x, B, prepared, lscale, N, K, D, logits_out, argmax_out, ws, ws_bytes, stream, flags)
+    assert L.mcq_logits_argmax(None, 4, None, 1.0, 4, 512, 64, None, None, None, 0, None, 0) == EUNSUP
+    assert L.mcq_logits_argmax(None, 4, None, 1.0, 3, 256, 64, None, None, None, 0, None, 0) == EUNSUP
+    assert L.mcq_logits_argmax(None, -1, None, 1.0, 4, 256, 64, None, None, None, 0, None, 0) == EINVAL
+    assert L.mcq_logits_argmax(None, 0, None, 1.0, 4, 256, 64, None, None, None, 0, None, 0) == 0
+    assert L.mcq_logits_argmax(None, 4, None, 1.0, 4, 256, 64, None, None, None, 0, None, 0) == EINVAL
+    # the loss kernels: K in 16 .. 256, B > 0 (an empty batch is INVALID, not a no-op)
+    for K, want in ((8, EUNSUP), (512, EUNSUP), (48, EUNSUP), (256, EINVAL)):
+        Bs = (0, -1) if want == EINVAL else (4, 0)
+        for Bq in Bs:
+            assert L.mcq_loss_fwd(None, None, Bq, 4, K, None, None, None, None, None, 0, None) == want, (K, Bq)
+            assert L.mcq_loss_bwd(None, None, None, Bq, 4, K, None, None, None, None) == want, (K, Bq)
+            assert L.mcq_loss_bwd_ex(None, None, None, Bq, 4, K, None, None, None, None, None, None) == want, (K, Bq)
+            assert L.mcq_recon_fwd(None, None, Bq, None, None, 4, K, 64, None, None, None, None) == want, (K, Bq)
+    assert L.mcq_loss_fwd(None, None, 4, 0, 64, None, None, None, None, None, 0, None) == EUNSUP        # N < 1
+    assert L.mcq_loss_bwd(None, None, None, 4, 0, 64, None, None, None, None) == EUNSUP
+    assert L.mcq_loss_bwd_ex(None, None, None, 4, 0, 64, None, None, None, None, None, None) == EUNSUP
+    assert L.mcq_loss_fwd(None, None, 4, 128, 64, None, None, None, None, None, 0, None) == EINVAL      # (no cap on N here)
+    assert L.mcq_loss_tail(None, None, None, 0, 64, 1.0, None, None, None, None) == EUNSUP
+    assert L.mcq_loss_head_tail(None, None, 1, None, 4, 1.0, None, None, None, 8, 1.0, None, None, None, None) == EUNSUP
+    assert L.mcq_loss_bwd(None, None, None, 4, 4, 64, None, None, None, None) == EINVAL                 # null pointers
+    assert L.mcq_loss_bwd_ex(p, p, p, 4, 4, 64, p, p, p, None, p, None) == EINVAL                       # null bias
+    assert L.mcq_loss_bwd_ex(p, p, p, 4, 4, 64, p, p, p, p, None, None) == EINVAL                       # null dot_part
+    assert L.mcq_recon_fwd(None, None, 4, None, None, 3, 64, 64, None, None, None, None) == EUNSUP      # domain_ok, not the K test
+    assert L.mcq_recon_fwd(None, None, 4, None, None, 4, 64, 64, None, None, None, None) == EINVAL
+    # mcq_weight_grad(G, x, B, M, D, scale_dev, gW, gb, ws, ws_bytes, stream)
+    assert L.mcq_weight_grad(p, p, 4, 24, 64, p, p, p, p, 1 << 30, None) == EINVAL                      # M % 16 != 0
+    assert L.mcq_weight_grad(None, None, 4, 32, 64, None, None, None, None, 0, None) == EINVAL
+    assert L.mcq_weight_grad(p, p, 4, 32, 64, p, p, p, p, 0, None) == m.MCQ_EWORKSPACE
+    # mcq_adam_step(p, g, m, v, n, ...)
+    assert L.mcq_adam_step(None, None, None, None, -1, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, 1.0, None) == EINVAL
+    assert L.mcq_adam_step(None, None, None, None, 0, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, 1.0, None) == 0
+    assert L.mcq_adam_step(None, None, None, None, 4, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, 1.0, None) == EINVAL
+    # mcq_scatter_rows(grad, stride_b, stride_n, idx, idx_stride, B, N, K, D, out, stream)
+    assert L.mcq_scatter_rows(None, 64, 0, None, 7, 0, 8, 256, 64, p, None) == EINVAL                   # idx_stride < N
+    # mcq_decode_backward_u8_ex(grad_out, codes, B, N, K, D, gC, sa, sb, sc, dotw, dot_part, stream)
+    assert L.mcq_decode_backward_u8_ex(None, None, 0, 8, 256, 64, p, None, None, 1.0, p, None, None) == EINVAL
+    assert L.mcq_decode_backward_u8_ex(None, None, 0, 8, 256, 64, p, None, None, 1.0, None, p, None) == EINVAL
+    assert L.mcq_decode_backward_u8_ex(None, None, 4, 8, 256, 64, p, None, None, 1.0, None, None, None) == EINVAL
+    # mcq_encode(x, B, prepared, lscale, N, K, D, iters, out_u8, out_i64, ws, ws_bytes, stream)
+    assert L.mcq_encode(None, 4, None, 1.0, 8, 256, 64, 1, p, p, None, 0, None) == EINVAL               # both outputs
+    assert L.mcq_encode(None, 4, None, 1.0, 8, 256, 64, 61, p, None, None, 0, None) == EINVAL
+    assert L.mcq_encode(None, 4, None, 1.0, 8, 256, 64, -1, p, None, None, 0, None) == EINVAL
+    # an empty batch is a no-op once exactly one output is named; with NO output the output check comes first
+    assert L.mcq_encode(None, 0, None, 1.0, 8, 256, 64, 1, p, None, None, 0, None) == 0
+    assert L.mcq_encode(None, 0, None, 1.0, 8, 256, 64, 1, None, None, None, 0, None) == EINVAL
+    assert L.mcq_last_encode_launches() == 0
+    assert L.mcq_encode(None, 4, None, 1.0, 4, 512, 64, 1, p, None, None, 0, None) == EINVAL            # two-byte entries, byte output
+    assert L.mcq_encode(None, 0, None, 1.0, 4, 512, 64, 1, None, p, None, 0, None) == 0
+    assert L.mcq_encode(None, 4, None, 1.0, 8, 256, 64, 1, p, None, None, 0, None) == EINVAL            # null x / prepared / workspace
+    assert L.mcq_encode(p, 4, p, 1.0, 8, 256, 64, 1, p, None, p, 0, None) == m.MCQ_EWORKSPACE
+    assert L.mcq_encode_ex(None, 4, None, 1.0, 8, 256, 64, 61, p, None, None, 0, None, 0) == EINVAL
+    # mcq_refine_indexes(x, B, prepared, N, K, D, iters, idx_in, idx_out, ws, ws_bytes, stream)
+    assert L.mcq_refine_indexes(None, 4, None, 8, 256, 64, 1, None, p, None, 0, None) == EINVAL
+    assert L.mcq_refine_indexes(None, 0, None, 8, 256, 64, 1, None, p, None, 0, None) == 0
+    assert L.mcq_refine_indexes(None, 4, None, 8, 8, 64, 1, None, None, None, 0, None) == EINVAL        # (the pointers come first)
+    # mcq_logits_refine_codes(x, B, prepared, lscale, N, K, D, iters, logits_out, idx_out, codes_out, ws, ws_bytes, stream, flags)
+    assert L.mcq_logits_refine_codes(None, 4, None, 1.0, 4, 256, 64, 1, None, p, None, None, 0, None, 0) == EINVAL
+    assert L.mcq_logits_refine_codes(None, 0, None, 1.0, 4, 256, 64, 1, None, p, None, None, 0, None, 0) == 0
+    assert L.mcq_logits_refine_codes(None, 4, None, 1.0, 4, 8, 64, 1, p, p, None, None, 0, None, 0) == EUNSUP
+    # mcq_prepare*: the domain first, then the pointers
+    assert L.mcq_prepare(None, 1.0, None, None, 8, 8, 64, None, None) == EUNSUP
+    assert L.mcq_prepare(p, 1.0, p, None, 8, 256, 64, p, None) == EINVAL                                # weight without bias
+    assert L.mcq_prepare_dev(p, None, None, None, 8, 256, 64, p, None) == EINVAL
+    assert L.mcq_prepare_params(p, None, p, 10.0, None, None, 8, 256, 64, p, None, None) == EINVAL
+
+
 def test_module_api_surface_and_state_dict():
     import torch
     from quantization_amd import Quantizer, QuantizerTrainer
