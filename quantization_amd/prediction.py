@@ -11,6 +11,12 @@ The module predicts codebook n of a frame from a predictor vector and the entrie
 
 and a hand-derived backward (mcq_loss_bwd, mcq_jcl_prefix_bwd, mcq_scatter_rows + library GEMMs).
 `checkpoint=True` (the reference's default) keeps only the inputs and recomputes A and Z in backward.
+
+Padding is per element, as in the reference (:44-50, F.cross_entropy(ignore_index=...)): a negative target contributes no
+loss for its own codebook, but as an INPUT to the later codebooks of the same frame it is clamped to entry 0.  So a frame
+that is negative in codebook j < N-1 and valid later gathers embedding row j*K in the forward, and that row receives the
+gradient of the frame's later codebooks in the backward: the scatter runs on the clamped indexes, exactly the rows the
+forward gathered.  (mcq_scatter_rows itself matches a negative index to no row; the clamp is this module's.)
 There is no CPU path: like the rest of the package this fails loudly off the HIP device.
 """
 import torch
@@ -121,7 +127,10 @@ class _JointCodebookLossFn(torch.autograd.Function):
             st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(L.mcq_jcl_prefix_bwd(A.data_ptr(), gA.contiguous().data_ptr(), B, N, H, ctx.scale, g_hp.data_ptr(),
                                             gE.data_ptr(), st), "mcq_jcl_prefix_bwd")
-            _lib.check(L.mcq_scatter_rows(gE.data_ptr(), H, B * H, idx2d.data_ptr(), N, B, N - 1, K, H, g_emb.data_ptr(), st),
+            # the rows the forward gathered: a negative index gathered row n*K + 0 (mcq_scatter_rows itself matches a
+            # negative index to no row); the last column is not read (N - 1 scattered codebooks, idx_stride N)
+            idx_rows = idx2d.clamp(min=0)
+            _lib.check(L.mcq_scatter_rows(gE.data_ptr(), H, B * H, idx_rows.data_ptr(), N, B, N - 1, K, H, g_emb.data_ptr(), st),
                        "mcq_scatter_rows")
         g_w1 = torch.mm(g_hp.t(), pred2d)
         g_b1 = g_hp.sum(dim=0) if ctx.has_b1 else None

@@ -22,7 +22,7 @@ def _module(fx, checkpoint):
 
 
 def test_surface_and_no_cpu_fallback():
-    assert len(FIXTURES) == 3
+    assert len(FIXTURES) == 4
     from quantization_amd import _lib
     fx = np.load(FIXTURES[0])
     m = _module(fx, True)
@@ -107,8 +107,9 @@ def test_ragged_sizes_against_the_torch_op_sequence(B, P, N, H, K):
         assert float((pa[k] - pb[k]).abs().max()) <= 1e-4 * float(pb[k].abs().max() + 1e-9), k
 
 
-def _torch_rows(m, pred, idx):
-    """the reference's op sequence (prediction.py:38-82) with reduction='none', in torch"""
+def _torch_rows(m, pred, idx, keep_hp=None):
+    """the reference's op sequence (prediction.py:38-82) with reduction='none', in torch; hp = linear1(predictor) is
+    appended to the list keep_hp, with its gradient retained, when one is given"""
     import torch.nn.functional as F
     N, K, H = m.num_codebooks, m.codebook_size, m.hidden_channels
     p2 = pred.reshape(-1, pred.shape[-1])
@@ -116,10 +117,129 @@ def _torch_rows(m, pred, idx):
     first = i2[:, :-1].clamp(min=0) + torch.arange(0, (N - 1) * K, K, device=i2.device)
     emb = F.embedding(first, m.codebook_embedding.weight) * (0.5 * ((H / N) ** 0.5))
     hp = F.linear(p2, m.linear1.weight, m.linear1.bias)
+    if keep_hp is not None:
+        hp.retain_grad()
+        keep_hp.append(hp)
     a = torch.relu(torch.cumsum(torch.cat((hp.unsqueeze(1), emb), dim=1), dim=1))
     z = torch.matmul(a.transpose(0, 1), m.linear2_weight.transpose(1, 2)).transpose(0, 1)
     z = z + torch.matmul(p2, m.linear2b_weight.transpose(1, 2)).transpose(0, 1) + m.linear2_bias
     return F.cross_entropy(z.reshape(-1, K), i2.reshape(-1), ignore_index=-100, reduction="none")
+
+
+# ---------------------------------------------------------------------------------------------- padding, per element
+PAD_SIZES = [(12, 20, 4, 24, 16), (130, 33, 5, 96, 128)]            # (B, P, N, H, K)
+PAD_PATTERNS = ["single", "last_column", "whole_frames", "column0"]
+
+
+def _padded_indexes(pattern, B, N, K, gen):
+    """targets in [1, K): entry 0 of a codebook is then gathered, and its embedding row trained, only through the clamp
+    of a negative target (prediction.py:44-50)"""
+    idx = torch.randint(1, K, (B, N), generator=gen)
+    if pattern == "single":            # (a) one negative per chosen frame, in a codebook j < N-1 whose later codebooks are valid
+        for i, b in enumerate(range(1, B, 3)):
+            idx[b, i % (N - 1)] = -100
+    elif pattern == "last_column":     # (b) the last codebook is no input to any other
+        idx[::3, N - 1] = -100
+    elif pattern == "whole_frames":    # (c) what the fixtures of the first three files hold
+        idx[::4] = -100
+    elif pattern == "column0":         # (d) embedding row 0 receives a contribution from every frame
+        idx[:, 0] = -100
+    elif pattern == "all":             # (e)
+        idx[:] = -100
+    else:
+        raise ValueError(pattern)
+    return idx
+
+
+_PAD_REFERENCES = {}
+
+
+def _padded_reference(size, pattern, reduction):
+    """inputs, fp32 state and the float64 CPU result of the reference's op sequence (_torch_rows); computed once per
+    (size, pattern, reduction), shared by both checkpoint settings and never modified"""
+    key = (size, pattern, reduction)
+    if key not in _PAD_REFERENCES:
+        from quantization_amd import JointCodebookLoss
+        B, P, N, H, K = size
+        gen = torch.Generator().manual_seed(B + 10 * PAD_SIZES.index(size) + 100 * (PAD_PATTERNS + ["all"]).index(pattern))
+        torch.manual_seed(7 + B)
+        m = JointCodebookLoss(P, N, H, K)
+        with torch.no_grad():
+            m.linear2_bias.normal_(std=0.1, generator=gen)
+        state = {k: v.clone() for k, v in m.state_dict().items()}
+        pred = torch.randn(B, P, generator=gen)
+        idx = _padded_indexes(pattern, B, N, K, gen)
+        w = torch.rand(B * N, generator=gen) + 0.5              # upstream weights of the rows of reduction='none'
+        m64 = m.double()
+        p64 = pred.double().requires_grad_(True)
+        rows = _torch_rows(m64, p64, idx)
+        valid = int((idx >= 0).sum())
+        out = rows if reduction == "none" else (rows.sum() if reduction == "sum" else rows.sum() / valid)
+        (rows * w.double()).sum().backward() if reduction == "none" else out.backward()
+        grads = {"grad_predictor": p64.grad.clone()}
+        grads.update({"grad." + k: p.grad.clone() for k, p in m64.named_parameters()})
+        _PAD_REFERENCES[key] = (state, pred, idx, w, out.detach().clone(), grads)
+    return _PAD_REFERENCES[key]
+
+
+def _padded_device(size, state, pred, idx, w, reduction, checkpoint):
+    from quantization_amd import JointCodebookLoss
+    B, P, N, H, K = size
+    m = JointCodebookLoss(P, N, H, K, reduction=reduction, checkpoint=checkpoint)
+    m.load_state_dict(state)
+    m = m.cuda()
+    p = pred.cuda().requires_grad_(True)
+    out = m(p, idx.cuda())
+    ((out * w.cuda()).sum() if reduction == "none" else out).backward()
+    grads = {"grad_predictor": p.grad}
+    grads.update({"grad." + k: q.grad for k, q in m.named_parameters()})
+    return out.detach().cpu().double(), {k: g.cpu().double() for k, g in grads.items()}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("checkpoint", [True, False])
+@pytest.mark.parametrize("reduction", ["sum", "mean", "none"])
+@pytest.mark.parametrize("pattern", PAD_PATTERNS)
+@pytest.mark.parametrize("size", PAD_SIZES, ids=lambda v: "x".join(map(str, v)))
+def test_padding_is_per_element_as_in_the_reference(size, pattern, reduction, checkpoint):
+    """JointCodebookLoss on the device against the reference's op sequence in float64 on the CPU, with negative targets
+    (a) alone in a codebook before the last, (b) in the last codebook only, (c) in whole frames, (d) in all of codebook
+    0.  Loss (each row of reduction='none') and every gradient within 1e-4 of the reference tensor's largest entry; and
+    every embedding row n*K (reached only through a clamped negative: no target is 0) that the reference trains is trained
+    on the device, to the same tolerance."""
+    B, P, N, H, K = size
+    state, pred, idx, w, ref_out, ref = _padded_reference(size, pattern, reduction)
+    out, got = _padded_device(size, state, pred, idx, w, reduction, checkpoint)
+    assert out.shape == ref_out.shape
+    err, scale = float((out - ref_out).abs().max()), max(float(ref_out.abs().max()), 1e-6)
+    print(f"loss: err {err:.3e} of {scale:.3e}")
+    assert err <= 1e-4 * scale, ("loss", err, scale)
+    for k, g in got.items():
+        scale = max(float(ref[k].abs().max()), 1e-6)
+        err = float((g - ref[k]).abs().max())
+        print(f"{k}: err {err:.3e} of {scale:.3e}")
+        assert torch.isfinite(g).all() and err <= 1e-4 * scale, (k, err, scale)
+    ge, re_ = got["grad.codebook_embedding.weight"], ref["grad.codebook_embedding.weight"]
+    scale = max(float(re_.abs().max()), 1e-6)
+    trained = [n for n in range(N - 1) if float(re_[n * K].abs().max()) > 0]
+    assert bool(trained) == (pattern in ("single", "column0")), (pattern, trained)
+    for n in trained:
+        err = float((ge[n * K] - re_[n * K]).abs().max())
+        print(f"embedding row {n}*K: norm {float(ge[n * K].norm()):.4f}, reference {float(re_[n * K].norm()):.4f}, err {err:.3e}")
+        assert float(ge[n * K].abs().max()) > 0 and err <= 1e-4 * scale, (n, err, scale)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("checkpoint", [True, False])
+@pytest.mark.parametrize("size", PAD_SIZES, ids=lambda v: "x".join(map(str, v)))
+def test_every_target_negative_gives_zero_loss_and_zero_gradients(size, checkpoint):
+    """(e) reduction='sum' over no valid target: the loss is 0 and every gradient exactly 0, nothing is NaN"""
+    state, pred, idx, w, ref_out, ref = _padded_reference(size, "all", "sum")
+    assert float(ref_out) == 0.0 and all(float(g.abs().max()) == 0.0 for g in ref.values())
+    out, got = _padded_device(size, state, pred, idx, w, "sum", checkpoint)
+    assert float(out) == 0.0
+    for k, g in got.items():
+        assert torch.isfinite(g).all() and float(g.abs().max()) == 0.0, k
 
 
 @pytest.mark.gpu

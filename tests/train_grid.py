@@ -129,6 +129,27 @@ def db_cw_of(D, K):
     return 4 if D >= c["db_d4"] else (2 if D >= c["db_d2"] else 1)
 
 
+def db_alignment():
+    """(stride mask, pointer mask) of db_cw: rows are read as float4 only when D and both strides are multiples of
+    stride mask + 1 floats and grad, out and dotw start on a multiple of pointer mask + 1 bytes"""
+    body = _body(_src("mcq_api.hip"), "int db_cw(")
+    d, sb, sn, pg, po, pw = _int(r"\(\(D & (\d+)\) == 0\) && \(\(gsb & (\d+)\) == 0\) && \(\(gsn & (\d+)\) == 0\) && "
+                                 r"\(\(reinterpret_cast<uintptr_t>\(g\) & (\d+)\) == 0\) &&\s*"
+                                 r"\(\(reinterpret_cast<uintptr_t>\(out\) & (\d+)\) == 0\) && "
+                                 r"\(\(reinterpret_cast<uintptr_t>\(dotw\) & (\d+)\) == 0\);\s*return al \? db_cw_of\(D, K\) : 1;",
+                                 body, "db_cw's alignment rule")
+    assert d == sb == sn and pg == po == pw
+    return d, pg
+
+
+def db_cw(D, K, gsb, gsn, g_addr=0, out_addr=0, dotw_addr=0):
+    """floats per lane of a launch: db_cw_of when every row involved is 16-byte aligned (strides in floats, addresses in
+    bytes), else 1"""
+    sm, pm = db_alignment()
+    al = not (D & sm or gsb & sm or gsn & sm or g_addr & pm or out_addr & pm or dotw_addr & pm)
+    return db_cw_of(D, K) if al else 1
+
+
 def db_chunks(D, cw):
     return (D + 64 * cw - 1) // (64 * cw)
 
