@@ -382,6 +382,39 @@ int mcq_search_range_fill(const float *tables, long Q, const uint8_t *codes, con
                           const float *thr, const int64_t *lims, float *out_score, int64_t *out_index, long capacity,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- search under a filter: a bitmask over the store -------------------------------
+ * Deleted rows, rows of another tenant, rows that fail a predicate: the scan and the two sweeps take a mask and look at the
+ * stored vectors whose bit is set, without a second copy of the store.  The contract continues (the tests restate rules 10
+ * and 11 in numpy and compare bit for bit):
+ *  10. a mask is uint64_t mask[(B + 63) / 64], 8-byte aligned (MCQ_EINVAL otherwise), in device memory.  Stored vector b is a
+ *      CANDIDATE iff bit b & 63 of word b >> 6 is set; read as bytes that is numpy.packbits(keep, bitorder="little").  Bits at
+ *      positions >= B of the last word are ignored, whatever they hold.  One mask serves all queries of a call.
+ *  11. rules 3, 3', 4, 7 and 8 hold as they stand over the set of candidates.  The score of a candidate is the same bits as
+ *      without a mask; the order is (score, b) ascending with b the ORIGINAL position, and original positions are reported;
+ *      top-k with fewer than k candidates (none included) has the tail (+inf, -1); the range search lists b iff its bit is
+ *      set and score[q][b] <= thr[q].  So the output equals, bit for bit, that of the unmasked call over the compacted store
+ *      codes[keep], w[keep] with its positions mapped through nonzero(keep) (an increasing map: the order carries over).
+ *  12. mask == NULL is the call without a mask.  A non-finite w or score behind a cleared bit changes no result, and a cleared
+ *      bit never makes a load go out of bounds.
+ * mcq_search_pack_mask: flags uint8 [B], one byte per stored vector, non-zero = keep -> mask_out, (B + 63) / 64 words, the
+ *   bits past B zero.  B == 0 returns 0 and writes nothing; B > 2^31 - 1 is MCQ_EUNSUPPORTED.  A store may as well keep the
+ *   words itself and flip bits (a delete clears one).
+ * mcq_search_scan_masked, mcq_search_range_count_masked, mcq_search_range_fill_masked: the unmasked calls' arguments with
+ *   `mask` after `metric`; their limits, status codes and the order of their checks (nothing touches the device before every
+ *   argument passed); their workspaces, sized by the same two queries.  A call with Q == 0 or B == 0 looks at no input, the
+ *   mask included.  fill takes the mask count took, like every other argument.  A step of 64 candidates whose mask word is
+ *   zero costs no load of codes: a selective mask makes the call cheaper.                                                   */
+int mcq_search_pack_mask(const uint8_t *flags, long B, uint64_t *mask_out, void *stream);
+int mcq_search_scan_masked(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
+                           int metric, const uint64_t *mask, float *out_score, int64_t *out_index, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int mcq_search_range_count_masked(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                  int metric, const uint64_t *mask, const float *thr, int64_t *lims, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+int mcq_search_range_fill_masked(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                 int metric, const uint64_t *mask, const float *thr, const int64_t *lims, float *out_score,
+                                 int64_t *out_index, long capacity, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- test / profiling hooks -------------------------------------------------
  * Logits of Quantizer._logits (:277-279) for a batch, fp32 [B][N*K]; used by the
  * parity tests to localise a divergence.                                       */

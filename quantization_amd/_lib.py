@@ -24,6 +24,7 @@ SYMBOLS = (
     "mcq_search_tables", "mcq_code_norms", "mcq_search_workspace_bytes", "mcq_search_scan",
     "mcq_search_scan_metric", "mcq_code_rnorms", "mcq_rnorms_from_norms",
     "mcq_search_range_workspace_bytes", "mcq_search_range_count", "mcq_search_range_fill",
+    "mcq_search_pack_mask", "mcq_search_scan_masked", "mcq_search_range_count_masked", "mcq_search_range_fill_masked",
 )
 
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
@@ -150,6 +151,16 @@ def lib():
         L.mcq_search_range_count.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, sz, vp]
         L.mcq_search_range_fill.restype = i32
         L.mcq_search_range_fill.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, i64, vp, sz, vp]
+    # (and the masked calls: an older build serves unmasked calls as before, and calling a masked one raises)
+    if not (_ALT and not hasattr(L, "mcq_search_pack_mask")):
+        L.mcq_search_pack_mask.restype = i32
+        L.mcq_search_pack_mask.argtypes = [vp, i64, vp, vp]
+        L.mcq_search_scan_masked.restype = i32
+        L.mcq_search_scan_masked.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+        L.mcq_search_range_count_masked.restype = i32
+        L.mcq_search_range_count_masked.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+        L.mcq_search_range_fill_masked.restype = i32
+        L.mcq_search_range_fill_masked.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, sz, vp]
     L.mcq_last_encode_launches.restype = i32
     L.mcq_profile_encode.restype = i32
     L.mcq_profile_encode.argtypes = [vp, i64, vp, f32, i32, i32, i32, i32, vp, sz, vp, ctypes.POINTER(f32), ctypes.POINTER(i32), i32]

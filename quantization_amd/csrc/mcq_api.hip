@@ -870,9 +870,9 @@ int search_domain(int N, int K, int D) {
 // What every scan and sweep entry point rejects, in this order (tests/test_search_host.py, test_search_metric_host.py and
 // test_search_range_host.py pin it); nothing touches the device.  k: 1 where the entry has none.  outs_ok: the outputs this
 // call writes are there (the caller knows which of them an empty call still writes).  A call with Q == 0 or B == 0 reads no
-// input, so none is looked at.
+// input, so none is looked at.  mask: NULL where the call has none (rule 12); one that is there is read as 8-byte words.
 int search_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
-                 bool outs_ok, const void *workspace) {
+                 const uint64_t *mask, bool outs_ok, const void *workspace) {
     if (const int rc = search_domain(N, K, 1)) return rc;
     if (k > 64) return MCQ_EUNSUPPORTED;
     if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
@@ -884,6 +884,7 @@ int search_check(const float *tables, long Q, const uint8_t *codes, const float 
     if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;                  // (the inner product never reads w)
     const int need = N >= 16 ? 16 : N;                                    // a candidate's codes are loaded as one vector
     if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
+    if (reinterpret_cast<uintptr_t>(mask) % 8 != 0) return MCQ_EINVAL;
     return 0;
 }
 
@@ -941,23 +942,28 @@ ScanPlan scan_plan(long Q, long B, int N, int K, int k) {
     return p;
 }
 
-template <int QT, int NN, int M>
+template <int QT, int NN, int M, bool MASKED>
 int launch_scan(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *norms, long B,
-                int K, int k, float *ws_s, int *ws_i) {
+                int K, int k, float *ws_s, int *ws_i, const uint64_t *mask) {
     static bool allowed[64] = {};
-    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_scan<QT, NN, M>), kScanTableLds))
+    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_scan<QT, NN, M, MASKED>), kScanTableLds))
         return rc;
-    hipLaunchKernelGGL((k_search_scan<QT, NN, M>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kScanWaves), p.lds, st,
-                       tables, Q, codes, norms, B, K, k, p.slices, p.per_slice, ws_s, ws_i);
+    hipLaunchKernelGGL((k_search_scan<QT, NN, M, MASKED>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kScanWaves),
+                       p.lds, st, tables, Q, codes, norms, B, K, k, p.slices, p.per_slice, ws_s, ws_i,
+                       reinterpret_cast<const u64 *>(mask));
     return launch_rc();
 }
 
+// the mask is a template parameter of the scan and of the sweeps as well: the instantiations without one are the code they
+// were before masks existed
 template <int QT, int M>
 int launch_scan_n(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *norms,
-                  long B, int N, int K, int k, float *ws_s, int *ws_i) {
+                  long B, int N, int K, int k, float *ws_s, int *ws_i, const uint64_t *mask) {
     switch (N) {
-#define MCQ_SCAN_CASE(NN) \
-    case NN: return launch_scan<QT, NN, M>(p, st, tables, Q, codes, norms, B, K, k, ws_s, ws_i);
+#define MCQ_SCAN_CASE(NN)                                                                                          \
+    case NN:                                                                                                       \
+        return mask ? launch_scan<QT, NN, M, true>(p, st, tables, Q, codes, norms, B, K, k, ws_s, ws_i, mask)      \
+                    : launch_scan<QT, NN, M, false>(p, st, tables, Q, codes, norms, B, K, k, ws_s, ws_i, nullptr);
         MCQ_SCAN_CASE(1) MCQ_SCAN_CASE(2) MCQ_SCAN_CASE(4) MCQ_SCAN_CASE(8) MCQ_SCAN_CASE(16) MCQ_SCAN_CASE(32) MCQ_SCAN_CASE(64)
 #undef MCQ_SCAN_CASE
     }
@@ -969,13 +975,13 @@ int launch_scan_n(const ScanPlan &p, hipStream_t st, const float *tables, int Q,
 static_assert(kMetricL2 == MCQ_SEARCH_L2 && kMetricIP == MCQ_SEARCH_IP && kMetricCos == MCQ_SEARCH_COS, "include/mcq.h");
 template <int M>
 int launch_scan_qt(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
-                   int N, int K, int k, float *ws_s, int *ws_i) {
+                   int N, int K, int k, float *ws_s, int *ws_i, const uint64_t *mask) {
     switch (p.qt) {
-        case 1: return launch_scan_n<1, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
-        case 2: return launch_scan_n<2, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
-        case 4: return launch_scan_n<4, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
-        case 8: return launch_scan_n<8, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
-        case 16: return launch_scan_n<16, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i);
+        case 1: return launch_scan_n<1, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
+        case 2: return launch_scan_n<2, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
+        case 4: return launch_scan_n<4, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
+        case 8: return launch_scan_n<8, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
+        case 16: return launch_scan_n<16, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
     }
     return MCQ_EUNSUPPORTED;
 }
@@ -1011,27 +1017,28 @@ struct RangeArgs {
     float *out_s;
     int64_t *out_i;
     long capacity;
+    const uint64_t *mask;                                                 // NULL: none (rule 12)
 };
 
-template <int QT, int CH, bool FILL>
+template <int QT, int CH, bool FILL, bool MASKED>
 int launch_range(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
     static bool allowed[64] = {};
-    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_sweep<QT, CH, FILL>),
+    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_sweep<QT, CH, FILL, MASKED>),
                                          kScanTableLds + kRangeWaves * kScanQTMax * 8))
         return rc;
-    hipLaunchKernelGGL((k_range_sweep<QT, CH, FILL>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kRangeWaves), p.lds,
-                       st, a.tables, a.Q, a.codes, a.w, a.B, a.N, a.K, a.metric, p.slices, p.per_slice, a.thr, a.ws, a.lims,
-                       a.out_s, a.out_i, a.capacity);
+    hipLaunchKernelGGL((k_range_sweep<QT, CH, FILL, MASKED>), dim3((unsigned)p.qtiles * (unsigned)p.slices),
+                       dim3(64 * kRangeWaves), p.lds, st, a.tables, a.Q, a.codes, a.w, a.B, a.N, a.K, a.metric, p.slices,
+                       p.per_slice, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity, reinterpret_cast<const u64 *>(a.mask));
     return launch_rc();
 }
 
 template <int QT, bool FILL>
 int launch_range_ch(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
     switch (a.N < 8 ? a.N : 8) {                                          // a candidate's digits arrive in chunks of CH
-        case 1: return launch_range<QT, 1, FILL>(p, st, a);
-        case 2: return launch_range<QT, 2, FILL>(p, st, a);
-        case 4: return launch_range<QT, 4, FILL>(p, st, a);
-        case 8: return launch_range<QT, 8, FILL>(p, st, a);
+        case 1: return a.mask ? launch_range<QT, 1, FILL, true>(p, st, a) : launch_range<QT, 1, FILL, false>(p, st, a);
+        case 2: return a.mask ? launch_range<QT, 2, FILL, true>(p, st, a) : launch_range<QT, 2, FILL, false>(p, st, a);
+        case 4: return a.mask ? launch_range<QT, 4, FILL, true>(p, st, a) : launch_range<QT, 4, FILL, false>(p, st, a);
+        case 8: return a.mask ? launch_range<QT, 8, FILL, true>(p, st, a) : launch_range<QT, 8, FILL, false>(p, st, a);
     }
     return MCQ_EUNSUPPORTED;
 }
@@ -1050,8 +1057,8 @@ int launch_range_qt(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
 
 // rule 9: what both range entry points reject (lims is written even by an empty call); nothing touches the device
 int range_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
-                const float *thr, const int64_t *lims, const void *workspace, size_t workspace_bytes) {
-    if (const int rc = search_check(tables, Q, codes, w, B, N, K, 1, metric, lims != nullptr, workspace)) return rc;
+                const uint64_t *mask, const float *thr, const int64_t *lims, const void *workspace, size_t workspace_bytes) {
+    if (const int rc = search_check(tables, Q, codes, w, B, N, K, 1, metric, mask, lims != nullptr, workspace)) return rc;
     if (Q == 0 || B == 0) return 0;
     if (!thr) return MCQ_EINVAL;                     // (after w and the alignment now: all three are MCQ_EINVAL, no code moved)
     if (workspace_bytes < range_plan(Q, B, N, K).ws_bytes) return MCQ_EWORKSPACE;
@@ -1684,7 +1691,15 @@ int mcq_search_scan(const float *tables, long Q, const uint8_t *codes, const flo
 int mcq_search_scan_metric(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
                            int metric, float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes,
                            void *stream) {
-    if (const int rc = search_check(tables, Q, codes, w, B, N, K, k, metric, Q == 0 || (out_score && out_index), workspace))
+    return mcq_search_scan_masked(tables, Q, codes, w, B, N, K, k, metric, nullptr, out_score, out_index, workspace,
+                                  workspace_bytes, stream);
+}
+
+// rules 10-12: the scan over the stored vectors whose bit is set (mask == NULL: over all of them)
+int mcq_search_scan_masked(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
+                           int metric, const uint64_t *mask, float *out_score, int64_t *out_index, void *workspace,
+                           size_t workspace_bytes, void *stream) {
+    if (const int rc = search_check(tables, Q, codes, w, B, N, K, k, metric, mask, Q == 0 || (out_score && out_index), workspace))
         return rc;
     if (Q == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1698,9 +1713,9 @@ int mcq_search_scan_metric(const float *tables, long Q, const uint8_t *codes, co
         ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
         int rc = MCQ_EUNSUPPORTED;
         switch (metric) {
-            case MCQ_SEARCH_L2: rc = launch_scan_qt<kMetricL2>(p, st, tables, (int)Q, codes, w, B, N, K, k, ws_s, ws_i); break;
-            case MCQ_SEARCH_IP: rc = launch_scan_qt<kMetricIP>(p, st, tables, (int)Q, codes, nullptr, B, N, K, k, ws_s, ws_i); break;
-            case MCQ_SEARCH_COS: rc = launch_scan_qt<kMetricCos>(p, st, tables, (int)Q, codes, w, B, N, K, k, ws_s, ws_i); break;
+            case MCQ_SEARCH_L2: rc = launch_scan_qt<kMetricL2>(p, st, tables, (int)Q, codes, w, B, N, K, k, ws_s, ws_i, mask); break;
+            case MCQ_SEARCH_IP: rc = launch_scan_qt<kMetricIP>(p, st, tables, (int)Q, codes, nullptr, B, N, K, k, ws_s, ws_i, mask); break;
+            case MCQ_SEARCH_COS: rc = launch_scan_qt<kMetricCos>(p, st, tables, (int)Q, codes, w, B, N, K, k, ws_s, ws_i, mask); break;
         }
         if (rc != 0) return rc;
     }
@@ -1716,14 +1731,21 @@ size_t mcq_search_range_workspace_bytes(long Q, long B, int N, int K) {
 
 int mcq_search_range_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
                            const float *thr, int64_t *lims, void *workspace, size_t workspace_bytes, void *stream) {
-    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, thr, lims, workspace, workspace_bytes)) return rc;
+    return mcq_search_range_count_masked(tables, Q, codes, w, B, N, K, metric, nullptr, thr, lims, workspace, workspace_bytes,
+                                         stream);
+}
+
+int mcq_search_range_count_masked(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                  int metric, const uint64_t *mask, const float *thr, int64_t *lims, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, thr, lims, workspace, workspace_bytes)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool empty = Q == 0 || B == 0;
     if (!empty) {
         const RangePlan p = range_plan(Q, B, N, K);
         int64_t *ws = static_cast<int64_t *>(workspace);
         const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr, ws, nullptr,
-                          nullptr, nullptr, 0};
+                          nullptr, nullptr, 0, mask};
         if (const int rc = launch_range_qt<false>(p, st, a)) return rc;
         hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)Q), dim3(64), 0, st, ws, p.slices * kRangeWaves, lims);
         if (const int rc = launch_rc()) return rc;
@@ -1735,14 +1757,33 @@ int mcq_search_range_count(const float *tables, long Q, const uint8_t *codes, co
 int mcq_search_range_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
                           const float *thr, const int64_t *lims, float *out_score, int64_t *out_index, long capacity,
                           void *workspace, size_t workspace_bytes, void *stream) {
-    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, thr, lims, workspace, workspace_bytes)) return rc;
+    return mcq_search_range_fill_masked(tables, Q, codes, w, B, N, K, metric, nullptr, thr, lims, out_score, out_index, capacity,
+                                        workspace, workspace_bytes, stream);
+}
+
+int mcq_search_range_fill_masked(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                 int metric, const uint64_t *mask, const float *thr, const int64_t *lims, float *out_score,
+                                 int64_t *out_index, long capacity, void *workspace, size_t workspace_bytes, void *stream) {
+    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, thr, lims, workspace, workspace_bytes)) return rc;
     if (capacity < 0) return MCQ_EINVAL;
     if (Q == 0 || B == 0 || capacity == 0) return 0;                       // nothing can be stored
     if (!out_score || !out_index) return MCQ_EINVAL;
     const RangePlan p = range_plan(Q, B, N, K);
     const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
-                      static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity};
+                      static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity, mask};
     return launch_range_qt<true>(p, static_cast<hipStream_t>(stream), a);
+}
+
+// rule 10: a byte per stored vector -> a bit per stored vector
+int mcq_search_pack_mask(const uint8_t *flags, long B, uint64_t *mask_out, void *stream) {
+    if (B < 0) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (B == 0) return 0;
+    if (!flags || !mask_out || reinterpret_cast<uintptr_t>(mask_out) % 8 != 0) return MCQ_EINVAL;
+    const long words = (B + 63) / 64;
+    hipLaunchKernelGGL(k_pack_mask, dim3((unsigned)((words + kPackWaves - 1) / kPackWaves)), dim3(64 * kPackWaves), 0,
+                       static_cast<hipStream_t>(stream), flags, B, reinterpret_cast<u64 *>(mask_out));
+    return launch_rc();
 }
 
 int mcq_last_encode_launches(void) { return g_last_launches; }

@@ -12,6 +12,9 @@
 // stores the hits.  A wave owns a CONTIGUOUS run of its slice's steps of 64 candidates, so ascending position is (slice,
 // wave, step, lane) and the fill learns its offsets from the counts alone.  Integer sums only: the output is a function of
 // scores and thresholds.
+// Under a mask (rules 10-12; MASKED) a candidate is a hit iff its bit is set and its score passes, in COUNT and in FILL alike,
+// and a wave skips the steps of its run whose word is zero (MaskWalk of mcq_search_kernels.h).  The run itself is unchanged, so
+// the offsets are still a matter of the counts alone.
 #pragma once
 #include "mcq_search_kernels.h"
 
@@ -29,11 +32,12 @@ constexpr int kRangeWaves = 16;           // k_range_sweep: waves per workgroup 
 // The metric is a wave-uniform runtime switch at the score's last operation (score_finish; the top-k scan makes it a template
 // parameter because its lists sit at the register edge; nothing does here, and it keeps the number of instantiations down).
 // ws: int64 [Q][S][kRangeWaves] -- counts out (COUNT), start offsets relative to lims[q] in (FILL).
-template <int QT, int CH, bool FILL>
+template <int QT, int CH, bool FILL, bool MASKED>
 __global__ void __launch_bounds__(64 * kRangeWaves)
 k_range_sweep(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w, long B,
               int N, int K, int metric, int S, long per_slice, const float *__restrict__ thr, int64_t *__restrict__ ws,
-              const int64_t *__restrict__ lims, float *__restrict__ out_s, int64_t *__restrict__ out_i, long capacity) {
+              const int64_t *__restrict__ lims, float *__restrict__ out_s, int64_t *__restrict__ out_i, long capacity,
+              const u64 *__restrict__ mask) {
     extern __shared__ __attribute__((aligned(16))) char range_smem[];
     float *Tl = reinterpret_cast<float *>(range_smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -61,31 +65,68 @@ k_range_sweep(const float *__restrict__ tables, int Q, const uint8_t *__restrict
     const u64 below = (1ull << lane) - 1;
     CodeChunk<CH> cur;
     float t = 0.f;
-    tile_first(cur, t, codes, w, metric, N, sl, first, stop, lane);
-    for (long blk = first; blk < stop; ++blk) {
-        const long bl = sl.begin + blk * 64 + lane;
-        const long bnext = blk + 1 < stop ? step_at(sl, blk + 1, lane) : step_at(sl, blk, lane);
-        float tn = t;
-        float acc[QT];
-        tile_step(acc, cur, tn, Tl, codes, w, metric, N, K, step_at(sl, blk, lane), bnext);
-        const bool valid = bl < sl.end;
+    if constexpr (MASKED) {
+        // the steps of the run that hold a candidate, in order; the next step is the next of THOSE.  A set bit lies inside the
+        // slice (MaskWalk trims the last word), so "bit && valid" is the bit.  The loop without a mask, below, stays the text
+        // it was: with the comparison moved into a helper both loops share, hipcc compiles the unmasked sweeps differently.
+        MaskWalk walk(mask, sl, first, stop, 1);
+        u64 word = 0, word_next = 0;
+        int blk = walk.next(word, lane);
+        tile_first(cur, t, codes, w, metric, N, sl, blk < 0 ? stop : blk, stop, lane);
+        while (blk >= 0) {
+            const int nblk = walk.next(word_next, lane);
+            float tn = t;
+            float acc[QT];
+            tile_step(acc, cur, tn, Tl, codes, w, metric, N, K, step_at(sl, blk, lane), step_at(sl, nblk < 0 ? blk : nblk, lane));
+            const long bl = sl.begin + (long)blk * 64 + lane;
+            const bool bit = (word >> lane) & 1;
 #pragma unroll
-        for (int q = 0; q < QT; ++q) {
-            const float s = score_finish(acc[q], t, metric);
-            const bool hit = valid && s <= th[q];            // rule 7 (a NaN compares false)
-            const u64 m = __ballot(hit);
-            if constexpr (FILL) {
-                if (m) {                                     // (uniform) hits are rare
-                    const long slot = base_at[q] + cnt[q] + __builtin_popcountll(m & below);
-                    if (hit && (unsigned long)slot < (unsigned long)capacity) {
-                        out_s[slot] = s;
-                        out_i[slot] = bl;
+            for (int q = 0; q < QT; ++q) {
+                const float s = score_finish(acc[q], t, metric);
+                const bool hit = bit && s <= th[q];              // rules 7 and 11 (a NaN compares false)
+                const u64 m = __ballot(hit);
+                if constexpr (FILL) {
+                    if (m) {                                     // (uniform) hits are rare
+                        const long slot = base_at[q] + cnt[q] + __builtin_popcountll(m & below);
+                        if (hit && (unsigned long)slot < (unsigned long)capacity) {
+                            out_s[slot] = s;
+                            out_i[slot] = bl;
+                        }
                     }
                 }
+                cnt[q] += __builtin_popcountll(m);
             }
-            cnt[q] += __builtin_popcountll(m);
+            t = tn;
+            blk = nblk;
+            word = word_next;
         }
-        t = tn;
+    } else {
+        tile_first(cur, t, codes, w, metric, N, sl, first, stop, lane);
+        for (long blk = first; blk < stop; ++blk) {
+            const long bl = sl.begin + blk * 64 + lane;
+            const long bnext = blk + 1 < stop ? step_at(sl, blk + 1, lane) : step_at(sl, blk, lane);
+            float tn = t;
+            float acc[QT];
+            tile_step(acc, cur, tn, Tl, codes, w, metric, N, K, step_at(sl, blk, lane), bnext);
+            const bool valid = bl < sl.end;
+#pragma unroll
+            for (int q = 0; q < QT; ++q) {
+                const float s = score_finish(acc[q], t, metric);
+                const bool hit = valid && s <= th[q];            // rule 7 (a NaN compares false)
+                const u64 m = __ballot(hit);
+                if constexpr (FILL) {
+                    if (m) {                                     // (uniform) hits are rare
+                        const long slot = base_at[q] + cnt[q] + __builtin_popcountll(m & below);
+                        if (hit && (unsigned long)slot < (unsigned long)capacity) {
+                            out_s[slot] = s;
+                            out_i[slot] = bl;
+                        }
+                    }
+                }
+                cnt[q] += __builtin_popcountll(m);
+            }
+            t = tn;
+        }
     }
 
     if constexpr (!FILL) {

@@ -18,6 +18,14 @@
 //      division (no v_rsq_f32, no fast-math: the tests restate it as float32(1) / sqrt(t) in numpy and compare bits).
 //   4. the result lists are the k smallest under "(s, b) ascending", listed in that order: pair_less below is the ONLY comparison
 //      of the scan and of the merge, so the k indexes are a function of the scores alone.  No floating-point atomics anywhere.
+//  10. a mask (k_search_scan<.., MASKED = true>, k_range_sweep likewise) is one bit per stored vector, bit b & 63 of the 64-bit
+//      word b >> 6 (k_pack_mask makes one from a byte per vector); bits at positions >= B are ignored.
+//  11. rules 3, 3', 4, 7 and 8 hold over the vectors whose bit is set, positions staying the original ones: a score is formed
+//      by tile_step and score_finish as without a mask, the mask only decides whether a lane OFFERS its candidate.
+//  12. no mask (MASKED = false) is the code as it was.  A step of 64 candidates is one aligned word of the mask (slices start
+//      at multiples of 64), so a wave learns from one wave-uniform word that a step is empty and skips it whole: no code
+//      load, no gather, no list insert (MaskWalk below).  Behind a cleared bit of a step that is not empty the codes and w are
+//      loaded as always (in bounds: step_at) and the score, whatever it is, is never offered.
 #pragma once
 #include "mcq_kernels.h"
 #include <hip/hip_fp16.h>
@@ -35,6 +43,7 @@ constexpr int kScanQTMax = 16;            //                queries per tile at 
 constexpr int kScanTableLds = 128 * 1024; //                bytes of LDS the tables of a tile may take (160 KiB per CU)
 constexpr int kScanTargetBlocks = 256;    //                workgroups that fill the chip once (one per CU)
 constexpr int kScanMaxSlices = 256;       //                cap of the slice count: the workspace stops growing with B here
+constexpr int kMaskWindow = 64;           // MaskWalk: steps of a wave whose mask words one refill reads, one word per lane
 constexpr int kNoIndex = 0x7fffffff;      // position of a list entry that holds no candidate (B <= 2^31 - 1: never a real one)
 // the finishing operation of a candidate's score (MCQ_SEARCH_L2 / _IP / _COS of include/mcq.h): a template parameter of the scan
 constexpr int kMetricL2 = 0;
@@ -234,6 +243,53 @@ __device__ __forceinline__ void tile_first(CodeChunk<CH> &cur, float &t, const u
     }
 }
 
+// ---- the mask (rules 10-12): which of a wave's steps are worth taking.  The wave's steps are first, first + stride, ... below
+// stop (stride kScanWaves in the scan, 1 in the sweeps).  A refill reads the words of the next kMaskWindow of them, one per
+// lane (none past stop; the last step of the slice keeps only the bits below the slice's end, which drops the bits at
+// positions >= B); a ballot of "non-zero" is the set of steps of the window that hold a candidate, and next() walks its set
+// bits.  Everything but `mine` is wave-uniform (first comes through readfirstlane), so the kernels' loops over next() branch
+// on scalars.
+struct MaskWalk {
+    const u64 *words;                                        // word i belongs to step i of the slice
+    int ahead, stop, stride, last;                           // `ahead`: the first step no refill has read yet; last: steps - 1
+    int base;                                                // the step of lane 0's word
+    u64 tail, live, mine;                                    // live: the window's non-empty steps not yet handed out
+
+    __device__ __forceinline__ MaskWalk(const u64 *__restrict__ mask, const Slice &sl, long first, long stop_, int stride_)
+        : words(mask + sl.begin / 64), ahead(__builtin_amdgcn_readfirstlane((int)first)),
+          stop(__builtin_amdgcn_readfirstlane((int)stop_)), stride(stride_), last((int)sl.steps - 1), base(0), live(0), mine(0) {
+        const int c = (int)(sl.end - sl.begin) - 64 * last;  // candidates of the slice's last step: 1 .. 64
+        tail = c == 64 ? ~0ull : (1ull << c) - 1;
+    }
+
+    // -> the wave's next step that holds a candidate, and its word (bit l: lane l offers its candidate); -1: there is none
+    __device__ __forceinline__ int next(u64 &word, int lane) {
+        while (live == 0) {
+            if (ahead >= stop) return -1;
+            const int step = ahead + lane * stride;
+            mine = step < stop ? words[step] : 0;
+            if (step == last) mine &= tail;
+            base = ahead;
+            ahead += kMaskWindow * stride;
+            live = __ballot(mine != 0);
+        }
+        const int j = __builtin_ctzll(live);
+        live &= live - 1;
+        word = readlane_u64(mine, j);
+        return base + j * stride;
+    }
+};
+
+// a byte per stored vector -> the mask of rule 10: a wave reads 64 flags and one ballot is the word (the bits past B are zero)
+constexpr int kPackWaves = 4;
+__global__ void __launch_bounds__(64 * kPackWaves)
+k_pack_mask(const uint8_t *__restrict__ flags, long B, u64 *__restrict__ mask) {
+    const long word = (long)blockIdx.x * kPackWaves + (threadIdx.x >> 6);
+    const long b = word * 64 + lane_id();
+    const u64 m = __ballot(b < B && flags[b] != 0);
+    if (lane_id() == 0 && word * 64 < B) mask[word] = m;
+}
+
 // One step of one wave against the QT queries of the staged tile: acc[q] = the N table additions of rule 3 in codebook order,
 // the digits arriving in N / CH chunks of CH codebooks.  b is the lane's candidate of this step and bnext that of the wave's
 // next step (b again in its last), both from step_at: the kernel says which step comes next.  `cur` holds the digits of b on
@@ -278,10 +334,12 @@ __device__ __forceinline__ void tile_step(float (&acc)[QT], CodeChunk<CH> &cur, 
 }
 
 // M: what finishes a score (rule 3).  w is t[b] (L2) or r[b] (cosine); the inner-product scan has no w and loads none.
-template <int QT, int N, int M>
+// MASKED: `mask` decides which candidates are offered (rules 10-12); without it the pointer is never read.
+template <int QT, int N, int M, bool MASKED>
 __global__ void __launch_bounds__(64 * kScanWaves)
 k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w,
-              long B, int K, int k, int S, long per_slice, float *__restrict__ ws_s, int *__restrict__ ws_i) {
+              long B, int K, int k, int S, long per_slice, float *__restrict__ ws_s, int *__restrict__ ws_i,
+              const u64 *__restrict__ mask) {
     extern __shared__ __attribute__((aligned(16))) char search_smem[];
     constexpr int CH = N < 8 ? N : 8;                        // a candidate's digits arrive in N / CH chunks of CH
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -302,17 +360,39 @@ k_search_scan(const float *__restrict__ tables, int Q, const uint8_t *__restrict
     const float *Tl = reinterpret_cast<const float *>(search_smem);
     CodeChunk<CH> cur;
     float t = 0.f;
-    tile_first(cur, t, codes, w, M, N, sl, wave, sl.steps, lane);
-    for (long blk = wave; blk < sl.steps; blk += kScanWaves) {
-        const long bl = sl.begin + blk * 64 + lane;
-        const long bnext = blk + kScanWaves < sl.steps ? step_at(sl, blk + kScanWaves, lane) : step_at(sl, blk, lane);
-        float tn = t;
-        float acc[QT];
-        tile_step<QT, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, step_at(sl, blk, lane), bnext);
+    if constexpr (MASKED) {
+        // the same loop over the wave's steps that hold a candidate: "next step" is the next of THOSE, and its digits and w
+        // travel ahead as below.  A wave without one loads nothing and its lists stay kNoIndex.
+        MaskWalk walk(mask, sl, wave, sl.steps, kScanWaves);
+        u64 word = 0, word_next = 0;
+        int blk = walk.next(word, lane);
+        tile_first(cur, t, codes, w, M, N, sl, blk < 0 ? sl.steps : blk, sl.steps, lane);
+        while (blk >= 0) {
+            const int nblk = walk.next(word_next, lane);
+            const long bl = sl.begin + (long)blk * 64 + lane;
+            float tn = t;
+            float acc[QT];
+            tile_step<QT, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, step_at(sl, blk, lane), step_at(sl, nblk < 0 ? blk : nblk, lane));
 #pragma unroll
-        for (int q = 0; q < QT; ++q)
-            list_insert(ls[q], li[q], ts[q], tb[q], score_finish(acc[q], t, M), (int)bl, bl < sl.end, k, lane);
-        t = tn;
+            for (int q = 0; q < QT; ++q)             // (a set bit lies inside the slice: MaskWalk trims the last word)
+                list_insert(ls[q], li[q], ts[q], tb[q], score_finish(acc[q], t, M), (int)bl, (word >> lane) & 1, k, lane);
+            t = tn;
+            blk = nblk;
+            word = word_next;
+        }
+    } else {
+        tile_first(cur, t, codes, w, M, N, sl, wave, sl.steps, lane);
+        for (long blk = wave; blk < sl.steps; blk += kScanWaves) {
+            const long bl = sl.begin + blk * 64 + lane;
+            const long bnext = blk + kScanWaves < sl.steps ? step_at(sl, blk + kScanWaves, lane) : step_at(sl, blk, lane);
+            float tn = t;
+            float acc[QT];
+            tile_step<QT, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, step_at(sl, blk, lane), bnext);
+#pragma unroll
+            for (int q = 0; q < QT; ++q)
+                list_insert(ls[q], li[q], ts[q], tb[q], score_finish(acc[q], t, M), (int)bl, bl < sl.end, k, lane);
+            t = tn;
+        }
     }
 
     // the waves' lists -> LDS -> one list per query of the tile

@@ -577,6 +577,46 @@ class Quantizer(nn.Module):
         assert w is None or tuple(w.shape) == (B,)
         return tables, codes, w, self._METRICS[metric], Q, B, dev
 
+    @staticmethod
+    def _check_mask(mask, B: int) -> None:
+        """what search and range_search accept as `mask` over a store of B vectors: bool (B,) flags, or the int64 words
+        pack_mask made of them.  Looks at shape and dtype only, so it runs before any device work."""
+        if mask is None:
+            return
+        words = (B + 63) // 64
+        if not isinstance(mask, Tensor) or mask.dtype not in (torch.bool, torch.int64) or mask.ndim != 1:
+            raise ValueError(f"mask: a bool ({B},) tensor or the int64 ({words},) tensor pack_mask returned, not "
+                             f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
+        if mask.dtype == torch.bool and mask.numel() != B:
+            raise ValueError(f"mask of {mask.numel()} flags for a store of {B} vectors")
+        if mask.dtype == torch.int64 and mask.numel() != words:
+            raise ValueError(f"packed mask of {mask.numel()} words for a store of {B} vectors, which takes {words}")
+
+    def pack_mask(self, keep: Tensor) -> Tensor:
+        """keep bool or uint8 (B,), non-zero = the stored vector is a candidate -> int64 (ceil(B / 64),): bit b & 63 of word
+        b >> 6 (mcq_search_pack_mask).  What search(mask=...) and range_search(mask=...) take; pack once, search many times."""
+        if not isinstance(keep, Tensor) or keep.dtype not in (torch.bool, torch.uint8) or keep.ndim != 1:
+            raise ValueError(f"pack_mask: a bool or uint8 (B,) tensor, not {getattr(keep, 'dtype', type(keep))} "
+                             f"{tuple(getattr(keep, 'shape', ()))}")
+        if not keep.is_cuda:
+            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
+        L = _lib.lib()
+        if not hasattr(L, "mcq_search_pack_mask"):
+            raise _lib.McqError(f"{_lib.LIB_PATH} has no masked search (mcq_search_pack_mask)")
+        flags = keep.detach().contiguous().view(torch.uint8)
+        B, dev = flags.numel(), flags.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            out = torch.empty(((B + 63) // 64,), dtype=torch.int64, device=dev)
+            rc = L.mcq_search_pack_mask(flags.data_ptr(), B, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "mcq_search_pack_mask")
+        return out
+
+    def _mask_words(self, mask):
+        """a mask that passed _check_mask and sits on the device -> its int64 words (None stays None)"""
+        if mask is None or mask.dtype == torch.int64:
+            return None if mask is None else mask.detach().contiguous()
+        return self.pack_mask(mask)
+
     def _metric_array(self, metric: str, flat: Tensor, norms, rnorms):
         """the per-candidate array of a metric, from what the caller handed in or else from the codes: norms (l2), none (ip),
         reciprocal roots (cosine: rnorms, or norms converted on the device, or code_rnorms)"""
@@ -588,31 +628,42 @@ class Quantizer(nn.Module):
             return rnorms.reshape(-1)
         return self.code_rnorms(flat) if norms is None else self.rnorms_from_norms(norms)
 
-    def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int, metric: str = "l2"):
+    def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int, metric: str = "l2", mask: Tensor = None):
         """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, norms fp32 (B,) -> (scores fp32 (Q, k), indexes int64 (Q, k)):
         the k smallest score[q][b] = sum_n tables[q][n][codes[b][n]] + norms[b] under (score, b) ascending (mcq_search_scan).
         metric "ip": the score is the sum alone and `norms` is not looked at (None will do); "cosine": `norms` holds the
-        reciprocal roots (code_rnorms) and the score is the sum times norms[b] (mcq_search_scan_metric)."""
+        reciprocal roots (code_rnorms) and the score is the sum times norms[b] (mcq_search_scan_metric).
+        mask: bool (B,) or the words of pack_mask: the k smallest among the positions whose bit is set
+        (mcq_search_scan_masked); None calls what it called before masks existed."""
         N, K = self.num_codebooks, self.codebook_size
-        tables, codes, norms, m, Q, B, dev = self._search_inputs(tables, codes, norms, metric)
+        self._check_mask(mask, codes.shape[0])
+        tables, codes, norms, m, Q, B, dev = self._search_inputs(tables, codes, norms, metric, *(() if mask is None else (mask,)))
         L = _lib.lib()
+        if mask is not None and not hasattr(L, "mcq_search_scan_masked"):
+            raise _lib.McqError(f"{_lib.LIB_PATH} has no masked search (mcq_search_scan_masked)")
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
             indexes = torch.empty((Q, k), dtype=torch.int64, device=dev)
             ws = torch.empty(L.mcq_search_workspace_bytes(Q, B, N, K, k), dtype=torch.uint8, device=dev)
-            if metric == "l2":
+            entry = "mcq_search_scan" if metric == "l2" else "mcq_search_scan_metric"
+            if mask is not None:
+                entry, words = "mcq_search_scan_masked", self._mask_words(mask)
+                rc = L.mcq_search_scan_masked(tables.data_ptr(), Q, codes.data_ptr(), None if norms is None else norms.data_ptr(),
+                                              B, N, K, int(k), m, words.data_ptr(), scores.data_ptr(), indexes.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), st)
+            elif metric == "l2":
                 rc = L.mcq_search_scan(tables.data_ptr(), Q, codes.data_ptr(), norms.data_ptr(), B, N, K, int(k),
                                        scores.data_ptr(), indexes.data_ptr(), ws.data_ptr(), ws.numel(), st)
             else:
                 rc = L.mcq_search_scan_metric(tables.data_ptr(), Q, codes.data_ptr(), None if norms is None else norms.data_ptr(),
                                               B, N, K, int(k), m, scores.data_ptr(), indexes.data_ptr(),
                                               ws.data_ptr(), ws.numel(), st)
-        _lib.check(rc, "mcq_search_scan" if metric == "l2" else "mcq_search_scan_metric")
+        _lib.check(rc, entry)
         return scores, indexes
 
     def search(self, queries: Tensor, codes: Tensor, k: int = 10, norms: Tensor = None, metric: str = "l2",
-               rnorms: Tensor = None):
+               rnorms: Tensor = None, mask: Tensor = None):
         """The k stored vectors nearest to each query, from the codes alone (nothing is decoded).
         queries (*, dim) fp32 or fp16; codes (B, num_codebooks) uint8 as encode(..., as_bytes=True) returned them (packed
         16-entry codes are unpacked first); norms = code_norms(codes) when not given (pass them in when searching repeatedly).
@@ -622,28 +673,33 @@ class Quantizer(nn.Module):
         metric="cosine": -> (similarities, indexes), cos(q, decode(codes[b])), largest first, 0 for a zero query or an
         all-zero reconstruction; it multiplies by rnorms = code_rnorms(codes): pass them in when searching repeatedly, or pass
         norms and they are converted on the device (rnorms_from_norms), else code_rnorms(codes) is run.
-        Under both the lower position comes first among equal scores and the tail of a short store is (-inf, -1)."""
+        Under both the lower position comes first among equal scores and the tail of a short store is (-inf, -1).
+        mask: search only the stored vectors it keeps -- a bool (B,) tensor (packed for this call), or the int64 tensor
+        pack_mask made of one (reused across calls); B counts stored vectors, for packed 16-entry codes as well.  Indexes
+        stay positions in `codes`, the result is that of a search over codes[mask] mapped back, and with fewer than k kept
+        vectors the tail is the short store's.  Nothing is copied: steps of 64 vectors without a kept one are skipped."""
         if metric not in self._METRICS:
             raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
+        self._check_mask(mask, codes.reshape(-1, codes.shape[-1]).shape[0])
         if metric != "l2":
-            return self._search_similarity(queries, codes, k, norms, metric, rnorms)
+            return self._search_similarity(queries, codes, k, norms, metric, rnorms, mask)
         with torch.no_grad():
             flat = self._unpacked_codes(codes)
             w = self._metric_array("l2", flat, norms, None)
             tables = self.search_tables(queries)
-            scores, indexes = self._search_scan(tables, flat, w, k)
+            scores, indexes = self._search_scan(tables, flat, w, k, mask=mask)
             q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
             dist = (scores + (q2d * q2d).sum(dim=1, keepdim=True)).clamp_(min=0.0)
         lead = queries.shape[:-1]
         return dist.reshape(*lead, k), indexes.reshape(*lead, k)
 
-    def _search_similarity(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms):
+    def _search_similarity(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask=None):
         """search() under "ip" and "cosine": the scan's scores are -2 <q, x^> and -2 |q| cos; halving is exact"""
         with torch.no_grad():
             flat = self._unpacked_codes(codes)
             w = self._metric_array(metric, flat, norms, rnorms)
             tables = self.search_tables(queries)
-            scores, indexes = self._search_scan(tables, flat, w, k, metric=metric)
+            scores, indexes = self._search_scan(tables, flat, w, k, metric=metric, mask=mask)
             sim = scores * -0.5
             if metric == "cosine":
                 q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
@@ -654,36 +710,44 @@ class Quantizer(nn.Module):
 
     # ------------------------------------------------- range search over stored codes
     def _search_range(self, tables: Tensor, codes: Tensor, w: Tensor, thr: Tensor, metric: str = "l2",
-                      max_results: int = None):
+                      max_results: int = None, mask: Tensor = None):
         """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, w as _search_scan takes it under the metric (norms, None,
         reciprocal roots), thr fp32 (Q,) -> (lims int64 (Q + 1,), scores fp32 (total,), indexes int64 (total,)): every b with
         score[q][b] <= thr[q], the entries of query q at [lims[q], lims[q+1]) in ascending position (mcq_search_range_count,
-        one host synchronisation to read lims[Q], mcq_search_range_fill).  More than max_results entries: McqError."""
+        one host synchronisation to read lims[Q], mcq_search_range_fill).  More than max_results entries: McqError.
+        mask as _search_scan takes it: only positions whose bit is set are listed (mcq_search_range_count_masked and
+        mcq_search_range_fill_masked, with the same words)."""
         N, K = self.num_codebooks, self.codebook_size
-        tables, codes, w, m, Q, B, dev = self._search_inputs(tables, codes, w, metric, thr)
+        self._check_mask(mask, codes.shape[0])
+        tables, codes, w, m, Q, B, dev = self._search_inputs(tables, codes, w, metric, thr, *(() if mask is None else (mask,)))
         L = _lib.lib()
-        if not hasattr(L, "mcq_search_range_count"):
-            raise _lib.McqError(f"{_lib.LIB_PATH} has no range search (mcq_search_range_count)")
+        count, fill = "mcq_search_range_count", "mcq_search_range_fill"
+        if mask is not None:
+            count, fill = count + "_masked", fill + "_masked"
+        if not hasattr(L, count):
+            raise _lib.McqError(f"{_lib.LIB_PATH} has no {'masked ' if mask is not None else ''}range search ({count})")
         thr = thr.detach().reshape(-1).to(torch.float32).contiguous()
         assert tuple(thr.shape) == (Q,)
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             lims = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
             ws = torch.empty(L.mcq_search_range_workspace_bytes(Q, B, N, K), dtype=torch.uint8, device=dev)
-            args = (tables.data_ptr(), Q, codes.data_ptr(), None if w is None else w.data_ptr(), B, N, K, m, thr.data_ptr(),
-                    lims.data_ptr())
-            _lib.check(L.mcq_search_range_count(*args, ws.data_ptr(), ws.numel(), st), "mcq_search_range_count")
+            args = (tables.data_ptr(), Q, codes.data_ptr(), None if w is None else w.data_ptr(), B, N, K, m)
+            if mask is not None:
+                words = self._mask_words(mask)                    # (alive until the fill has been enqueued)
+                args += (words.data_ptr(),)
+            args += (thr.data_ptr(), lims.data_ptr())
+            _lib.check(getattr(L, count)(*args, ws.data_ptr(), ws.numel(), st), count)
             total = int(lims[Q])                                  # the one host synchronisation: the result is allocated next
             if max_results is not None and total > max_results:
                 raise _lib.McqError(f"range search: {total} results exceed max_results = {max_results}")
             scores = torch.empty((total,), dtype=torch.float32, device=dev)
             indexes = torch.empty((total,), dtype=torch.int64, device=dev)
-            _lib.check(L.mcq_search_range_fill(*args, scores.data_ptr(), indexes.data_ptr(), total, ws.data_ptr(), ws.numel(), st),
-                       "mcq_search_range_fill")
+            _lib.check(getattr(L, fill)(*args, scores.data_ptr(), indexes.data_ptr(), total, ws.data_ptr(), ws.numel(), st), fill)
         return lims, scores, indexes
 
     def range_search(self, queries: Tensor, codes: Tensor, radius, norms: Tensor = None, metric: str = "l2",
-                     rnorms: Tensor = None, max_results: int = 1 << 26):
+                     rnorms: Tensor = None, max_results: int = 1 << 26, mask: Tensor = None):
         """Every stored vector within `radius` of each query, from the codes alone (nothing is decoded).
         queries (*, dim) fp32 or fp16, flattened to Q rows; codes, norms and rnorms exactly as search takes them; radius a
         Python float or a tensor of Q values.
@@ -695,9 +759,11 @@ class Quantizer(nn.Module):
         metric="ip": listed iff <q, decode(codes[b])> >= radius.  metric="cosine": listed iff cos >= radius; a zero query has
         every similarity 0: everything is listed when radius <= 0 and nothing otherwise.
         One host synchronisation (reading lims[Q]) separates counting from filling; more than max_results entries raise
-        McqError, naming the count, before anything is allocated for them.  Not differentiable."""
+        McqError, naming the count, before anything is allocated for them.  Not differentiable.
+        mask: as search takes it; only stored vectors it keeps are listed, at their positions in `codes`."""
         if metric not in self._METRICS:
             raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
+        self._check_mask(mask, codes.reshape(-1, codes.shape[-1]).shape[0])
         with torch.no_grad():
             flat = self._unpacked_codes(codes)
             tables = self.search_tables(queries)
@@ -722,7 +788,7 @@ class Quantizer(nn.Module):
                 zero = qn[:, 0] == 0                               # every similarity of a zero query is 0
                 thr = torch.where(zero, torch.where(rad <= 0, float("inf"), float("-inf")).to(thr.dtype), thr)
                 qn = qn.masked_fill(qn == 0, 1.0)
-            lims, scores, indexes = self._search_range(tables, flat, w, thr, metric, max_results)
+            lims, scores, indexes = self._search_range(tables, flat, w, thr, metric, max_results, mask)
             rows = torch.repeat_interleave(torch.arange(Q, device=dev), lims[1:] - lims[:-1], output_size=scores.numel())
             if metric == "l2":
                 values = (scores + qq[:, 0][rows]).clamp_(min=0.0)
