@@ -12,6 +12,7 @@
 #include "mcq_range_kernels.h"
 
 #include <cstdlib>
+#include <iterator>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -174,11 +175,12 @@ WorkspaceT<CT> carve(void *ws, long Bc, int N, int K, int D) {
 
 // up to 64 codebooks (QuantizerTrainer produces at most 64 x 16 and 32 x 256: bytes_per_frame <= 32); codebooks of 512 and 1,024
 // entries (Quantizer(codebook_size = ...) used with as_bytes = False) as long as the Gram matrix stays within 16,384 rows (1 GB)
+constexpr int kMaxRows = 16384;
 bool domain_ok(int N, int K, int D) {
-    return is_pow2(K) && K >= 16 && K <= 1024 && is_pow2(N) && N <= 64 && (long)N * K <= 16384 && D >= 1 && D <= 16384;
+    return is_pow2(K) && K >= 16 && K <= 1024 && is_pow2(N) && N <= 64 && (long)N * K <= kMaxRows && D >= 1 && D <= 16384;
 }
 int domain_err(int N, int K, int D = 1) {
-    return (K < 16 || K > 1024 || N > 64 || (long)N * K > 16384 || D > 16384) ? MCQ_EUNSUPPORTED : MCQ_EINVAL;
+    return (K < 16 || K > 1024 || N > 64 || (long)N * K > kMaxRows || D > 16384) ? MCQ_EUNSUPPORTED : MCQ_EINVAL;
 }
 
 // optional per-launch timing (mcq_profile_encode)
@@ -230,6 +232,36 @@ inline int launch_rc() {
     return e == hipSuccess ? 0 : (int)e;
 }
 inline int counted_launch_rc() { MCQ_LAUNCH_CHECK(); return 0; }
+
+// Kernel selection: a runtime value becomes a template argument ("Kernel selection").  pick<Vs...>(v, f) calls
+// f(std::integral_constant<int, V>{}) for the V that equals v and returns what f returns; no V equals v: MCQ_EUNSUPPORTED.  The
+// list IS the set of instantiations: f is stamped for every V, so a case belongs in it only if the host can reach it.
+template <int... Vs, typename F>
+int pick(int v, F &&f) {
+    int rc = MCQ_EUNSUPPORTED;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+template <typename F>
+int pick_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// The same over the rows of a constexpr table of pairs (a list of pairs, not the product of two lists): f(A, B) for the row
+// {A, B} that equals {a, b}.  A predicate that asks "is there a kernel for (a, b)" reads the same table (in_pairs).
+struct Pair { int a, b; };
+template <const auto &Table, typename F, size_t... I>
+int pick_pair(int a, int b, F &&f, std::index_sequence<I...>) {
+    int rc = MCQ_EUNSUPPORTED;
+    (void)((a == Table[I].a && b == Table[I].b &&
+            ((rc = f(std::integral_constant<int, Table[I].a>{}, std::integral_constant<int, Table[I].b>{})), true)) || ...);
+    return rc;
+}
+template <const auto &Table, typename F>
+int pick_pair(int a, int b, F &&f) { return pick_pair<Table>(a, b, f, std::make_index_sequence<std::size(Table)>{}); }
+template <size_t R>
+bool in_pairs(const Pair (&table)[R], int a, int b) {
+    for (const Pair &p : table) if (p.a == a && p.b == b) return true;
+    return false;
+}
 
 // Allow `kernel` up to `bytes` of dynamic LDS, once per device (a process may drive several).  `allowed` is the calling
 // launcher's static flag array: one per kernel instantiation.
@@ -348,113 +380,113 @@ int launch_logits(const int8_t *xf, const int *xe, long B, const Prepared &P, in
 constexpr unsigned kCapStage0 = 32768, kCapWave = 65536;     // workgroups of four waves / of one wave
 inline unsigned pass_grid(unsigned full, bool capped, unsigned cap) { return (capped && full > cap) ? cap : full; }
 
-template <int K>
-int launch_tf_stage0_k(int N, const float *G, const float *XC, const tf_code_of<K> *idx, const float *R, const float *Q, long B,
-                       int keep, tf_code_of<K> *ent, float *S, tf_code_of<K> *fin, const int *nact, const int *map, hipStream_t st,
-                       bool capped) {
+// Stage 0 of a pass.  Four or more 16-entry codebooks: four codebooks per wave, rank-in-row selection (k_tf_stage0_k16: its lists
+// of kc[0] == 8 fit a row, so k_tf_stage0<16, N> exists for N <= 2 only).  No shape past kMaxRows rows is stamped either.
+template <typename CT>
+int launch_tf_stage0(int K, int N, const float *G, const float *XC, const CT *idx, const float *R, const float *Q, long B, int keep,
+                     CT *ent, float *S, CT *fin, const int *nact, const int *map, hipStream_t st, bool capped) {
     const unsigned vgrid = (unsigned)(((B + 3) / 4) * N);
     const dim3 grid(pass_grid(vgrid, capped, kCapStage0)), block(256);
-#define MCQ_S0_CASE(NN)                                                                                                            \
-    case NN:                                                                                                                       \
-        if (capped) hipLaunchKernelGGL((k_tf_stage0<K, NN, true>), grid, block, 0, st, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, vgrid); \
-        else hipLaunchKernelGGL((k_tf_stage0<K, NN, false>), grid, block, 0, st, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, vgrid);      \
-        break;
-    switch (N) {
-        MCQ_S0_CASE(1) MCQ_S0_CASE(2) MCQ_S0_CASE(4) MCQ_S0_CASE(8) MCQ_S0_CASE(16) MCQ_S0_CASE(32) MCQ_S0_CASE(64)
-        default: return MCQ_EUNSUPPORTED;
-    }
-#undef MCQ_S0_CASE
-    return counted_launch_rc();
-}
-
-int launch_tf_stage0(int K, int N, const float *G, const float *XC, const uint16_t *idx, const float *R, const float *Q,
-                     long B, int keep, uint16_t *ent, float *S, uint16_t *fin, const int *nact, const int *map, hipStream_t st,
-                     bool capped) {
-    switch (K) {
-        case 512: return launch_tf_stage0_k<512>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
-        case 1024: return launch_tf_stage0_k<1024>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
-        default: return MCQ_EUNSUPPORTED;
-    }
-}
-
-int launch_tf_stage0(int K, int N, const float *G, const float *XC, const uint8_t *idx, const float *R, const float *Q,
-                     long B, int keep, uint8_t *ent, float *S, uint8_t *fin, const int *nact, const int *map, hipStream_t st,
-                     bool capped) {
-    if (K == 16 && N >= 4 && keep <= 16) {       // four codebooks per wave, rank-in-row selection
-        const dim3 grid((unsigned)((B * (N / 4) + 3) / 4)), block(256);
-#define MCQ_S16_CASE(NN) \
-    case NN: hipLaunchKernelGGL((k_tf_stage0_k16<NN>), grid, block, 0, st, G, XC, idx, R, Q, B, keep, ent, S, nact, map); break;
-        switch (N) {
-            MCQ_S16_CASE(4) MCQ_S16_CASE(8) MCQ_S16_CASE(16) MCQ_S16_CASE(32) MCQ_S16_CASE(64)
-            default: return MCQ_EUNSUPPORTED;
+    auto with_k = [&](auto kk) {
+        constexpr int KK = kk;
+        return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
+            constexpr int NN = nn;
+            if constexpr ((KK == 16 && NN >= 4) || KK * NN > kMaxRows) return MCQ_EUNSUPPORTED;
+            else return pick_bool(capped, [&](auto strided) {
+                constexpr bool STRIDED = strided;
+                hipLaunchKernelGGL((k_tf_stage0<KK, NN, STRIDED>), grid, block, 0, st, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, vgrid);
+                return counted_launch_rc();
+            });
+        });
+    };
+    if constexpr (sizeof(CT) == 1) {
+        if (K == 16 && N >= 4) {
+            const dim3 grid16((unsigned)((B * (N / 4) + 3) / 4));
+            return pick<4, 8, 16, 32, 64>(N, [&](auto nn) {
+                constexpr int NN = nn;
+                hipLaunchKernelGGL((k_tf_stage0_k16<NN>), grid16, block, 0, st, G, XC, idx, R, Q, B, keep, ent, S, nact, map);
+                return counted_launch_rc();
+            });
         }
-#undef MCQ_S16_CASE
-        MCQ_LAUNCH_CHECK();
-        return 0;
-    }
-    switch (K) {
-        case 16: return launch_tf_stage0_k<16>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
-        case 32: return launch_tf_stage0_k<32>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
-        case 64: return launch_tf_stage0_k<64>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
-        case 128: return launch_tf_stage0_k<128>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
-        case 256: return launch_tf_stage0_k<256>(N, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, st, capped);
-        default: return MCQ_EUNSUPPORTED;
+        return pick<16, 32, 64, 128, 256>(K, with_k);
+    } else {
+        return pick<512, 1024>(K, with_k);
     }
 }
 
+// E / R of a pass's vectors; a codebook entry of two bytes means K >= 512, so no more than kMaxRows / 512 codebooks
 template <typename CT>
 int launch_tf_er(int N, const float *G, const float *XC, const CT *idx, const float *xx, long B, int K, float *E, float *R,
                  float *gterms, const int *nact, const int *map, hipStream_t st) {
     const dim3 grid((unsigned)((B + 3) / 4)), block(256);
     const bool direct = B <= 8192;          // one launch instead of two (E / R of a trainer batch: 4.9 + 4.7 -> about 5 us)
-#define MCQ_ER_CASE(NN)                                                                                                  \
-    case NN:                                                                                                             \
-        if (!direct) {                                                                                                   \
-            hipLaunchKernelGGL((k_tf_gram_terms<NN, CT>), dim3((unsigned)(((B + 4 * (64 / NN) - 1) / (4 * (64 / NN))) * NN)), block, 0, st, G, idx, \
-                               B, K, gterms, nact);                                                                      \
-            MCQ_LAUNCH_CHECK();                                                                                          \
-        }                                                                                                                \
-        hipLaunchKernelGGL((k_tf_er<NN, CT>), grid, block, 0, st, gterms, XC, idx, xx, B, K, E, R, nact, map,              \
-                           direct ? G : static_cast<const float *>(nullptr));                                           \
-        break;
-    switch (N) {
-        MCQ_ER_CASE(1) MCQ_ER_CASE(2) MCQ_ER_CASE(4) MCQ_ER_CASE(8) MCQ_ER_CASE(16) MCQ_ER_CASE(32) MCQ_ER_CASE(64)
-        default: return MCQ_EUNSUPPORTED;
-    }
-#undef MCQ_ER_CASE
-    return counted_launch_rc();
+    return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
+        constexpr int NN = nn, VG = 4 * (64 / NN);      // vectors per workgroup of k_tf_gram_terms
+        if constexpr (sizeof(CT) == 2 && NN * 512 > kMaxRows) return MCQ_EUNSUPPORTED;
+        else {
+            if (!direct) {
+                hipLaunchKernelGGL((k_tf_gram_terms<NN, CT>), dim3((unsigned)(((B + VG - 1) / VG) * NN)), block, 0, st, G, idx, B, K, gterms, nact);
+                if (const int rc = counted_launch_rc()) return rc;
+            }
+            hipLaunchKernelGGL((k_tf_er<NN, CT>), grid, block, 0, st, gterms, XC, idx, xx, B, K, E, R, nact, map,
+                               direct ? G : static_cast<const float *>(nullptr));
+            return counted_launch_rc();
+        }
+    });
+}
+
+// The (kh, kc) list lengths of two consecutive levels >= 1: K >= 32 holds lists of 16, 16, 32, 32, 64, 64 candidates, K == 16
+// lists of 8, 8, 16, 16, 32, 32 (one-byte entries only)
+constexpr Pair kTfUpLists[] = {{16, 32}, {32, 32}, {32, 64}, {8, 16}, {16, 16}};
+constexpr Pair kTfCombLists[] = {{16, 32}, {32, 32}, {32, 64}, {64, 64}, {8, 16}, {16, 16}};
+
+// Which combines run_tf_combines asks for (DESIGN.md section 4 has the table).  Level v combines lists of (kc[v - 1], kc[v]) and
+// is the last one of 2^(v + 1) codebooks, but level 3 of 16 codebooks is k_tf_comb3's: lists of equal lengths (level 3, and
+// level 5 of 64 x 16 with (32, 32)) are never the last combine otherwise.  (32, 64) is level 4 (32 codebooks: last; 64: not),
+// (64, 64) level 5 (64 codebooks: last).  Two-byte entries (K >= 512) stop at 32 codebooks, lists of 8 are one-byte entries'.
+// k_tf_comb<64, 64, false, uint8_t> is never asked for either, and stays: without it the compiler emits other code for its
+// two LAST siblings
+template <typename CT>
+constexpr bool tf_comb_reached(int kh, int kc, bool last) {
+    const bool wide = sizeof(CT) == 2;
+    if (kh == 8 || kc == 16) return !wide && !(kh == kc && last);
+    if (kh == 64) return !wide;
+    if (kh == kc) return !(last && wide);
+    return !(kc == 64 && wide && !last);
 }
 
 // group tables of level u >= 2 from those of level u - 1 (list lengths kh -> kc)
 int launch_tf_up(int kh, int kc, const TfLists &L, long B, int N, int u, int ntab, int per, const float *in, float *out,
                  const int *nact, hipStream_t st) {
-    const dim3 grid((unsigned)(B * ntab)), block(64);
-#define MCQ_UP_CASE(A, C) \
-    if (kh == A && kc == C) { hipLaunchKernelGGL((k_tf_up<A, C>), grid, block, 0, st, L, B, N, u, ntab, per, in, out, nact); MCQ_LAUNCH_CHECK(); return 0; }
-    MCQ_UP_CASE(16, 32) MCQ_UP_CASE(32, 32) MCQ_UP_CASE(32, 64) MCQ_UP_CASE(8, 16) MCQ_UP_CASE(16, 16)
-#undef MCQ_UP_CASE
-    return MCQ_EUNSUPPORTED;
+    return pick_pair<kTfUpLists>(kh, kc, [&](auto a, auto c) {
+        constexpr int KH = a, KC = c;
+        hipLaunchKernelGGL((k_tf_up<KH, KC>), dim3((unsigned)(B * ntab)), dim3(64), 0, st, L, B, N, u, ntab, per, in, out, nact);
+        return counted_launch_rc();
+    });
 }
 
-// combine of the siblings of level v >= 2 (list lengths kh at level v - 1, kc at level v)
+// combine of the siblings of level v >= 2 (list lengths kh at level v - 1, kc at level v); fin: the last combine
 template <typename CT>
 int launch_tf_comb(int kh, int kc, const float *E, const TfLists &L, long B, int N, int v, int keep, const float *tabs,
                    CT *fin, const int *nact, hipStream_t st, bool capped) {
     // (capped: the last combine only; the others of more than 8 codebooks keep their full grid)
     if (fin == nullptr) capped = false;
     const dim3 grid(pass_grid((unsigned)(B * (N >> (v + 1))), capped, kCapWave)), block(64);
-#define MCQ_COMB_CASE(A, C)                                                                                                        \
-    if (kh == A && kc == C) {                                                                                                     \
-        if (fin && capped) hipLaunchKernelGGL((k_tf_comb<A, C, true, CT, true>), grid, block, 0, st, E, L, B, N, v, keep, tabs, fin, nact); \
-        else if (fin) hipLaunchKernelGGL((k_tf_comb<A, C, true, CT>), grid, block, 0, st, E, L, B, N, v, keep, tabs, fin, nact);  \
-        else hipLaunchKernelGGL((k_tf_comb<A, C, false, CT>), grid, block, 0, st, E, L, B, N, v, keep, tabs, fin, nact);          \
-        MCQ_LAUNCH_CHECK();                                                                                                       \
-        return 0;                                                                                                                 \
-    }
-    MCQ_COMB_CASE(16, 32) MCQ_COMB_CASE(32, 32) MCQ_COMB_CASE(32, 64) MCQ_COMB_CASE(64, 64)
-    if constexpr (sizeof(CT) == 1) { MCQ_COMB_CASE(8, 16) MCQ_COMB_CASE(16, 16) }      // (lists of 8: 16-entry codebooks)
-#undef MCQ_COMB_CASE
-    return MCQ_EUNSUPPORTED;
+    return pick_pair<kTfCombLists>(kh, kc, [&](auto a, auto c) {
+        return pick_bool(fin != nullptr, [&](auto last) {
+            constexpr int KH = decltype(a)::value, KC = decltype(c)::value;
+            constexpr bool LAST = last;
+            if constexpr (!tf_comb_reached<CT>(KH, KC, LAST)) return MCQ_EUNSUPPORTED;
+            else return pick_bool(capped, [&](auto strided) {
+                constexpr bool STRIDED = strided;
+                if constexpr (STRIDED && !LAST) return MCQ_EUNSUPPORTED;      // (not reached: capped only with fin)
+                else {
+                    hipLaunchKernelGGL((k_tf_comb<KH, KC, LAST, CT, STRIDED>), grid, block, 0, st, E, L, B, N, v, keep, tabs, fin, nact);
+                    return counted_launch_rc();
+                }
+            });
+        });
+    });
 }
 
 // profiling categories (mcq_profile_encode): one per KIND OF LAUNCH of the shipped sequence -- the profiler records events round
@@ -477,16 +509,13 @@ const char *const kCatNames[CAT_COUNT] = {
     "encode_tail",                // k_finalize / k_import_indexes / k_compact
 };
 
-// the combines of one refinement pass; lists of K >= 32 hold 16, 16, 32, 32, 64 candidates, of K == 16: 8, 8, 16, 16, 32, 32
-// (the kernels over lists of 8 -- 16-entry codebooks -- exist for one-byte entries only)
-#define MCQ_TF_LAUNCH2(SMALLK, BIGK, grid, block, ...)                                                       \
-    do {                                                                                                     \
-        bool s_ = false;                                                                                     \
-        if constexpr (sizeof(CT) == 1) {                                                                     \
-            if (small) { hipLaunchKernelGGL(SMALLK, grid, block, 0, st, __VA_ARGS__); s_ = true; }           \
-        }                                                                                                    \
-        if (!s_) hipLaunchKernelGGL(BIGK, grid, block, 0, st, __VA_ARGS__);                                  \
-    } while (0)
+// The list length of levels 0 and 1 as a template argument: 8 for 16-entry codebooks, else 16.  The kernels over lists of 8
+// exist for one-byte entries only
+template <typename CT, typename F>
+int pick_leaf_lists(int K, F &&f) {
+    if constexpr (sizeof(CT) == 1) return pick<8, 16>(K == 16 ? 8 : 16, f);
+    else return pick<16>(16, f);
+}
 // MCQ_PASS16=0: the separate kernels for 16 x 16 codebooks as well (same-box A/B of the LDS-resident pass; identical results)
 inline bool pass16_enabled() {
     static const bool on = !(getenv("MCQ_PASS16") && atoi(getenv("MCQ_PASS16")) == 0);
@@ -499,31 +528,35 @@ inline long skip_min_batch() {
     return v ? atol(v) : 8192;      // (4,096 vectors: 0.472 ms with compaction, 0.477 without; 8,192: 0.773 / 0.800)
 }
 
+// the combines of one refinement pass
 template <typename CT>
 int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const WorkspaceT<CT> &w, const TfLists &L, long B, int N,
                     int K, const int *nact, hipStream_t st, Prof *prof, bool capped) {
     const bool small = (K == 16);
     const int nlev = tf_levels(N);
+    const dim3 wave(64);
     {   // level 0: single codebooks
         const int keep = (N == 2) ? 1 : L.kc[1];
         CT *fin = (N == 2) ? idx_new : nullptr;
         const dim3 grid((unsigned)(B * (N / 2)));
         Timed t(prof, CAT_LEVEL0);
-        bool done0 = false;
-        if constexpr (sizeof(CT) == 1) {
-            // lists of 16 one-byte entries: the slot-major kernel (a 16-lane group of a gather = one table row: a fifth faster than
-            // the lane-major one, profiles/r06_ab_pair0_slot_major.txt)
-            if (!small) {
-                if (capped)
-                    hipLaunchKernelGGL(k_tf_pair0s<true>, dim3(pass_grid(grid.x, true, kCapWave)), dim3(64), 0, st, G, idx_cur, w.E, L, B, N,
+        const int rc = pick_leaf_lists<CT>(K, [&](auto kc0) {
+            constexpr int KC = kc0;
+            if constexpr (sizeof(CT) == 1 && KC == 16) {
+                // lists of 16 one-byte entries: the slot-major kernel (a 16-lane group of a gather = one table row: a fifth faster than
+                // the lane-major one, profiles/r06_ab_pair0_slot_major.txt)
+                return pick_bool(capped, [&](auto strided) {
+                    constexpr bool STRIDED = strided;
+                    hipLaunchKernelGGL(k_tf_pair0s<STRIDED>, dim3(pass_grid(grid.x, capped, kCapWave)), wave, 0, st, G, idx_cur, w.E, L, B, N,
                                        K, keep, fin, nact);
-                else
-                    hipLaunchKernelGGL(k_tf_pair0s<false>, grid, dim3(64), 0, st, G, idx_cur, w.E, L, B, N, K, keep, fin, nact);
-                done0 = true;
+                    return counted_launch_rc();
+                });
+            } else {
+                hipLaunchKernelGGL((k_tf_pair0<KC, CT>), grid, wave, 0, st, G, idx_cur, w.E, L, B, N, K, keep, fin, nact);
+                return counted_launch_rc();
             }
-        }
-        if (!done0) MCQ_TF_LAUNCH2((k_tf_pair0<8, CT>), (k_tf_pair0<16, CT>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, fin, nact);
-        MCQ_LAUNCH_CHECK();
+        });
+        if (rc) return rc;
     }
     // the level-1 combines and the cousin tables of level 2 share a launch (k_tf_level1): same workgroup-to-XCD mapping as the two
     // launches, one boundary and one tail less (5.95 -> 5.86 ms per encode of 65,536 vectors, 0.55 -> 0.51 ms at 4,096)
@@ -540,20 +573,24 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
         const unsigned vgrid = pair_blocks + tab_blocks + (fuse_l3 ? (unsigned)(B * ntab3) : 0u);
         const dim3 grid(pass_grid(vgrid, capped, kCapWave));
         Timed t(prof, CAT_LEVEL1_FUSED);
-        if (capped)
-            MCQ_TF_LAUNCH2((k_tf_level1<8, 8, CT, true>), (k_tf_level1<16, 16, CT, true>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, ntab1,
-                           per1, w.tabs[0], nact, pair_blocks, tab_blocks, ntab3, per3, w.tabs[1], vgrid);
-        else
-            MCQ_TF_LAUNCH2((k_tf_level1<8, 8, CT>), (k_tf_level1<16, 16, CT>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, ntab1, per1, w.tabs[0],
-                           nact, pair_blocks, tab_blocks, ntab3, per3, w.tabs[1], vgrid);
-        MCQ_LAUNCH_CHECK();
-    } else if (N >= 4) {   // level 1: pairs of codebooks
-        const int keep = (N == 4) ? 1 : L.kc[2];
-        CT *fin = (N == 4) ? idx_new : nullptr;
-        const dim3 grid((unsigned)(B * (N / 4)));
+        const int rc = pick_leaf_lists<CT>(K, [&](auto kc0) {
+            return pick_bool(capped, [&](auto strided) {
+                constexpr int KC = decltype(kc0)::value;
+                constexpr bool STRIDED = strided;
+                hipLaunchKernelGGL((k_tf_level1<KC, KC, CT, STRIDED>), grid, wave, 0, st, G, idx_cur, w.E, L, B, N, K, keep, ntab1, per1,
+                                   w.tabs[0], nact, pair_blocks, tab_blocks, ntab3, per3, w.tabs[1], vgrid);
+                return counted_launch_rc();
+            });
+        });
+        if (rc) return rc;
+    } else if (N >= 4) {   // level 1: pairs of codebooks -- four codebooks (eight and more: above), so this is the last combine
         Timed t(prof, CAT_LEVEL1);
-        MCQ_TF_LAUNCH2((k_tf_pair1<8, 8, CT>), (k_tf_pair1<16, 16, CT>), grid, dim3(64), G, idx_cur, w.E, L, B, N, K, keep, fin, nact);
-        MCQ_LAUNCH_CHECK();
+        const int rc = pick_leaf_lists<CT>(K, [&](auto kc0) {
+            constexpr int KC = kc0;
+            hipLaunchKernelGGL((k_tf_pair1<KC, KC, CT>), dim3((unsigned)B), wave, 0, st, G, idx_cur, w.E, L, B, N, K, 1, idx_new, nact);
+            return counted_launch_rc();
+        });
+        if (rc) return rc;
     }
     for (int v = 2; v < nlev; ++v) {   // level v: level-1 tables of the cousins below, raised level by level, then the combine
         const int groups = N >> (v + 1);
@@ -564,15 +601,23 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
         const int cat_tab = (v == 2) ? CAT_TABLES : CAT_TABLES_UP, cat_comb = (v == 2) ? CAT_COMBINE : CAT_COMBINE_UP;
         if (!(fuse_l1 && v == 2) && !(fuse_l3 && v == 3)) {     // (these tables came with the level-1 combines)
             Timed t(prof, cat_tab);
-            MCQ_TF_LAUNCH2((k_tf_table1<8, 8, CT>), (k_tf_table1<16, 16, CT>), dim3((unsigned)(B * ntab1)), dim3(64), G, idx_cur, L, B, N, K, ntab1, per1,
-                           w.tabs[0], nact);
-            MCQ_LAUNCH_CHECK();
+            const int rc = pick_leaf_lists<CT>(K, [&](auto kc0) {
+                constexpr int KC = kc0;
+                hipLaunchKernelGGL((k_tf_table1<KC, KC, CT>), dim3((unsigned)(B * ntab1)), wave, 0, st, G, idx_cur, L, B, N, K, ntab1, per1,
+                                   w.tabs[0], nact);
+                return counted_launch_rc();
+            });
+            if (rc) return rc;
         }
         if (N == 16 && v == 3) {       // two groups of eight: levels 2 and 3 in one kernel, tables in LDS
             Timed t(prof, cat_comb);
             const float *t3 = fuse_l3 ? w.tabs[1] : w.tabs[0];
-            MCQ_TF_LAUNCH2((k_tf_comb3<8, 16, 16, CT>), (k_tf_comb3<16, 32, 32, CT>), dim3((unsigned)B), dim3(256), idx_cur, w.E, L, B, N, t3, idx_new, nact);
-            MCQ_LAUNCH_CHECK();
+            const int rc = pick_leaf_lists<CT>(K, [&](auto kc0) {
+                constexpr int KC = kc0;
+                hipLaunchKernelGGL((k_tf_comb3<KC, 2 * KC, 2 * KC, CT>), dim3((unsigned)B), dim3(256), 0, st, idx_cur, w.E, L, B, N, t3, idx_new, nact);
+                return counted_launch_rc();
+            });
+            if (rc) return rc;
             continue;
         }
         int cur = 0;
@@ -587,7 +632,6 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
     }
     return 0;
 }
-#undef MCQ_TF_LAUNCH2
 
 // ---------------------------------------------------------------- the encode: checks, then per chunk start / pass16 or passes / tail
 struct EncodeCall {     // what every chunk of one call shares
@@ -659,11 +703,11 @@ int launch_pass16(const EncodeCall &c, const WorkspaceT<uint8_t> &w, long Bc, co
     a.out_i64 = out.pack == 1 ? out.i64 : nullptr;
     a.out_u8 = out.pack == 1 ? out.bytes() : nullptr;
     const long wgs = (Bc + kP16Waves - 1) / kP16Waves;
-    if (c.N == 16)   // one workgroup per CU (157,696 B of LDS), two with eight codebooks (62,464 B)
-        hipLaunchKernelGGL(k_tf_pass16<16>, dim3((unsigned)(wgs < 256 ? wgs : 256)), dim3(64 * kP16Waves), p16_lds_bytes<16>(), c.st, a);
-    else
-        hipLaunchKernelGGL(k_tf_pass16<8>, dim3((unsigned)(wgs < 512 ? wgs : 512)), dim3(64 * kP16Waves), p16_lds_bytes<8>(), c.st, a);
-    return counted_launch_rc();
+    return pick<16, 8>(c.N, [&](auto nn) {   // one workgroup per CU (157,696 B of LDS), two with eight codebooks (62,464 B)
+        constexpr int NN = nn, cap = NN == 16 ? 256 : 512;
+        hipLaunchKernelGGL(k_tf_pass16<NN>, dim3((unsigned)(wgs < cap ? wgs : cap)), dim3(64 * kP16Waves), p16_lds_bytes<NN>(), c.st, a);
+        return counted_launch_rc();
+    });
 }
 
 // What moves from pass to pass.  Without skipping the indexes are refined in place in w.idx and nothing rotates.  Under skipping
@@ -851,10 +895,12 @@ int launch_decode_backward(const float *g, const IdxT *idx, long B, int N, int K
     if (chunks <= 8 && (8 % chunks) == 0) blocks = ((rowgroups + (8 / chunks) - 1) / (8 / chunks)) * 8;
     else blocks = ((long)N * K * chunks + 3) / 4;
     const dim3 grid((unsigned)blocks), block(256);
-    if (cw == 4) hipLaunchKernelGGL((k_decode_backward<IdxT, 4>), grid, block, 0, st, g, idx, B, N, K, D, chunks, out, gsb, gsn, idx_stride, sa, sb, sc, dotw, dot_part);
-    else if (cw == 2) hipLaunchKernelGGL((k_decode_backward<IdxT, 2>), grid, block, 0, st, g, idx, B, N, K, D, chunks, out, gsb, gsn, idx_stride, sa, sb, sc, dotw, dot_part);
-    else hipLaunchKernelGGL((k_decode_backward<IdxT, 1>), grid, block, 0, st, g, idx, B, N, K, D, chunks, out, gsb, gsn, idx_stride, sa, sb, sc, dotw, dot_part);
-    return launch_rc();
+    return pick<4, 2, 1>(cw, [&](auto w) {
+        constexpr int CW = w;
+        hipLaunchKernelGGL((k_decode_backward<IdxT, CW>), grid, block, 0, st, g, idx, B, N, K, D, chunks, out, gsb, gsn, idx_stride, sa, sb, sc,
+                           dotw, dot_part);
+        return launch_rc();
+    });
 }
 }  // namespace
 
@@ -942,48 +988,29 @@ ScanPlan scan_plan(long Q, long B, int N, int K, int k) {
     return p;
 }
 
-template <int QT, int NN, int M, bool MASKED>
-int launch_scan(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *norms, long B,
-                int K, int k, float *ws_s, int *ws_i, const uint64_t *mask) {
-    static bool allowed[64] = {};
-    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_scan<QT, NN, M, MASKED>), kScanTableLds))
-        return rc;
-    hipLaunchKernelGGL((k_search_scan<QT, NN, M, MASKED>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kScanWaves),
-                       p.lds, st, tables, Q, codes, norms, B, K, k, p.slices, p.per_slice, ws_s, ws_i,
-                       reinterpret_cast<const u64 *>(mask));
-    return launch_rc();
-}
-
-// the mask is a template parameter of the scan and of the sweeps as well: the instantiations without one are the code they
-// were before masks existed
-template <int QT, int M>
-int launch_scan_n(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *norms,
-                  long B, int N, int K, int k, float *ws_s, int *ws_i, const uint64_t *mask) {
-    switch (N) {
-#define MCQ_SCAN_CASE(NN)                                                                                          \
-    case NN:                                                                                                       \
-        return mask ? launch_scan<QT, NN, M, true>(p, st, tables, Q, codes, norms, B, K, k, ws_s, ws_i, mask)      \
-                    : launch_scan<QT, NN, M, false>(p, st, tables, Q, codes, norms, B, K, k, ws_s, ws_i, nullptr);
-        MCQ_SCAN_CASE(1) MCQ_SCAN_CASE(2) MCQ_SCAN_CASE(4) MCQ_SCAN_CASE(8) MCQ_SCAN_CASE(16) MCQ_SCAN_CASE(32) MCQ_SCAN_CASE(64)
-#undef MCQ_SCAN_CASE
-    }
-    return MCQ_EUNSUPPORTED;
-}
-
-// the metric is a template parameter of the scan: the L2 instantiations are the code they were before
-// the other two metrics existed
+// The metric and the mask are template parameters of the scan (and the mask of the sweeps) as the tile and the codebook count
+// are: the L2 instantiations without a mask are the code they were before the other metrics and the masks existed (DESIGN.md
+// section 4)
 static_assert(kMetricL2 == MCQ_SEARCH_L2 && kMetricIP == MCQ_SEARCH_IP && kMetricCos == MCQ_SEARCH_COS, "include/mcq.h");
-template <int M>
-int launch_scan_qt(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
-                   int N, int K, int k, float *ws_s, int *ws_i, const uint64_t *mask) {
-    switch (p.qt) {
-        case 1: return launch_scan_n<1, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
-        case 2: return launch_scan_n<2, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
-        case 4: return launch_scan_n<4, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
-        case 8: return launch_scan_n<8, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
-        case 16: return launch_scan_n<16, M>(p, st, tables, Q, codes, w, B, N, K, k, ws_s, ws_i, mask);
-    }
-    return MCQ_EUNSUPPORTED;
+int launch_scan(const ScanPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B, int N,
+                int K, int k, int metric, float *ws_s, int *ws_i, const uint64_t *mask) {
+    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        return pick<1, 2, 4, 8, 16>(p.qt, [&](auto qt) {
+            return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
+                return pick_bool(mask != nullptr, [&](auto masked) {
+                    constexpr int M = decltype(m)::value, QT = decltype(qt)::value, NN = decltype(nn)::value;
+                    constexpr bool MASKED = masked;
+                    static bool allowed[64] = {};
+                    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_scan<QT, NN, M, MASKED>), kScanTableLds))
+                        return rc;
+                    hipLaunchKernelGGL((k_search_scan<QT, NN, M, MASKED>), dim3((unsigned)p.qtiles * (unsigned)p.slices), dim3(64 * kScanWaves),
+                                       p.lds, st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.slices, p.per_slice, ws_s, ws_i,
+                                       reinterpret_cast<const u64 *>(mask));
+                    return launch_rc();
+                });
+            });
+        });
+    });
 }
 
 }  // namespace
@@ -1020,39 +1047,25 @@ struct RangeArgs {
     const uint64_t *mask;                                                 // NULL: none (rule 12)
 };
 
-template <int QT, int CH, bool FILL, bool MASKED>
-int launch_range(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
-    static bool allowed[64] = {};
-    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_sweep<QT, CH, FILL, MASKED>),
-                                         kScanTableLds + kRangeWaves * kScanQTMax * 8))
-        return rc;
-    hipLaunchKernelGGL((k_range_sweep<QT, CH, FILL, MASKED>), dim3((unsigned)p.qtiles * (unsigned)p.slices),
-                       dim3(64 * kRangeWaves), p.lds, st, a.tables, a.Q, a.codes, a.w, a.B, a.N, a.K, a.metric, p.slices,
-                       p.per_slice, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity, reinterpret_cast<const u64 *>(a.mask));
-    return launch_rc();
-}
-
-template <int QT, bool FILL>
-int launch_range_ch(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
-    switch (a.N < 8 ? a.N : 8) {                                          // a candidate's digits arrive in chunks of CH
-        case 1: return a.mask ? launch_range<QT, 1, FILL, true>(p, st, a) : launch_range<QT, 1, FILL, false>(p, st, a);
-        case 2: return a.mask ? launch_range<QT, 2, FILL, true>(p, st, a) : launch_range<QT, 2, FILL, false>(p, st, a);
-        case 4: return a.mask ? launch_range<QT, 4, FILL, true>(p, st, a) : launch_range<QT, 4, FILL, false>(p, st, a);
-        case 8: return a.mask ? launch_range<QT, 8, FILL, true>(p, st, a) : launch_range<QT, 8, FILL, false>(p, st, a);
-    }
-    return MCQ_EUNSUPPORTED;
-}
-
+// a sweep: FILL == false counts, FILL == true stores; a candidate's digits arrive in chunks of CH = min(N, 8)
 template <bool FILL>
-int launch_range_qt(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
-    switch (p.qt) {
-        case 1: return launch_range_ch<1, FILL>(p, st, a);
-        case 2: return launch_range_ch<2, FILL>(p, st, a);
-        case 4: return launch_range_ch<4, FILL>(p, st, a);
-        case 8: return launch_range_ch<8, FILL>(p, st, a);
-        case 16: return launch_range_ch<16, FILL>(p, st, a);
-    }
-    return MCQ_EUNSUPPORTED;
+int launch_range(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
+    return pick<1, 2, 4, 8, 16>(p.qt, [&](auto qt) {
+        return pick<1, 2, 4, 8>(a.N < 8 ? a.N : 8, [&](auto ch) {
+            return pick_bool(a.mask != nullptr, [&](auto masked) {
+                constexpr int QT = decltype(qt)::value, CH = decltype(ch)::value;
+                constexpr bool MASKED = masked;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_sweep<QT, CH, FILL, MASKED>),
+                                                     kScanTableLds + kRangeWaves * kScanQTMax * 8))
+                    return rc;
+                hipLaunchKernelGGL((k_range_sweep<QT, CH, FILL, MASKED>), dim3((unsigned)p.qtiles * (unsigned)p.slices),
+                                   dim3(64 * kRangeWaves), p.lds, st, a.tables, a.Q, a.codes, a.w, a.B, a.N, a.K, a.metric, p.slices,
+                                   p.per_slice, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity, reinterpret_cast<const u64 *>(a.mask));
+                return launch_rc();
+            });
+        });
+    });
 }
 
 // rule 9: what both range entry points reject (lims is written even by an empty call); nothing touches the device
@@ -1095,24 +1108,22 @@ bool decode_blk_applies(const DecodeArgs &a) {
            decode_blk_lpv(a.N, a.K) != 0 && (a.N == 4 || a.N == 8 || a.N == 16) &&
            ((reinterpret_cast<uintptr_t>(a.codes) & 15) == 0) && ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0);
 }
-template <int NN, int LL>
-int launch_decode_blk_t(const DecodeArgs &a) {
-    static bool allowed[64] = {};
-    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_decode_blk<NN, LL>), (int)kDecBlkLdsMax)) return rc;
-    const int W = 4 * LL, ns = a.Dp / W, per_xcd = (ns + 7) / 8;
-    int groups = 256 / (8 * per_xcd);            // one workgroup per CU
-    groups = groups < 1 ? 1 : groups;
-    const long per = (((a.B + groups - 1) / groups) + 255) / 256 * 256;
-    hipLaunchKernelGGL((k_decode_blk<NN, LL>), dim3((unsigned)(8 * per_xcd * groups)), dim3(1024),
-                       (size_t)a.N * a.K * W * 4 + kDecBlkCodeBytes, a.st, static_cast<const uint8_t *>(a.codes), a.B, a.C, a.K, a.D,
-                       a.Dp, groups, per, a.out);
-    return launch_rc();
-}
 int launch_decode_blk(const DecodeArgs &a) {
-    const bool wide = decode_blk_lpv(a.N, a.K) == 4;
-    if (a.N == 4) return wide ? launch_decode_blk_t<4, 4>(a) : launch_decode_blk_t<4, 2>(a);
-    if (a.N == 8) return wide ? launch_decode_blk_t<8, 4>(a) : launch_decode_blk_t<8, 2>(a);
-    return wide ? launch_decode_blk_t<16, 4>(a) : launch_decode_blk_t<16, 2>(a);
+    return pick<4, 8, 16>(a.N, [&](auto nn) {
+        return pick<4, 2>(decode_blk_lpv(a.N, a.K), [&](auto ll) {
+            constexpr int NN = decltype(nn)::value, LL = decltype(ll)::value, W = 4 * LL;
+            static bool allowed[64] = {};
+            if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_decode_blk<NN, LL>), (int)kDecBlkLdsMax)) return rc;
+            const int ns = a.Dp / W, per_xcd = (ns + 7) / 8;
+            int groups = 256 / (8 * per_xcd);            // one workgroup per CU
+            groups = groups < 1 ? 1 : groups;
+            const long per = (((a.B + groups - 1) / groups) + 255) / 256 * 256;
+            hipLaunchKernelGGL((k_decode_blk<NN, LL>), dim3((unsigned)(8 * per_xcd * groups)), dim3(1024),
+                               (size_t)a.N * a.K * W * 4 + kDecBlkCodeBytes, a.st, static_cast<const uint8_t *>(a.codes), a.B, a.C, a.K, a.D,
+                               a.Dp, groups, per, a.out);
+            return launch_rc();
+        });
+    });
 }
 
 // LDS-resident kernel: batches of >= 16,384 vectors whose codebook slice (N*K*64 B) fits the LDS
@@ -1140,49 +1151,34 @@ int decode_sliced_lpv(int Dp) {
 bool decode_sliced_applies(const DecodeArgs &a) {
     return a.sliced_ok && a.rep == 1 && a.B >= 4096 && a.K >= 32 && decode_sliced_lpv(a.Dp) <= 64;
 }
-template <typename T, int CHH>
-int launch_decode_sliced_t(const DecodeArgs &a) {
-    const int lpv = decode_sliced_lpv(a.Dp), vpw = 64 / lpv;
-    const dim3 g((unsigned)(((a.B + 4 * vpw - 1) / (4 * vpw)) * 8));
-#define MCQ_DECS_LAUNCH(LL) \
-    hipLaunchKernelGGL((k_decode_sliced<T, CHH, LL>), g, dim3(256), 0, a.st, static_cast<const T *>(a.codes), a.B, a.C, a.N, a.K, a.D, a.Dp, a.out)
-    switch (lpv) {
-        case 4: MCQ_DECS_LAUNCH(4); break;
-        case 8: MCQ_DECS_LAUNCH(8); break;
-        case 16: MCQ_DECS_LAUNCH(16); break;
-        case 32: MCQ_DECS_LAUNCH(32); break;
-        default: MCQ_DECS_LAUNCH(64); break;
-    }
-#undef MCQ_DECS_LAUNCH
-    return launch_rc();
-}
 template <typename T>
 int launch_decode_sliced(const DecodeArgs &a) {
-    if (a.N <= 4) return launch_decode_sliced_t<T, 4>(a);
-    return a.N <= 8 ? launch_decode_sliced_t<T, 8>(a) : launch_decode_sliced_t<T, 16>(a);
+    const int lpv = decode_sliced_lpv(a.Dp), vpw = 64 / lpv;
+    const dim3 g((unsigned)(((a.B + 4 * vpw - 1) / (4 * vpw)) * 8));
+    return pick<4, 8, 16>(a.N <= 4 ? 4 : (a.N <= 8 ? 8 : 16), [&](auto ch) {      // codes of a vector per load
+        return pick<4, 8, 16, 32, 64>(lpv, [&](auto ll) {
+            constexpr int CHH = decltype(ch)::value, LL = decltype(ll)::value;
+            hipLaunchKernelGGL((k_decode_sliced<T, CHH, LL>), g, dim3(256), 0, a.st, static_cast<const T *>(a.codes), a.B, a.C, a.N, a.K, a.D,
+                               a.Dp, a.out);
+            return launch_rc();
+        });
+    });
 }
 
 // register kernel (k_decode_reg<N, J>): one-byte codes of 2, 4, 8 or 16 codebooks, J = float4s per lane of a row
-#define MCQ_DEC_REG_SHAPES(X) X(8, 2) X(8, 1) X(4, 1) X(4, 2) X(4, 4) X(16, 1) X(16, 2) X(2, 1) X(2, 2)
+constexpr Pair kDecRegShapes[] = {{8, 2}, {8, 1}, {4, 1}, {4, 2}, {4, 4}, {16, 1}, {16, 2}, {2, 1}, {2, 2}};
+inline int decode_reg_j(const DecodeArgs &a) { return (a.Dp / 4 + 63) / 64; }
 bool decode_reg_applies(const DecodeArgs &a) {
-    const int J = (a.Dp / 4 + 63) / 64;
-#define MCQ_DEC_CASE(NN, JJ) || (a.N == NN && J == JJ)
-    return a.code_bytes == 1 && a.rep == 1 && (false MCQ_DEC_REG_SHAPES(MCQ_DEC_CASE));
-#undef MCQ_DEC_CASE
+    return a.code_bytes == 1 && a.rep == 1 && in_pairs(kDecRegShapes, a.N, decode_reg_j(a));
 }
 int launch_decode_reg(const DecodeArgs &a) {
-    const int J = (a.Dp / 4 + 63) / 64;
-#define MCQ_DEC_CASE(NN, JJ)                                                                                                  \
-    if (a.N == NN && J == JJ) {                                                                                               \
-        hipLaunchKernelGGL((k_decode_reg<NN, JJ>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, a.st,                         \
-                           static_cast<const uint8_t *>(a.codes), a.B, a.C, a.K, a.D, a.Dp, a.out);                             \
-        return launch_rc();                                                                                                   \
-    }
-    MCQ_DEC_REG_SHAPES(MCQ_DEC_CASE)
-#undef MCQ_DEC_CASE
-    return MCQ_EUNSUPPORTED;      // (not reached: decode_reg_applies)
+    return pick_pair<kDecRegShapes>(a.N, decode_reg_j(a), [&](auto nn, auto jj) {
+        constexpr int NN = nn, JJ = jj;
+        hipLaunchKernelGGL((k_decode_reg<NN, JJ>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, a.st,
+                           static_cast<const uint8_t *>(a.codes), a.B, a.C, a.K, a.D, a.Dp, a.out);
+        return launch_rc();
+    });
 }
-#undef MCQ_DEC_REG_SHAPES
 
 template <typename T>
 int launch_decode_generic(const DecodeArgs &a) {
@@ -1451,15 +1447,12 @@ int launch_loss_bwd(const float *logits, const int64_t *idx, const float *lse, l
     if (B <= 0) return MCQ_EINVAL;
     if (!logits || !idx || !lse || !g_chosen || !g_prob || !grad_logits || (ex && (!bias || !dot_part))) return MCQ_EINVAL;
     const dim3 grid((unsigned)loss_bwd_blocks(B, N, K)), block(64 * kLossWaves);
-#define MCQ_LOSS_CASE(KK)                                                                                             \
-    case KK: hipLaunchKernelGGL((k_loss_bwd<KK>), grid, block, 0, static_cast<hipStream_t>(stream), logits, idx, lse, B, N, g_chosen, \
-                                g_prob, grad_logits, bias, dot_part); break;
-    switch (K) {
-        MCQ_LOSS_CASE(16) MCQ_LOSS_CASE(32) MCQ_LOSS_CASE(64) MCQ_LOSS_CASE(128) MCQ_LOSS_CASE(256)
-        default: return MCQ_EUNSUPPORTED;
-    }
-#undef MCQ_LOSS_CASE
-    return counted_launch_rc();
+    return pick<16, 32, 64, 128, 256>(K, [&](auto kk) {
+        constexpr int KK = kk;
+        hipLaunchKernelGGL((k_loss_bwd<KK>), grid, block, 0, static_cast<hipStream_t>(stream), logits, idx, lse, B, N, g_chosen, g_prob,
+                           grad_logits, bias, dot_part);
+        return counted_launch_rc();
+    });
 }
 }  // namespace
 
@@ -1480,14 +1473,12 @@ int mcq_loss_fwd(const float *logits, const int64_t *idx, long B, int N, int K, 
     float *pc = pp + chunks * N * K;
     float *ph = pc + chunks * N * K;
     const dim3 grid((unsigned)(chunks * N)), block(64 * kLossWaves);
-#define MCQ_LOSS_CASE(KK)                                                                                             \
-    case KK: hipLaunchKernelGGL((k_loss_fwd<KK>), grid, block, 0, st, logits, idx, B, N, rpc, lse, pp, pc, ph); break;
-    switch (K) {
-        MCQ_LOSS_CASE(16) MCQ_LOSS_CASE(32) MCQ_LOSS_CASE(64) MCQ_LOSS_CASE(128) MCQ_LOSS_CASE(256)
-        default: return MCQ_EUNSUPPORTED;
-    }
-#undef MCQ_LOSS_CASE
-    MCQ_LAUNCH_CHECK();
+    const int rc = pick<16, 32, 64, 128, 256>(K, [&](auto kk) {
+        constexpr int KK = kk;
+        hipLaunchKernelGGL((k_loss_fwd<KK>), grid, block, 0, st, logits, idx, B, N, rpc, lse, pp, pc, ph);
+        return counted_launch_rc();
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(k_loss_reduce, dim3((unsigned)N), dim3(256), 0, st, pp, pc, ph, chunks, N, K, prob_sum, count,
                        chosen_sum);
     return counted_launch_rc();
@@ -1711,13 +1702,7 @@ int mcq_search_scan_masked(const float *tables, long Q, const uint8_t *codes, co
         if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
         ws_s = static_cast<float *>(workspace);
         ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
-        int rc = MCQ_EUNSUPPORTED;
-        switch (metric) {
-            case MCQ_SEARCH_L2: rc = launch_scan_qt<kMetricL2>(p, st, tables, (int)Q, codes, w, B, N, K, k, ws_s, ws_i, mask); break;
-            case MCQ_SEARCH_IP: rc = launch_scan_qt<kMetricIP>(p, st, tables, (int)Q, codes, nullptr, B, N, K, k, ws_s, ws_i, mask); break;
-            case MCQ_SEARCH_COS: rc = launch_scan_qt<kMetricCos>(p, st, tables, (int)Q, codes, w, B, N, K, k, ws_s, ws_i, mask); break;
-        }
-        if (rc != 0) return rc;
+        if (const int rc = launch_scan(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, ws_s, ws_i, mask)) return rc;
     }
     hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, p.slices, k, out_score, out_index);
     return launch_rc();
@@ -1746,7 +1731,7 @@ int mcq_search_range_count_masked(const float *tables, long Q, const uint8_t *co
         int64_t *ws = static_cast<int64_t *>(workspace);
         const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr, ws, nullptr,
                           nullptr, nullptr, 0, mask};
-        if (const int rc = launch_range_qt<false>(p, st, a)) return rc;
+        if (const int rc = launch_range<false>(p, st, a)) return rc;
         hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)Q), dim3(64), 0, st, ws, p.slices * kRangeWaves, lims);
         if (const int rc = launch_rc()) return rc;
     }
@@ -1771,7 +1756,7 @@ int mcq_search_range_fill_masked(const float *tables, long Q, const uint8_t *cod
     const RangePlan p = range_plan(Q, B, N, K);
     const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
                       static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity, mask};
-    return launch_range_qt<true>(p, static_cast<hipStream_t>(stream), a);
+    return launch_range<true>(p, static_cast<hipStream_t>(stream), a);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector
@@ -1791,18 +1776,17 @@ int mcq_last_encode_launches(void) { return g_last_launches; }
 int mcq_test_select(const float *scores, int cases, int per_lane, int cnt, float *out_v, int *out_p, void *stream) {
     if (!scores || !out_v || !out_p || cases <= 0 || cnt < 1 || cnt > 64) return MCQ_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (per_lane) {
-        case 1: hipLaunchKernelGGL((k_test_select<1>), dim3(cases), dim3(64), 0, st, scores, cnt, out_v, out_p); break;
-        case 4: hipLaunchKernelGGL((k_test_select<4>), dim3(cases), dim3(64), 0, st, scores, cnt, out_v, out_p); break;
-        case 16: hipLaunchKernelGGL((k_test_select<16>), dim3(cases), dim3(64), 0, st, scores, cnt, out_v, out_p); break;
-        // (negative: the same number of keys per lane in the slot-major layout, key i of a lane at position 64 * i + lane; the third
-        // layout, positions in any order, is the general form followed by a rank by position)
-        case -4: hipLaunchKernelGGL((k_test_select<4, kSlotMajor>), dim3(cases), dim3(64), 0, st, scores, cnt, out_v, out_p); break;
-        case -16: hipLaunchKernelGGL((k_test_select<16, kSlotMajor>), dim3(cases), dim3(64), 0, st, scores, cnt, out_v, out_p); break;
-        case -1004: hipLaunchKernelGGL((k_test_select<4, kAnyOrder>), dim3(cases), dim3(64), 0, st, scores, cnt, out_v, out_p); break;
-        default: return MCQ_EINVAL;
-    }
-    return launch_rc();
+    // per_lane < 0: the same number of keys per lane in the slot-major layout, key i of a lane at position 64 * i + lane; -1004:
+    // four keys per lane, positions in any order (the general form followed by a rank by position)
+    static constexpr Pair kShapes[] = {{1, kLaneMajor}, {4, kLaneMajor}, {16, kLaneMajor}, {4, kSlotMajor}, {16, kSlotMajor}, {4, kAnyOrder}};
+    const int vpl = per_lane == -1004 ? 4 : (per_lane < 0 ? -per_lane : per_lane);
+    const int layout = per_lane == -1004 ? kAnyOrder : (per_lane < 0 ? kSlotMajor : kLaneMajor);
+    const int rc = pick_pair<kShapes>(vpl, layout, [&](auto v, auto l) {
+        constexpr int VPL = v, LAYOUT = l;
+        hipLaunchKernelGGL((k_test_select<VPL, LAYOUT>), dim3(cases), dim3(64), 0, st, scores, cnt, out_v, out_p);
+        return launch_rc();
+    });
+    return rc == MCQ_EUNSUPPORTED ? MCQ_EINVAL : rc;
 }
 
 #ifdef MCQ_STAMPS
