@@ -415,6 +415,44 @@ int mcq_search_range_fill_masked(const float *tables, long Q, const uint8_t *cod
                                  int metric, const uint64_t *mask, const float *thr, const int64_t *lims, float *out_score,
                                  int64_t *out_index, long capacity, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- search list by list: an inverted file over the store ---------------------------
+ * Every call above is a scan: each query meets each stored vector.  An inverted file keeps the store IN LIST ORDER by a coarse
+ * partition, and a query is scored against the few lists it probes and no others.  The candidate sets differ per query,
+ * which the one mask of rules 10-12 cannot say.  The contract continues (the tests restate rules 13-15 in numpy and compare
+ * bit for bit):
+ *  13. the store is in list order.  list_offsets is int64[L + 1] in device memory, non-decreasing, with
+ *      0 <= list_offsets[0] and list_offsets[L] <= B.  List l is the positions [list_offsets[l], list_offsets[l + 1]); an empty
+ *      list is legal, and positions outside every list belong to none.  probes is int32[Q][P] in device memory: an entry in
+ *      [0, L) names a list, any other value names none (-1 is the documented padding).  The CANDIDATES of query q are the
+ *      union of the lists its row names.  A row holds distinct list numbers; a repeated number leaves that query's row of
+ *      results unspecified (it may list a position twice) and neither faults nor hangs.
+ *  14. rules 3, 3' and 4 hold as they stand over a query's candidates.  The score of a candidate is the same bits as in
+ *      mcq_search_scan_metric; the order is (score, b) ascending with b the position in the store, and positions in the
+ *      store are reported; fewer than k candidates (none included): the tail is (+inf, -1).  So row q equals, bit for bit,
+ *      row 0 of mcq_search_scan_masked called with that one query and a mask whose set bits are the union of its probed
+ *      lists; and with every list probed and the lists covering [0, B) it equals row q of mcq_search_scan_metric, whatever
+ *      the order of the probes in the row.
+ *  15. mask != NULL (rule 10's words): b is a candidate iff it lies in a probed list AND its bit is set.  Lists do not start
+ *      at multiples of 64, so every lane tests its own bit; that steps without a candidate are skipped is not promised here.
+ *      mask == NULL reads no mask.
+ *  16. limits and the order of the checks; everything is checked before anything touches the device.  First the limits of
+ *      mcq_search_scan_masked with its status codes: one-byte codes (K <= 256), N a power of two <= 64, 1 <= k <= 64,
+ *      B <= 2^31 - 1, an unknown metric.  Then P < 0 or L < 0: MCQ_EINVAL; P > 4096: MCQ_EUNSUPPORTED (a query's per-probe
+ *      step counts and their prefix sums live in on-chip memory beside its tables).  Q == 0 returns 0 and looks at no input.
+ *      B == 0, L == 0 or P == 0 return 0 after filling the outputs with (+inf, -1), and look at no other input.  Then the
+ *      pointers: tables, codes, workspace, list_offsets, probes non-NULL, w == NULL only under MCQ_SEARCH_IP, codes aligned
+ *      to min(N, 16) bytes, mask and list_offsets to 8, probes to 4 (MCQ_EINVAL); last a short workspace, MCQ_EWORKSPACE.
+ *      The workspace holds partial lists only, k entries per (query, part of its candidates): its size is a function of
+ *      (Q, P, N, K, k) and depends on neither B nor L, and not on D.  The call reads nothing back from the device and does
+ *      not synchronise: the offsets are read by the kernel, never by the host.
+ * Defence, not contract: the kernel clamps every list's range to [0, B] and treats begin >= end as empty, so offsets that
+ * break rule 13 give wrong answers but can never make a load go out of bounds (as a cleared bit cannot under rule 12).      */
+size_t mcq_search_lists_workspace_bytes(long Q, int P, int N, int K, int k);
+int mcq_search_scan_lists(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
+                          int metric, const uint64_t *mask /* may be NULL */,
+                          const int64_t *list_offsets, long L, const int32_t *probes, int P,
+                          float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- test / profiling hooks -------------------------------------------------
  * Logits of Quantizer._logits (:277-279) for a batch, fp32 [B][N*K]; used by the
  * parity tests to localise a divergence.                                       */

@@ -25,6 +25,7 @@ SYMBOLS = (
     "mcq_search_scan_metric", "mcq_code_rnorms", "mcq_rnorms_from_norms",
     "mcq_search_range_workspace_bytes", "mcq_search_range_count", "mcq_search_range_fill",
     "mcq_search_pack_mask", "mcq_search_scan_masked", "mcq_search_range_count_masked", "mcq_search_range_fill_masked",
+    "mcq_search_lists_workspace_bytes", "mcq_search_scan_lists",
 )
 
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
@@ -161,6 +162,12 @@ def lib():
         L.mcq_search_range_count_masked.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, sz, vp]
         L.mcq_search_range_fill_masked.restype = i32
         L.mcq_search_range_fill_masked.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, sz, vp]
+    # (and the search list by list: an older build scans the whole store as before, and calling search_lists raises)
+    if not (_ALT and not hasattr(L, "mcq_search_scan_lists")):
+        L.mcq_search_lists_workspace_bytes.restype = sz
+        L.mcq_search_lists_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
+        L.mcq_search_scan_lists.restype = i32
+        L.mcq_search_scan_lists.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, vp, i64, vp, i32, vp, vp, vp, sz, vp]
     L.mcq_last_encode_launches.restype = i32
     L.mcq_profile_encode.restype = i32
     L.mcq_profile_encode.argtypes = [vp, i64, vp, f32, i32, i32, i32, i32, vp, sz, vp, ctypes.POINTER(f32), ctypes.POINTER(i32), i32]

@@ -1013,6 +1013,44 @@ int launch_scan(const ScanPlan &p, hipStream_t st, const float *tables, int Q, c
     });
 }
 
+// the search list by list (rules 13-16; mirrored by lists_plan of tests/search_lists_grid.py): one query per workgroup and
+// `parts` parts of each query's candidates -- as many as fill the chip once at small Q, capped as the slice count is.  A
+// function of the call's shape alone: the lists' lengths are known to the device only (nothing is read back).
+struct ListsPlan {
+    int parts;
+    size_t lds, ws_half;
+};
+
+ListsPlan lists_plan(long Q, int P, int N, int K, int k) {
+    ListsPlan p;
+    long parts = kListTargetBlocks / (Q > 0 ? Q : 1);
+    p.parts = (int)(parts < 1 ? 1 : (parts > kScanMaxSlices ? kScanMaxSlices : parts));
+    p.lds = (size_t)lists_lds_bytes(N * K, P);
+    p.ws_half = align256((size_t)Q * p.parts * k * 4);                   // scores, then positions
+    return p;
+}
+
+int launch_lists(const ListsPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
+                 int N, int K, int k, int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes,
+                 int P, float *ws_s, int *ws_i) {
+    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
+            return pick_bool(mask != nullptr, [&](auto masked) {
+                constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
+                constexpr bool MASKED = masked;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_lists<NN, M, MASKED>),
+                                                     lists_lds_bytes(64 * 256, kListMaxProbes)))
+                    return rc;
+                hipLaunchKernelGGL((k_search_lists<NN, M, MASKED>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kListWaves), p.lds,
+                                   st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, list_offsets, L, probes, P,
+                                   ws_s, ws_i, reinterpret_cast<const u64 *>(mask));
+                return launch_rc();
+            });
+        });
+    });
+}
+
 }  // namespace
 
 
@@ -1705,6 +1743,45 @@ int mcq_search_scan_masked(const float *tables, long Q, const uint8_t *codes, co
         if (const int rc = launch_scan(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, ws_s, ws_i, mask)) return rc;
     }
     hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, p.slices, k, out_score, out_index);
+    return launch_rc();
+}
+
+// rules 13-16: the search list by list.  The size depends on neither B nor L: the parts of a query are cut on the device.
+size_t mcq_search_lists_workspace_bytes(long Q, int P, int N, int K, int k) {
+    if (Q <= 0 || P <= 0 || P > kListMaxProbes || k < 1 || k > 64 || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
+    return 2 * lists_plan(Q, P, N, K, k).ws_half;
+}
+
+int mcq_search_scan_lists(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
+                          int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes, int P,
+                          float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
+    // the checks of search_check in its order, with rule 16's own between the limits and the pointers
+    if (const int rc = search_domain(N, K, 1)) return rc;
+    if (k > 64) return MCQ_EUNSUPPORTED;
+    if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
+    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (P < 0 || L < 0) return MCQ_EINVAL;
+    if (P > kListMaxProbes) return MCQ_EUNSUPPORTED;
+    if (Q == 0) return 0;
+    if (!out_score || !out_index) return MCQ_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (B == 0 || L == 0 || P == 0) {                                      // no candidate anywhere: the fill of rule 4
+        hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, nullptr, nullptr, 0, k, out_score, out_index);
+        return launch_rc();
+    }
+    if (!tables || !codes || !workspace || !list_offsets || !probes) return MCQ_EINVAL;
+    if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;
+    const int need = N >= 16 ? 16 : N;
+    if (reinterpret_cast<uintptr_t>(codes) % need != 0 || reinterpret_cast<uintptr_t>(mask) % 8 != 0) return MCQ_EINVAL;
+    if (reinterpret_cast<uintptr_t>(list_offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(probes) % 4 != 0) return MCQ_EINVAL;
+    const ListsPlan p = lists_plan(Q, P, N, K, k);
+    if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
+    float *ws_s = static_cast<float *>(workspace);
+    int *ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
+    if (const int rc = launch_lists(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, list_offsets, L, probes, P, ws_s, ws_i))
+        return rc;
+    hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, p.parts, k, out_score, out_index);
     return launch_rc();
 }
 

@@ -26,6 +26,8 @@
 //      at multiples of 64), so a wave learns from one wave-uniform word that a step is empty and skips it whole: no code
 //      load, no gather, no list insert (MaskWalk below).  Behind a cleared bit of a step that is not empty the codes and w are
 //      loaded as always (in bounds: step_at) and the score, whatever it is, is never offered.
+//  13-15. k_search_lists: the candidates of a query are the lists its row of probes names (and, under a mask, whose bit is set);
+//      scores, order and tails are those above over these candidates, positions staying those of the store.
 #pragma once
 #include "mcq_kernels.h"
 #include <hip/hip_fp16.h>
@@ -452,6 +454,178 @@ k_search_merge(const float *__restrict__ ws_s, const int *__restrict__ ws_i, int
     if (lane < k) {
         out_s[(long)q * k + lane] = ms;
         out_i[(long)q * k + lane] = (mi == kNoIndex) ? (int64_t)-1 : (int64_t)mi;
+    }
+}
+
+// -------------------------------------------------------------------- lists
+// The search list by list (rules 13-16): the store is in list order, list l is [list_offsets[l], list_offsets[l + 1]), and
+// query q is scored against the lists its row of `probes` names and no others.  The candidate sets differ per query, so a
+// code is no longer shared by the queries of a tile: a workgroup is ONE query (QT = 1) and part s of S of ITS candidates.
+//   * step space: per probe the range clamped to [0, B] (begin >= end, and a probe outside [0, L), are empty) and its steps
+//     of 64 candidates, ceil(len / 64); an exclusive prefix sum over the probes flattens them into T steps.  Part s owns
+//     the steps [s*T/S, (s+1)*T/S): the candidates are cut by COUNT, whichever lists they sit in (a cut by position leaves
+//     one part all the work when the candidates are one run).  A part's waves take its steps in turn.
+//   * a step is (probe p, offset j in its list) with pre[p] <= step < pre[p + 1]: found once per wave by bisection, then by
+//     a pointer that walks up (the steps of a wave ascend).  The lane's candidate is begin + 64*j + lane, lanes past the
+//     list's end re-read its last candidate and offer nothing (step_at over the list as a Slice).
+//   * the score is tile_step<1, CH, N> + score_finish, as everywhere; the next step's candidate, across a list boundary too,
+//     is the bnext of tile_step, so codes and w still travel one step ahead.  Under a mask each lane tests its own bit.
+//   * the waves' lists are merged through LDS as in k_search_scan and leave as list (q, s) of the workspace: k_search_merge
+//     finishes the call.  No atomics of any kind.
+// LDS: [the table, N*K floats; later the waves' lists][pre: int64 P + 1][begin: int32 P][end: int32 P].
+constexpr int kListWaves = 4;             // k_search_lists: waves per workgroup (256 threads)
+constexpr int kListTargetBlocks = 1024;   //                 workgroups that fill the chip once (4 per CU, 4 waves per SIMD)
+// probes per query at most.  A query's per-probe ranges and prefix sums take 16 bytes per probe (8 + 4 + 4) and live in LDS
+// beside up to 64 KiB of tables (N*K = 64 * 256 floats): 64 KiB + 4096 * 16 B + 8 B = 128 KiB + 8 B of the CU's 160 KiB.
+// Twice as many probes would need 192 KiB.
+constexpr int kListMaxProbes = 4096;
+
+// bytes of the first LDS region: the table, and after the scoring the kListWaves lists of 64 (score, position) pairs
+__host__ __device__ constexpr int lists_lds_head(int NK) {
+    return ((NK * 4 > kListWaves * 64 * 8 ? NK * 4 : kListWaves * 64 * 8) + 15) & ~15;
+}
+__host__ __device__ constexpr int lists_lds_bytes(int NK, int P) { return lists_lds_head(NK) + (P + 1) * 8 + P * 8; }
+
+// the (probe, list) of a step: p walks up until pre[p] <= step < pre[p + 1] (step < pre[P]; probes without a step are passed)
+struct ListWalk {
+    const long long *pre;
+    const int *lbeg, *lend;
+    int P, p;
+    __device__ __forceinline__ Slice at(long long step, long &j) {
+        while (p + 1 < P && pre[p + 1] <= step) ++p;
+        j = (long)(step - pre[p]);
+        return {lbeg[p], lend[p], 0};
+    }
+};
+
+template <int N, int M, bool MASKED>
+__global__ void __launch_bounds__(64 * kListWaves)
+k_search_lists(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w,
+               long B, int K, int k, int S, const int64_t *__restrict__ list_offsets, long L, const int *__restrict__ probes,
+               int P, float *__restrict__ ws_s, int *__restrict__ ws_i, const u64 *__restrict__ mask) {
+    extern __shared__ __attribute__((aligned(16))) char search_smem[];
+    constexpr int CH = N < 8 ? N : 8;
+    constexpr int THREADS = 64 * kListWaves;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x / S, part = blockIdx.x % S;
+    long long *pre = reinterpret_cast<long long *>(search_smem + lists_lds_head(N * K));
+    int *lbeg = reinterpret_cast<int *>(pre + P + 1);
+    int *lend = lbeg + P;
+
+    // the query's step space: clamped ranges and step counts, then the prefix sums in chunks of 64 through wave 0
+    for (int e = tid; e < P; e += THREADS) {
+        const int l = probes[(long)q * P + e];
+        long a = 0, z = 0;
+        if (l >= 0 && l < L) {
+            a = list_offsets[l];
+            z = list_offsets[l + 1];
+            a = a < 0 ? 0 : (a > B ? B : a);                 // (defence: a range never leaves [0, B], whatever the offsets hold)
+            z = z < 0 ? 0 : (z > B ? B : z);
+            if (a >= z) a = z = 0;
+        }
+        lbeg[e] = (int)a;
+        lend[e] = (int)z;
+        pre[e + 1] = (z - a + 63) / 64;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        long long carry = 0;
+        for (int c0 = 0; c0 < P; c0 += 64) {
+            const int e = c0 + lane;
+            long long v = e < P ? pre[e + 1] : 0;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const long long u = __shfl_up(v, d, 64);
+                if (lane >= d) v += u;
+            }
+            v += carry;
+            if (e < P) pre[e + 1] = v;
+            carry = __shfl(v, 63, 64);
+        }
+        if (lane == 0) pre[0] = 0;
+    }
+    __syncthreads();
+    const long long T = pre[P];
+    const long long lo = T * part / S, hi = T * (part + 1) / S;           // (T <= 2^37, S <= 256)
+    if (lo >= hi) {                                          // no step: the empty list, and nothing is staged
+        if (tid < k) {
+            const long at = ((long)q * S + part) * k + tid;
+            ws_s[at] = __builtin_inff();
+            ws_i[at] = kNoIndex;
+        }
+        return;
+    }
+    tile_stage<1, THREADS>(reinterpret_cast<float *>(search_smem), tables, Q, q, N * K, tid);
+    const float *Tl = reinterpret_cast<const float *>(search_smem);
+
+    float ls = __builtin_inff(), ts = __builtin_inff();
+    int li = kNoIndex, tb = kNoIndex;
+    CodeChunk<CH> cur;
+    float t = 0.f;
+    long long step = lo + wave;
+    ListWalk walk{pre, lbeg, lend, P, 0};
+    Slice sl{0, 1, 0};
+    long j = 0;
+    if (step < hi) {
+        int a = 0, z = P;                                    // pre[a] <= step < pre[z]
+        while (z - a > 1) {
+            const int mid = (a + z) >> 1;
+            if (pre[mid] <= step) a = mid; else z = mid;
+        }
+        walk.p = a;
+        sl = walk.at(step, j);
+    }
+    tile_first(cur, t, codes, w, M, N, sl, j, step < hi ? j + 1 : j, lane);
+    long b = step_at(sl, j, lane);
+    bool live = sl.begin + j * 64 + lane < sl.end;
+    u64 word = 0;
+    if constexpr (MASKED) {
+        if (step < hi) word = mask[b >> 6];
+    }
+    while (step < hi) {
+        const long long nstep = step + kListWaves;
+        long bnext = b;
+        bool live_next = false;
+        if (nstep < hi) {
+            sl = walk.at(nstep, j);
+            bnext = step_at(sl, j, lane);
+            live_next = sl.begin + j * 64 + lane < sl.end;
+        }
+        u64 word_next = 0;
+        if constexpr (MASKED) word_next = mask[bnext >> 6];
+        float tn = t;
+        float acc[1];
+        tile_step<1, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, b, bnext);
+        bool offer = live;
+        if constexpr (MASKED) offer = live && ((word >> (b & 63)) & 1);
+        list_insert(ls, li, ts, tb, score_finish(acc[0], t, M), (int)b, offer, k, lane);
+        t = tn;
+        b = bnext;
+        live = live_next;
+        word = word_next;
+        step = nstep;
+    }
+
+    // the waves' lists -> LDS -> the list of (query, part)
+    __syncthreads();
+    float *Ls = reinterpret_cast<float *>(search_smem);
+    int *Li = reinterpret_cast<int *>(search_smem + (size_t)kListWaves * 64 * 4);
+    Ls[wave * 64 + lane] = ls;
+    Li[wave * 64 + lane] = li;
+    __syncthreads();
+    if (wave == 0) {
+        float ms = __builtin_inff(), mts = __builtin_inff();
+        int mi = kNoIndex, mtb = kNoIndex;
+        for (int v = 0; v < kListWaves; ++v) {
+            const float s = Ls[v * 64 + lane];
+            const int c = Li[v * 64 + lane];
+            list_insert(ms, mi, mts, mtb, s, c, lane < k && c != kNoIndex, k, lane);
+        }
+        if (lane < k) {
+            const long at = ((long)q * S + part) * k + lane;
+            ws_s[at] = ms;
+            ws_i[at] = mi;
+        }
     }
 }
 

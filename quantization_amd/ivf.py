@@ -1,0 +1,59 @@
+"""An inverted file over a store of codes: the torch plumbing round Quantizer.search_lists (no hot path; the scoring is
+mcq_search_scan_lists).
+
+    order, list_offsets = build_lists(assign, num_lists)       # once per store: assign[b] = the coarse cell of vector b
+    codes, norms = codes[order], norms[order]                  # the store in list order
+    probes = probe_lists(queries, centroids, nprobe)           # per call: the nprobe nearest cells of each query
+    dist, idx = quantizer.search_lists(queries, codes, list_offsets, probes, k=10, norms=norms)
+    original = torch.where(idx >= 0, order[idx.clamp(min=0)], idx)
+
+Where the coarse centroids come from (k-means over a sample, a trained layer) is the caller's business."""
+import torch
+from torch import Tensor
+
+__all__ = ["build_lists", "probe_lists"]
+
+
+def build_lists(assign: Tensor, num_lists: int):
+    """assign (B,) integer, assign[b] in [0, num_lists) -> (order int64 (B,), list_offsets int64 (num_lists + 1,)).
+    order is the STABLE sort of the assignments: list l is order[list_offsets[l]:list_offsets[l + 1]], in ascending original
+    position.  The caller stores codes[order] (and norms[order], and a packed mask of keep[order]) and maps a result back
+    through order."""
+    if not isinstance(assign, Tensor) or assign.ndim != 1 or assign.dtype.is_floating_point or assign.dtype == torch.bool:
+        raise ValueError(f"assign: an integer (B,) tensor, not {getattr(assign, 'dtype', type(assign))} "
+                         f"{tuple(getattr(assign, 'shape', ()))}")
+    num_lists = int(num_lists)
+    if num_lists < 0 or (assign.numel() and num_lists == 0):
+        raise ValueError(f"{num_lists} lists for {assign.numel()} vectors")
+    a = assign.detach().to(torch.int64)
+    if a.numel() and (int(a.min()) < 0 or int(a.max()) >= num_lists):
+        raise ValueError(f"assign holds values outside [0, {num_lists})")
+    order = torch.sort(a, stable=True).indices
+    counts = torch.bincount(a, minlength=num_lists)
+    offsets = torch.zeros(num_lists + 1, dtype=torch.int64, device=a.device)
+    offsets[1:] = torch.cumsum(counts, dim=0)
+    return order, offsets
+
+
+def probe_lists(queries: Tensor, centroids: Tensor, nprobe: int, metric: str = "l2") -> Tensor:
+    """queries (*, dim), centroids (L, dim) -> int32 (*, nprobe): per query the nprobe best lists, best first -- the nearest
+    centroids under "l2", the largest inner products under "ip", the largest cosines under "cosine".  One matmul and one
+    topk; the rows hold distinct lists by construction."""
+    if metric not in ("l2", "ip", "cosine"):
+        raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
+    if not isinstance(centroids, Tensor) or centroids.ndim != 2 or queries.shape[-1] != centroids.shape[1]:
+        raise ValueError(f"centroids: an (L, {queries.shape[-1]}) tensor, not {tuple(getattr(centroids, 'shape', ()))}")
+    nprobe = int(nprobe)
+    if not 1 <= nprobe <= centroids.shape[0]:
+        raise ValueError(f"nprobe {nprobe} for {centroids.shape[0]} lists")
+    with torch.no_grad():
+        q = queries.detach().reshape(-1, queries.shape[-1]).to(torch.float32)
+        c = centroids.detach().to(torch.float32)
+        sim = q @ c.t()
+        if metric == "l2":                                  # |q - c|^2 = |q|^2 - 2 <q, c> + |c|^2: |q|^2 does not order the lists
+            sim = sim - 0.5 * (c * c).sum(dim=1)[None, :]
+        elif metric == "cosine":
+            cn = (c * c).sum(dim=1).sqrt()
+            sim = sim / cn.masked_fill(cn == 0, 1.0)[None, :]
+        top = torch.topk(sim, nprobe, dim=1).indices.to(torch.int32)
+    return top.reshape(*queries.shape[:-1], nprobe)

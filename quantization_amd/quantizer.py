@@ -617,6 +617,34 @@ class Quantizer(nn.Module):
             return None if mask is None else mask.detach().contiguous()
         return self.pack_mask(mask)
 
+    @staticmethod
+    def _check_lists(lists, Q: int) -> None:
+        """what search_lists accepts as (list_offsets, probes) for Q queries: int64 (L + 1,) and int32 or int64 (Q, P).  Looks
+        at shape and dtype only, so it runs before any device work."""
+        if lists is None:
+            return
+        offsets, probes = lists
+        if not isinstance(offsets, Tensor) or offsets.dtype != torch.int64 or offsets.ndim != 1 or offsets.numel() < 1:
+            raise ValueError(f"list_offsets: an int64 (L + 1,) tensor, not {getattr(offsets, 'dtype', type(offsets))} "
+                             f"{tuple(getattr(offsets, 'shape', ()))}")
+        if not isinstance(probes, Tensor) or probes.dtype not in (torch.int32, torch.int64) or probes.ndim < 1:
+            raise ValueError(f"probes: an int32 or int64 (*, P) tensor, not {getattr(probes, 'dtype', type(probes))} "
+                             f"{tuple(getattr(probes, 'shape', ()))}")
+        rows = torch.Size(probes.shape[:-1]).numel()                   # (a (P,) tensor is the one row of one query)
+        if rows != Q:
+            raise ValueError(f"probes of {rows} rows for {Q} queries")
+
+    @staticmethod
+    def _list_arrays(offsets: Tensor, probes: Tensor):
+        """(list_offsets, probes) that passed _check_lists and sit on the device -> (int64 (L + 1,), int32 (Q, P)) as the
+        library reads them; an int64 entry that names no list becomes -1 before it is narrowed"""
+        offsets = offsets.detach().contiguous()
+        probes = probes.detach().reshape(torch.Size(probes.shape[:-1]).numel(), probes.shape[-1])
+        if probes.dtype == torch.int64:
+            named = (probes >= 0) & (probes < offsets.numel() - 1)
+            probes = torch.where(named, probes, torch.full_like(probes, -1)).to(torch.int32)
+        return offsets, probes.contiguous()
+
     def _metric_array(self, metric: str, flat: Tensor, norms, rnorms):
         """the per-candidate array of a metric, from what the caller handed in or else from the codes: norms (l2), none (ip),
         reciprocal roots (cosine: rnorms, or norms converted on the device, or code_rnorms)"""
@@ -628,23 +656,41 @@ class Quantizer(nn.Module):
             return rnorms.reshape(-1)
         return self.code_rnorms(flat) if norms is None else self.rnorms_from_norms(norms)
 
-    def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int, metric: str = "l2", mask: Tensor = None):
+    def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int, metric: str = "l2", mask: Tensor = None,
+                     lists=None):
         """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, norms fp32 (B,) -> (scores fp32 (Q, k), indexes int64 (Q, k)):
         the k smallest score[q][b] = sum_n tables[q][n][codes[b][n]] + norms[b] under (score, b) ascending (mcq_search_scan).
         metric "ip": the score is the sum alone and `norms` is not looked at (None will do); "cosine": `norms` holds the
         reciprocal roots (code_rnorms) and the score is the sum times norms[b] (mcq_search_scan_metric).
         mask: bool (B,) or the words of pack_mask: the k smallest among the positions whose bit is set
-        (mcq_search_scan_masked); None calls what it called before masks existed."""
+        (mcq_search_scan_masked); None calls what it called before masks existed.
+        lists: (list_offsets int64 (L + 1,), probes (Q, P) int32 or int64) as search_lists takes them: the k smallest among
+        the positions of the lists row q of `probes` names, under the mask if there is one (mcq_search_scan_lists)."""
         N, K = self.num_codebooks, self.codebook_size
         self._check_mask(mask, codes.shape[0])
-        tables, codes, norms, m, Q, B, dev = self._search_inputs(tables, codes, norms, metric, *(() if mask is None else (mask,)))
+        self._check_lists(lists, tables.shape[0])
+        more = (() if mask is None else (mask,)) + (() if lists is None else tuple(lists))
+        tables, codes, norms, m, Q, B, dev = self._search_inputs(tables, codes, norms, metric, *more)
         L = _lib.lib()
         if mask is not None and not hasattr(L, "mcq_search_scan_masked"):
             raise _lib.McqError(f"{_lib.LIB_PATH} has no masked search (mcq_search_scan_masked)")
+        if lists is not None and not hasattr(L, "mcq_search_scan_lists"):
+            raise _lib.McqError(f"{_lib.LIB_PATH} has no search by lists (mcq_search_scan_lists)")
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
             indexes = torch.empty((Q, k), dtype=torch.int64, device=dev)
+            if lists is not None:
+                offsets, probes = self._list_arrays(*lists)
+                nl, P = offsets.numel() - 1, probes.shape[1]
+                ws = torch.empty(L.mcq_search_lists_workspace_bytes(Q, P, N, K, k), dtype=torch.uint8, device=dev)
+                words = self._mask_words(mask)
+                rc = L.mcq_search_scan_lists(tables.data_ptr(), Q, codes.data_ptr(), None if norms is None else norms.data_ptr(),
+                                             B, N, K, int(k), m, None if words is None else words.data_ptr(), offsets.data_ptr(),
+                                             nl, probes.data_ptr(), P, scores.data_ptr(), indexes.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), st)
+                _lib.check(rc, "mcq_search_scan_lists")
+                return scores, indexes
             ws = torch.empty(L.mcq_search_workspace_bytes(Q, B, N, K, k), dtype=torch.uint8, device=dev)
             entry = "mcq_search_scan" if metric == "l2" else "mcq_search_scan_metric"
             if mask is not None:
@@ -678,28 +724,47 @@ class Quantizer(nn.Module):
         pack_mask made of one (reused across calls); B counts stored vectors, for packed 16-entry codes as well.  Indexes
         stay positions in `codes`, the result is that of a search over codes[mask] mapped back, and with fewer than k kept
         vectors the tail is the short store's.  Nothing is copied: steps of 64 vectors without a kept one are skipped."""
+        return self._search_topk(queries, codes, k, norms, metric, rnorms, mask)
+
+    def search_lists(self, queries: Tensor, codes: Tensor, list_offsets: Tensor, probes: Tensor, k: int = 10,
+                     norms: Tensor = None, metric: str = "l2", rnorms: Tensor = None, mask: Tensor = None):
+        """search() over an inverted file: the store is kept in list order and each query is scored against the lists it
+        probes and no others (quantization_amd.ivf.build_lists orders a store, probe_lists picks the lists).
+        list_offsets int64 (L + 1,): list l is the positions [list_offsets[l], list_offsets[l + 1]) of `codes`; probes (*, P)
+        int32 or int64, one row per query with the leading dimensions of `queries`: an entry in [0, L) names a list, any
+        other value (-1 is the padding) names none, and a row holds distinct lists.
+        Everything else is search()'s: the arguments, the three metrics, the return values, the clamping, the order among
+        equal scores, the tail of a query with fewer than k candidates, and the mask (a stored vector is a candidate iff it
+        lies in a probed list AND the mask keeps it: a delete clears one bit, whatever list the vector sits in).  Indexes
+        are positions in `codes`, that is in list order (map them through build_lists' `order` for the original ones).
+        Row q equals search(queries[q], ..., mask=the union of its lists); the cost falls with the probed share."""
+        return self._search_topk(queries, codes, k, norms, metric, rnorms, mask, (list_offsets, probes))
+
+    def _search_topk(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask, lists=None):
+        """search() and search_lists(): `lists` is None or (list_offsets, probes)"""
         if metric not in self._METRICS:
             raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
         self._check_mask(mask, codes.reshape(-1, codes.shape[-1]).shape[0])
+        self._check_lists(lists, queries.numel() // max(queries.shape[-1], 1))
         if metric != "l2":
-            return self._search_similarity(queries, codes, k, norms, metric, rnorms, mask)
+            return self._search_similarity(queries, codes, k, norms, metric, rnorms, mask, lists)
         with torch.no_grad():
             flat = self._unpacked_codes(codes)
             w = self._metric_array("l2", flat, norms, None)
             tables = self.search_tables(queries)
-            scores, indexes = self._search_scan(tables, flat, w, k, mask=mask)
+            scores, indexes = self._search_scan(tables, flat, w, k, mask=mask, lists=lists)
             q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
             dist = (scores + (q2d * q2d).sum(dim=1, keepdim=True)).clamp_(min=0.0)
         lead = queries.shape[:-1]
         return dist.reshape(*lead, k), indexes.reshape(*lead, k)
 
-    def _search_similarity(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask=None):
+    def _search_similarity(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask=None, lists=None):
         """search() under "ip" and "cosine": the scan's scores are -2 <q, x^> and -2 |q| cos; halving is exact"""
         with torch.no_grad():
             flat = self._unpacked_codes(codes)
             w = self._metric_array(metric, flat, norms, rnorms)
             tables = self.search_tables(queries)
-            scores, indexes = self._search_scan(tables, flat, w, k, metric=metric, mask=mask)
+            scores, indexes = self._search_scan(tables, flat, w, k, metric=metric, mask=mask, lists=lists)
             sim = scores * -0.5
             if metric == "cosine":
                 q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
