@@ -34,6 +34,23 @@ k_tf_er<N, CT> at N * K > 4096 other than the two added cells, k_tf_comb<32, 32,
 
 Decode: the nine (N, J) shapes of k_decode_reg (kDecRegShapes; J = float4s per lane of a row of round_up16(D) floats) at 5
 vectors of one-byte codes, bit for bit against the oracle: dim 20 -> J = 1, dim 300 -> J = 2, dim 1000 -> J = 4.
+
+The other decode dispatchers (the cells are the tables of tests/search_selection_grid.py, which tests/test_search_selection_host.py
+checks against the pick<...> lists of the source), all bit for bit against the oracle:
+
+  launch_decode_sliced   k_decode_sliced<T, CH, LPV>: N = 1, 2, 4 (CH 4; 1 and 2 run the `n0 + j < N` tail inside a chunk), 8 (CH 8),
+                         16, 32, 64 (CH 16; 32 and 64 run several chunks) x dims 100, 200, 300, 1,000, 1,100 (LPV 4, 8, 16, 32, 64;
+                         none a multiple of 16: a last slice reaches into the padding), K = 32, 4,099 vectors, uint8 and int64 codes
+  launch_decode_blk      k_decode_blk<4, 2>: 4 x 1,024, <8, 2>: 8 x 512 -- one-byte codes given to a quantizer of wide codebooks
+                         (decode accepts any integer dtype and passes bytes through), 4,355 vectors of dim 72 under
+                         MCQ_DECODE_LDS_MIN=4096 (read per call), and the same call under MCQ_DECODE_BLK=0.  The other four
+                         cells, <4, 4>, <8, 4>, <16, 4> and <16, 2>, are cases of tests/test_gpu_parity.py.
+  k_decode<T>            packed digits, 16 x 16: int64 codes of rep = 2, 4, 8 and 16 digits (the top digit below 8: 16^16 does not
+                         fit an int64) and uint8 codes of 2, packed least significant digit first, 5 vectors at dim 20 and 300
+
+Reachable, but not from the cells above: k_decode_lds<T> (batches from 16,384 vectors whose 64-byte slices fit the LDS, other
+than the block-staged shapes) and the whole-block path of k_decode_blk (a workgroup with at least 16,384 / N vectors);
+tests/test_gpu_parity.py runs both.
 """
 import os
 import subprocess
@@ -43,6 +60,7 @@ import numpy as np
 import pytest
 import torch
 
+import search_selection_grid as ss
 from golden import gen
 from test_gpu_parity import load_quantizer, oracle_of
 
@@ -109,3 +127,68 @@ def test_decode_reg_shape_vs_oracle(N, J):
     with torch.no_grad():
         got = q.decode(torch.from_numpy(codes).cuda()).cpu().numpy()
     assert np.array_equal(got, oracle_of(sd).decode(codes))
+
+
+@pytest.mark.parametrize("dim", sorted(ss.SLICED_DIMS))
+@pytest.mark.parametrize("N", ss.SLICED_NS)
+def test_decode_sliced_cell_vs_oracle(N, dim):
+    K, B, lpv = ss.SLICED_K, ss.SLICED_B, ss.SLICED_DIMS[dim]
+    Dp = (dim + 15) // 16 * 16
+    assert ss.decode_sliced_lpv(dim) == lpv and 8 * lpv * 4 >= Dp and (lpv == 4 or 8 * (lpv // 2) * 4 < Dp) and dim % 16
+    sd = gen.synthetic_state(1900 + 10 * N + lpv, dim, K, N)
+    q = load_quantizer(sd, dim, K, N)
+    codes = np.random.RandomState(1901 + 10 * N + lpv).randint(0, K, size=(B, N)).astype(np.uint8)
+    want = oracle_of(sd).decode(codes)
+    with torch.no_grad():
+        got8 = q.decode(torch.from_numpy(codes).cuda())
+        got64 = q.decode(torch.from_numpy(codes.astype(np.int64)).cuda())
+    assert got8.dtype == torch.float32 and tuple(got8.shape) == (B, dim)
+    assert np.array_equal(got8.cpu().numpy().view(np.uint32), want.view(np.uint32)), f"{N} x {K}, dim {dim}: uint8 codes differ from the oracle"
+    assert np.array_equal(got64.cpu().numpy().view(np.uint32), want.view(np.uint32)), f"{N} x {K}, dim {dim}: int64 codes differ from the oracle"
+    assert torch.equal(got8, got64)
+
+
+def _with_env(name, value, f):
+    """f() under a per-call hook of the library, the hook restored afterwards"""
+    old = os.environ.get(name)
+    os.environ[name] = value
+    try:
+        return f()
+    finally:
+        os.environ.pop(name, None)
+        if old is not None:
+            os.environ[name] = old
+
+
+@pytest.mark.parametrize("N,K", sorted(ss.BLK_CELLS))
+def test_decode_blk_narrow_slices_of_wide_codebooks_vs_oracle(N, K):
+    B, dim = ss.BLK_B, ss.BLK_D
+    assert ss.BLK_CELLS[(N, K)] == (N, 2) and ss.decode_blk_lpv(N, K) == 2 and B >= ss.BLK_LDS_MIN and dim % 4 == 0
+    sd = gen.synthetic_state(2100 + N, dim, K, N)
+    q = load_quantizer(sd, dim, K, N)
+    codes = np.random.RandomState(2101 + N).randint(0, 256, size=(B, N)).astype(np.uint8)      # indexes below 256 of K entries
+    cd = torch.from_numpy(codes).cuda()
+    want = oracle_of(sd).decode(codes)
+    with torch.no_grad():
+        got = _with_env("MCQ_DECODE_LDS_MIN", str(ss.BLK_LDS_MIN), lambda: q.decode(cd))
+        other = _with_env("MCQ_DECODE_LDS_MIN", str(ss.BLK_LDS_MIN), lambda: _with_env("MCQ_DECODE_BLK", "0", lambda: q.decode(cd)))
+    assert np.array_equal(got.cpu().numpy().view(np.uint32), want.view(np.uint32)), f"{N} x {K}: k_decode_blk differs from the oracle"
+    assert torch.equal(other, got)
+
+
+@pytest.mark.parametrize("dim", ss.PACKED_DIMS)
+def test_decode_of_packed_digits_vs_oracle(dim):
+    N, K, B = ss.PACKED_N, ss.PACKED_K, ss.PACKED_B
+    sd = gen.synthetic_state(2300 + dim, dim, K, N)
+    q = load_quantizer(sd, dim, K, N)
+    idx = np.random.RandomState(2301 + dim).randint(0, K, size=(B, N))
+    idx[:, N - 1] %= 8                                       # the top digit of a code of 16 digits stays below 8
+    idx[0] = K - 1                                           # the largest digits everywhere ...
+    idx[0, N - 1] = 7                                        # ... that still fit
+    want = oracle_of(sd).decode(idx.astype(np.uint8))
+    for rep, dtype in ss.PACKED_REPS:
+        packed = ss.pack_digits(idx, rep, K, np.dtype(dtype))
+        assert packed.shape == (B, N // rep)
+        with torch.no_grad():
+            got = q.decode(torch.from_numpy(packed).cuda())
+        assert np.array_equal(got.cpu().numpy().view(np.uint32), want.view(np.uint32)), f"rep {rep}, {dtype} codes, dim {dim}"
