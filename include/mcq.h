@@ -453,6 +453,48 @@ int mcq_search_scan_lists(const float *tables, long Q, const uint8_t *codes, con
                           const int64_t *list_offsets, long L, const int32_t *probes, int P,
                           float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- range search list by list: every hit within a threshold in the probed lists -----
+ * The range search of rules 7-9 over the candidates of rules 13 and 15: per query every stored vector of the lists its row
+ * of probes names whose score does not exceed its threshold, as CSR.  Tables, codes, w, thr and the metric are those of
+ * mcq_search_range_count_masked; mask (may be NULL), list_offsets, L, probes and P those of mcq_search_scan_lists.  The
+ * contract continues (the tests restate rules 17 and 18 in numpy and compare bit for bit):
+ *  17. listing.  b is LISTED for q iff it is a candidate of q under rules 13 and 15 (it lies in a list row q names and, under
+ *      a mask, its bit is set) and score[q][b] <= thr[q] under rule 7: one fp32 comparison, inclusive, and a NaN on either
+ *      side lists nothing.  The score of a candidate is the same bits as everywhere else (rules 3 and 3').
+ *  18. layout and order.  The output is CSR as in rule 8: lims int64[Q + 1], lims[0] = 0, entries (score fp32, position
+ *      int64) with positions those of the store.  The entries of query q come IN THE ORDER OF ITS PROBE ROW: the hits of the
+ *      list slot 0 names first, then slot 1's, and within a list in ascending position.  When the named lists of a row
+ *      ascend this is ascending position, and row q then equals, bit for bit, what mcq_search_range_count_masked and
+ *      mcq_search_range_fill_masked give when called with that one query and a mask whose set bits are the union of its
+ *      lists (under `mask`, the union intersected with it).  With every list named in ascending order and the lists covering
+ *      [0, B) it equals row q of mcq_search_range_count / _fill (under `mask`, of the masked calls).  A list named twice is
+ *      listed twice, its second block where the second naming stands: count and fill agree on this, and it neither faults
+ *      nor hangs.  The same inputs give the same bits (the only sums are of integers; no atomics).
+ *  19. empty calls and the order of the checks.  First the limits of rule 16 without k, with its status codes: one-byte
+ *      codes (K <= 256), N a power of two <= 64, Q and B not negative, an unknown metric, B <= 2^31 - 1, then P < 0 or
+ *      L < 0: MCQ_EINVAL; P > 4096: MCQ_EUNSUPPORTED.  lims is always needed (MCQ_EINVAL without it).  Q, B, L or P equal to
+ *      0: lims is all zeros, nothing else is written and no other input is looked at (fill returns 0 and writes nothing).
+ *      Otherwise the pointers of rule 16 (tables, codes, workspace, list_offsets, probes non-NULL, w == NULL only under
+ *      MCQ_SEARCH_IP, codes aligned to min(N, 16) bytes, mask and list_offsets to 8, probes to 4), then thr non-NULL, all
+ *      MCQ_EINVAL, and last a short workspace, MCQ_EWORKSPACE.  Nothing touches the device before every check has passed.
+ *  20. fill takes the SAME arguments, the same lims and the same, untouched workspace, after the caller has read lims[Q]
+ *      and allocated out_score float[total] and out_index int64[total].  It stores no entry whose slot is outside
+ *      [0, capacity), whatever lims and the workspace hold (capacity < 0 is MCQ_EINVAL, capacity == 0 writes nothing; with
+ *      room for an entry, out_score and out_index non-NULL).  The workspace is 8 bytes per (query, part of its candidates,
+ *      wave): a function of (Q, P, N, K) that depends on neither B, L, D nor the number of results.  The host reads nothing
+ *      back inside either call, and neither synchronises.
+ * Defence, not contract: list ranges are clamped to [0, B] and begin >= end is empty, as in rule 16's footnote.              */
+size_t mcq_search_range_lists_workspace_bytes(long Q, int P, int N, int K);
+int mcq_search_range_lists_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                 int metric, const uint64_t *mask /* may be NULL */,
+                                 const int64_t *list_offsets, long L, const int32_t *probes, int P,
+                                 const float *thr, int64_t *lims, void *workspace, size_t workspace_bytes, void *stream);
+int mcq_search_range_lists_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                int metric, const uint64_t *mask /* may be NULL */,
+                                const int64_t *list_offsets, long L, const int32_t *probes, int P,
+                                const float *thr, const int64_t *lims, float *out_score, int64_t *out_index, long capacity,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- test / profiling hooks -------------------------------------------------
  * Logits of Quantizer._logits (:277-279) for a batch, fp32 [B][N*K]; used by the
  * parity tests to localise a divergence.                                       */

@@ -26,6 +26,7 @@ SYMBOLS = (
     "mcq_search_range_workspace_bytes", "mcq_search_range_count", "mcq_search_range_fill",
     "mcq_search_pack_mask", "mcq_search_scan_masked", "mcq_search_range_count_masked", "mcq_search_range_fill_masked",
     "mcq_search_lists_workspace_bytes", "mcq_search_scan_lists",
+    "mcq_search_range_lists_workspace_bytes", "mcq_search_range_lists_count", "mcq_search_range_lists_fill",
 )
 
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
@@ -168,6 +169,15 @@ def lib():
         L.mcq_search_lists_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
         L.mcq_search_scan_lists.restype = i32
         L.mcq_search_scan_lists.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, vp, i64, vp, i32, vp, vp, vp, sz, vp]
+    # (and the range search list by list: an older build has none, and calling range_search_lists raises)
+    if not (_ALT and not hasattr(L, "mcq_search_range_lists_count")):
+        L.mcq_search_range_lists_workspace_bytes.restype = sz
+        L.mcq_search_range_lists_workspace_bytes.argtypes = [i64, i32, i32, i32]
+        L.mcq_search_range_lists_count.restype = i32
+        L.mcq_search_range_lists_count.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp, i32, vp, vp, vp, sz, vp]
+        L.mcq_search_range_lists_fill.restype = i32
+        L.mcq_search_range_lists_fill.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp, i32, vp, vp, vp, vp, i64,
+                                                  vp, sz, vp]
     L.mcq_last_encode_launches.restype = i32
     L.mcq_profile_encode.restype = i32
     L.mcq_profile_encode.argtypes = [vp, i64, vp, f32, i32, i32, i32, i32, vp, sz, vp, ctypes.POINTER(f32), ctypes.POINTER(i32), i32]

@@ -1116,6 +1116,74 @@ int range_check(const float *tables, long Q, const uint8_t *codes, const float *
     return 0;
 }
 
+// the range search list by list (rules 17-20; mirrored by range_lists_plan of tests/search_range_lists_grid.py): the parts of
+// lists_plan, the LDS of k_search_lists, one int64 per (query, part, wave) of workspace.  A function of the call's shape alone.
+struct RangeListsPlan {
+    int parts;
+    size_t lds, ws_bytes;
+};
+
+RangeListsPlan range_lists_plan(long Q, int P, int N, int K) {
+    RangeListsPlan p;
+    long parts = kListTargetBlocks / (Q > 0 ? Q : 1);
+    p.parts = (int)(parts < 1 ? 1 : (parts > kScanMaxSlices ? kScanMaxSlices : parts));
+    p.lds = (size_t)lists_lds_bytes(N * K, P);
+    p.ws_bytes = align256((size_t)Q * p.parts * kRangeListWaves * 8);
+    return p;
+}
+
+struct RangeListsArgs : RangeArgs {
+    const int64_t *list_offsets;
+    long L;
+    const int32_t *probes;
+    int P;
+};
+
+template <bool FILL>
+int launch_range_lists(const RangeListsPlan &p, hipStream_t st, const RangeListsArgs &a) {
+    return pick<1, 2, 4, 8>(a.N < 8 ? a.N : 8, [&](auto ch) {
+        return pick_bool(a.mask != nullptr, [&](auto masked) {
+            constexpr int CH = decltype(ch)::value;
+            constexpr bool MASKED = masked;
+            static bool allowed[64] = {};
+            if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_lists<CH, FILL, MASKED>),
+                                                 lists_lds_bytes(64 * 256, kListMaxProbes)))
+                return rc;
+            hipLaunchKernelGGL((k_range_lists<CH, FILL, MASKED>), dim3((unsigned)a.Q * (unsigned)p.parts), dim3(64 * kRangeListWaves),
+                               p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts, a.list_offsets, a.L, a.probes,
+                               a.P, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity, reinterpret_cast<const u64 *>(a.mask));
+            return launch_rc();
+        });
+    });
+}
+
+// rule 19: what both entry points of the range search list by list reject, in rule 16's order without k; nothing touches
+// the device.  *empty: the call has no candidate anywhere (Q, B, L or P is 0) and looked at no input but lims.
+int range_lists_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+                      const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes, int P, const float *thr,
+                      const int64_t *lims, const void *workspace, size_t workspace_bytes, bool *empty) {
+    *empty = false;
+    if (const int rc = search_domain(N, K, 1)) return rc;
+    if (Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
+    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (P < 0 || L < 0) return MCQ_EINVAL;
+    if (P > kListMaxProbes) return MCQ_EUNSUPPORTED;
+    if (!lims) return MCQ_EINVAL;                                          // (lims is always needed, as in rule 9)
+    if (Q == 0 || B == 0 || L == 0 || P == 0) {
+        *empty = true;
+        return 0;
+    }
+    if (!tables || !codes || !workspace || !list_offsets || !probes) return MCQ_EINVAL;
+    if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;
+    const int need = N >= 16 ? 16 : N;
+    if (reinterpret_cast<uintptr_t>(codes) % need != 0 || reinterpret_cast<uintptr_t>(mask) % 8 != 0) return MCQ_EINVAL;
+    if (reinterpret_cast<uintptr_t>(list_offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(probes) % 4 != 0) return MCQ_EINVAL;
+    if (!thr) return MCQ_EINVAL;
+    if (workspace_bytes < range_lists_plan(Q, P, N, K).ws_bytes) return MCQ_EWORKSPACE;
+    return 0;
+}
+
 }  // namespace
 
 // ---- mcq_decode: a predicate and a launcher per path.  The paths are tried in the order below; the generic kernel takes the rest
@@ -1834,6 +1902,51 @@ int mcq_search_range_fill_masked(const float *tables, long Q, const uint8_t *cod
     const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
                       static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity, mask};
     return launch_range<true>(p, static_cast<hipStream_t>(stream), a);
+}
+
+// ---- rules 17-20: the range search list by list.  The size depends on neither B nor L: the parts of a query are cut on the device.
+size_t mcq_search_range_lists_workspace_bytes(long Q, int P, int N, int K) {
+    if (Q <= 0 || P <= 0 || P > kListMaxProbes || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
+    return range_lists_plan(Q, P, N, K).ws_bytes;
+}
+
+int mcq_search_range_lists_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                 int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes,
+                                 int P, const float *thr, int64_t *lims, void *workspace, size_t workspace_bytes, void *stream) {
+    bool empty = false;
+    if (const int rc = range_lists_check(tables, Q, codes, w, B, N, K, metric, mask, list_offsets, L, probes, P, thr, lims,
+                                         workspace, workspace_bytes, &empty))
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!empty) {
+        const RangeListsPlan p = range_lists_plan(Q, P, N, K);
+        int64_t *ws = static_cast<int64_t *>(workspace);
+        const RangeListsArgs a{{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr, ws, nullptr,
+                                nullptr, nullptr, 0, mask}, list_offsets, L, probes, P};
+        if (const int rc = launch_range_lists<false>(p, st, a)) return rc;
+        hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)Q), dim3(64), 0, st, ws, p.parts * kRangeListWaves, lims);
+        if (const int rc = launch_rc()) return rc;
+    }
+    hipLaunchKernelGGL(k_range_lims, dim3(1), dim3(64), 0, st, lims, Q, empty ? 1 : 0);
+    return launch_rc();
+}
+
+int mcq_search_range_lists_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes,
+                                int P, const float *thr, const int64_t *lims, float *out_score, int64_t *out_index, long capacity,
+                                void *workspace, size_t workspace_bytes, void *stream) {
+    bool empty = false;
+    if (const int rc = range_lists_check(tables, Q, codes, w, B, N, K, metric, mask, list_offsets, L, probes, P, thr, lims,
+                                         workspace, workspace_bytes, &empty))
+        return rc;
+    if (capacity < 0) return MCQ_EINVAL;
+    if (empty || capacity == 0) return 0;                                  // nothing can be stored
+    if (!out_score || !out_index) return MCQ_EINVAL;
+    const RangeListsPlan p = range_lists_plan(Q, P, N, K);
+    const RangeListsArgs a{{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
+                            static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity, mask},
+                           list_offsets, L, probes, P};
+    return launch_range_lists<true>(p, static_cast<hipStream_t>(stream), a);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

@@ -1,11 +1,13 @@
-"""An inverted file over a store of codes: the torch plumbing round Quantizer.search_lists (no hot path; the scoring is
-mcq_search_scan_lists).
+"""An inverted file over a store of codes: the torch plumbing round Quantizer.search_lists and Quantizer.range_search_lists
+(no hot path; the scoring is mcq_search_scan_lists and mcq_search_range_lists_count / _fill).
 
     order, list_offsets = build_lists(assign, num_lists)       # once per store: assign[b] = the coarse cell of vector b
     codes, norms = codes[order], norms[order]                  # the store in list order
     probes = probe_lists(queries, centroids, nprobe)           # per call: the nprobe nearest cells of each query
     dist, idx = quantizer.search_lists(queries, codes, list_offsets, probes, k=10, norms=norms)
     original = torch.where(idx >= 0, order[idx.clamp(min=0)], idx)
+    lims, dist, idx = quantizer.range_search_lists(queries, codes, list_offsets, probes, radius, norms=norms)
+    original = order[idx]                                      # every hit within the radius in the probed lists, as CSR
 
 Where the coarse centroids come from (k-means over a sample, a trained layer) is the caller's business."""
 import torch

@@ -775,19 +775,28 @@ class Quantizer(nn.Module):
 
     # ------------------------------------------------- range search over stored codes
     def _search_range(self, tables: Tensor, codes: Tensor, w: Tensor, thr: Tensor, metric: str = "l2",
-                      max_results: int = None, mask: Tensor = None):
+                      max_results: int = None, mask: Tensor = None, lists=None):
         """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, w as _search_scan takes it under the metric (norms, None,
         reciprocal roots), thr fp32 (Q,) -> (lims int64 (Q + 1,), scores fp32 (total,), indexes int64 (total,)): every b with
         score[q][b] <= thr[q], the entries of query q at [lims[q], lims[q+1]) in ascending position (mcq_search_range_count,
         one host synchronisation to read lims[Q], mcq_search_range_fill).  More than max_results entries: McqError.
         mask as _search_scan takes it: only positions whose bit is set are listed (mcq_search_range_count_masked and
-        mcq_search_range_fill_masked, with the same words)."""
+        mcq_search_range_fill_masked, with the same words).
+        lists: (list_offsets, probes) as _search_scan takes them: every such b among the positions of the lists row q of
+        `probes` names, under the mask if there is one, IN THE ORDER OF THE ROW -- slot 0's list first, ascending position
+        within a list (mcq_search_range_lists_count and mcq_search_range_lists_fill)."""
         N, K = self.num_codebooks, self.codebook_size
         self._check_mask(mask, codes.shape[0])
-        tables, codes, w, m, Q, B, dev = self._search_inputs(tables, codes, w, metric, thr, *(() if mask is None else (mask,)))
+        self._check_lists(lists, tables.shape[0])
+        more = (() if mask is None else (mask,)) + (() if lists is None else tuple(lists))
+        tables, codes, w, m, Q, B, dev = self._search_inputs(tables, codes, w, metric, thr, *more)
         L = _lib.lib()
         count, fill = "mcq_search_range_count", "mcq_search_range_fill"
-        if mask is not None:
+        if lists is not None:
+            count, fill = "mcq_search_range_lists_count", "mcq_search_range_lists_fill"
+            if not hasattr(L, count):
+                raise _lib.McqError(f"{_lib.LIB_PATH} has no range search by lists ({count})")
+        elif mask is not None:
             count, fill = count + "_masked", fill + "_masked"
         if not hasattr(L, count):
             raise _lib.McqError(f"{_lib.LIB_PATH} has no {'masked ' if mask is not None else ''}range search ({count})")
@@ -796,11 +805,17 @@ class Quantizer(nn.Module):
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             lims = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
-            ws = torch.empty(L.mcq_search_range_workspace_bytes(Q, B, N, K), dtype=torch.uint8, device=dev)
             args = (tables.data_ptr(), Q, codes.data_ptr(), None if w is None else w.data_ptr(), B, N, K, m)
-            if mask is not None:
-                words = self._mask_words(mask)                    # (alive until the fill has been enqueued)
-                args += (words.data_ptr(),)
+            words = self._mask_words(mask)                        # (alive until the fill has been enqueued)
+            if lists is not None:
+                offsets, probes = self._list_arrays(*lists)       # (alive likewise)
+                nl, P = offsets.numel() - 1, probes.shape[1]
+                ws = torch.empty(L.mcq_search_range_lists_workspace_bytes(Q, P, N, K), dtype=torch.uint8, device=dev)
+                args += (None if words is None else words.data_ptr(), offsets.data_ptr(), nl, probes.data_ptr(), P)
+            else:
+                ws = torch.empty(L.mcq_search_range_workspace_bytes(Q, B, N, K), dtype=torch.uint8, device=dev)
+                if mask is not None:
+                    args += (words.data_ptr(),)
             args += (thr.data_ptr(), lims.data_ptr())
             _lib.check(getattr(L, count)(*args, ws.data_ptr(), ws.numel(), st), count)
             total = int(lims[Q])                                  # the one host synchronisation: the result is allocated next
@@ -826,9 +841,35 @@ class Quantizer(nn.Module):
         One host synchronisation (reading lims[Q]) separates counting from filling; more than max_results entries raise
         McqError, naming the count, before anything is allocated for them.  Not differentiable.
         mask: as search takes it; only stored vectors it keeps are listed, at their positions in `codes`."""
+        return self._range_search(queries, codes, radius, norms, metric, rnorms, max_results, mask)
+
+    def range_search_lists(self, queries: Tensor, codes: Tensor, list_offsets: Tensor, probes: Tensor, radius,
+                           norms: Tensor = None, metric: str = "l2", rnorms: Tensor = None, max_results: int = 1 << 26,
+                           mask: Tensor = None):
+        """range_search() over an inverted file: every stored vector within `radius` of each query AMONG THE LISTS IT PROBES
+        (quantization_amd.ivf.build_lists orders a store, probe_lists picks the lists).
+        list_offsets and probes exactly as search_lists takes them: int64 (L + 1,), and (*, P) int32 or int64 with one row
+        per query, an entry in [0, L) naming a list and any other value (-1 is the padding) none.  Everything else is
+        range_search()'s: radius (float or a tensor of Q values) and what it means under each metric, the thresholds, the
+        returned values and their clamping, max_results, the one host synchronisation, and the mask (a stored vector is listed
+        iff it lies in a probed list AND the mask keeps it AND it is within the radius).
+        -> (lims int64 (Q + 1,), values fp32 (total,), indexes int64 (total,)): CSR; indexes are positions in `codes`, that
+        is in list order (map them through build_lists' `order` for the original ones).
+        This method sorts each probe row ascending before the call (entries that name no list stay out of the way), so the
+        results of a query are IN ASCENDING POSITION and row q equals range_search(queries[q], ..., mask=the union of its
+        lists).  The C entry (mcq_search_range_lists_count / _fill) keeps the row's own order: slot 0's list first.  A list
+        named twice in a row is listed twice.  The cost falls with the probed share; nothing sweeps the whole store."""
+        self._check_lists((list_offsets, probes), queries.numel() // max(queries.shape[-1], 1))
+        offsets, rows = self._list_arrays(list_offsets, probes)
+        return self._range_search(queries, codes, radius, norms, metric, rnorms, max_results, mask,
+                                  (offsets, torch.sort(rows, dim=1).values))
+
+    def _range_search(self, queries: Tensor, codes: Tensor, radius, norms, metric: str, rnorms, max_results, mask, lists=None):
+        """range_search() and range_search_lists(): `lists` is None or (list_offsets, probes)"""
         if metric not in self._METRICS:
             raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
         self._check_mask(mask, codes.reshape(-1, codes.shape[-1]).shape[0])
+        self._check_lists(lists, queries.numel() // max(queries.shape[-1], 1))
         with torch.no_grad():
             flat = self._unpacked_codes(codes)
             tables = self.search_tables(queries)
@@ -853,7 +894,7 @@ class Quantizer(nn.Module):
                 zero = qn[:, 0] == 0                               # every similarity of a zero query is 0
                 thr = torch.where(zero, torch.where(rad <= 0, float("inf"), float("-inf")).to(thr.dtype), thr)
                 qn = qn.masked_fill(qn == 0, 1.0)
-            lims, scores, indexes = self._search_range(tables, flat, w, thr, metric, max_results, mask)
+            lims, scores, indexes = self._search_range(tables, flat, w, thr, metric, max_results, mask, lists)
             rows = torch.repeat_interleave(torch.arange(Q, device=dev), lims[1:] - lims[:-1], output_size=scores.numel())
             if metric == "l2":
                 values = (scores + qq[:, 0][rows]).clamp_(min=0.0)
