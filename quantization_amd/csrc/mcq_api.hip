@@ -913,24 +913,41 @@ int search_domain(int N, int K, int D) {
     return K > 256 ? MCQ_EUNSUPPORTED : 0;
 }
 
-// What every scan and sweep entry point rejects, in this order (tests/test_search_host.py, test_search_metric_host.py and
-// test_search_range_host.py pin it); nothing touches the device.  k: 1 where the entry has none.  outs_ok: the outputs this
-// call writes are there (the caller knows which of them an empty call still writes).  A call with Q == 0 or B == 0 reads no
-// input, so none is looked at.  mask: NULL where the call has none (rule 12); one that is there is read as 8-byte words.
+// the probe set of a call that goes list by list (rules 13-20); a call over the whole store has none and passes NULL
+struct ListsIn {
+    const int64_t *list_offsets;
+    long L;
+    const int32_t *probes;
+    int P;
+};
+
+// What every scan, sweep and list-by-list entry point rejects, in this order (tests/test_search_host.py, test_search_metric_host.py,
+// test_search_mask_host.py, test_search_range_host.py, test_search_lists_host.py and test_search_range_lists_host.py pin it);
+// nothing touches the device.  k: 1 where the entry has none.  outs_ok: the outputs this call writes are there (the caller
+// knows which of them an empty call still writes).  *empty: the call has no candidate anywhere (Q or B is 0; with lists, L or
+// P) -- it reads no input, so none is looked at.  mask: NULL where the call has none (rule 12); one that is there is read as
+// 8-byte words.  li: the limits of rule 16 come between B's and the outputs, its pointers and alignments with the others.
 int search_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
-                 const uint64_t *mask, bool outs_ok, const void *workspace) {
+                 const uint64_t *mask, const ListsIn *li, bool outs_ok, const void *workspace, bool *empty) {
+    *empty = false;
     if (const int rc = search_domain(N, K, 1)) return rc;
     if (k > 64) return MCQ_EUNSUPPORTED;
     if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
     if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
     if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (li && (li->P < 0 || li->L < 0)) return MCQ_EINVAL;
+    if (li && li->P > kListMaxProbes) return MCQ_EUNSUPPORTED;
     if (!outs_ok) return MCQ_EINVAL;
-    if (Q == 0 || B == 0) return 0;
-    if (!tables || !codes || !workspace) return MCQ_EINVAL;
+    if (Q == 0 || B == 0 || (li && (li->L == 0 || li->P == 0))) {
+        *empty = true;
+        return 0;
+    }
+    if (!tables || !codes || !workspace || (li && (!li->list_offsets || !li->probes))) return MCQ_EINVAL;
     if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;                  // (the inner product never reads w)
     const int need = N >= 16 ? 16 : N;                                    // a candidate's codes are loaded as one vector
     if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
     if (reinterpret_cast<uintptr_t>(mask) % 8 != 0) return MCQ_EINVAL;
+    if (li && (reinterpret_cast<uintptr_t>(li->list_offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(li->probes) % 4 != 0)) return MCQ_EINVAL;
     return 0;
 }
 
@@ -1021,18 +1038,18 @@ struct ListsPlan {
     size_t lds, ws_half;
 };
 
+int lists_parts(long Q) {
+    const long parts = kListTargetBlocks / (Q > 0 ? Q : 1);
+    return (int)(parts < 1 ? 1 : (parts > kScanMaxSlices ? kScanMaxSlices : parts));
+}
+
 ListsPlan lists_plan(long Q, int P, int N, int K, int k) {
-    ListsPlan p;
-    long parts = kListTargetBlocks / (Q > 0 ? Q : 1);
-    p.parts = (int)(parts < 1 ? 1 : (parts > kScanMaxSlices ? kScanMaxSlices : parts));
-    p.lds = (size_t)lists_lds_bytes(N * K, P);
-    p.ws_half = align256((size_t)Q * p.parts * k * 4);                   // scores, then positions
-    return p;
+    const int parts = lists_parts(Q);
+    return {parts, (size_t)lists_lds_bytes(N * K, P), align256((size_t)Q * parts * k * 4)};   // scores, then positions
 }
 
 int launch_lists(const ListsPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
-                 int N, int K, int k, int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes,
-                 int P, float *ws_s, int *ws_i) {
+                 int N, int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
     return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
         return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
             return pick_bool(mask != nullptr, [&](auto masked) {
@@ -1043,12 +1060,45 @@ int launch_lists(const ListsPlan &p, hipStream_t st, const float *tables, int Q,
                                                      lists_lds_bytes(64 * 256, kListMaxProbes)))
                     return rc;
                 hipLaunchKernelGGL((k_search_lists<NN, M, MASKED>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kListWaves), p.lds,
-                                   st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, list_offsets, L, probes, P,
-                                   ws_s, ws_i, reinterpret_cast<const u64 *>(mask));
+                                   st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, li.list_offsets, li.L, li.probes,
+                                   li.P, ws_s, ws_i, reinterpret_cast<const u64 *>(mask));
                 return launch_rc();
             });
         });
     });
+}
+
+// every top-k entry point: the scan over the whole store (rules 1-6 and 10-12), or list by list (li; rules 13-16)
+int search_topk(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
+                const uint64_t *mask, const ListsIn *li, float *out_score, int64_t *out_index, void *workspace,
+                size_t workspace_bytes, void *stream) {
+    bool empty;
+    if (const int rc = search_check(tables, Q, codes, w, B, N, K, k, metric, mask, li, Q == 0 || (out_score && out_index), workspace, &empty))
+        return rc;
+    if (Q == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws_s = nullptr;
+    int *ws_i = nullptr;
+    const auto split = [&](size_t half) {                                 // the workspace: scores, then positions
+        if (workspace_bytes < 2 * half) return false;
+        ws_s = static_cast<float *>(workspace);
+        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + half);
+        return true;
+    };
+    int S = 0;                                                            // lists per query; 0 (no candidate anywhere): the fill of rule 4
+    if (!empty && li) {
+        const ListsPlan p = lists_plan(Q, li->P, N, K, k);
+        if (!split(p.ws_half)) return MCQ_EWORKSPACE;
+        if (const int rc = launch_lists(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, *li, ws_s, ws_i)) return rc;
+        S = p.parts;
+    } else if (!empty) {
+        const ScanPlan p = scan_plan(Q, B, N, K, k);
+        if (!split(p.ws_half)) return MCQ_EWORKSPACE;
+        if (const int rc = launch_scan(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, ws_s, ws_i, mask)) return rc;
+        S = p.slices;
+    }
+    hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, S, k, out_score, out_index);
+    return launch_rc();
 }
 
 }  // namespace
@@ -1106,16 +1156,6 @@ int launch_range(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
     });
 }
 
-// rule 9: what both range entry points reject (lims is written even by an empty call); nothing touches the device
-int range_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
-                const uint64_t *mask, const float *thr, const int64_t *lims, const void *workspace, size_t workspace_bytes) {
-    if (const int rc = search_check(tables, Q, codes, w, B, N, K, 1, metric, mask, lims != nullptr, workspace)) return rc;
-    if (Q == 0 || B == 0) return 0;
-    if (!thr) return MCQ_EINVAL;                     // (after w and the alignment now: all three are MCQ_EINVAL, no code moved)
-    if (workspace_bytes < range_plan(Q, B, N, K).ws_bytes) return MCQ_EWORKSPACE;
-    return 0;
-}
-
 // the range search list by list (rules 17-20; mirrored by range_lists_plan of tests/search_range_lists_grid.py): the parts of
 // lists_plan, the LDS of k_search_lists, one int64 per (query, part, wave) of workspace.  A function of the call's shape alone.
 struct RangeListsPlan {
@@ -1124,23 +1164,12 @@ struct RangeListsPlan {
 };
 
 RangeListsPlan range_lists_plan(long Q, int P, int N, int K) {
-    RangeListsPlan p;
-    long parts = kListTargetBlocks / (Q > 0 ? Q : 1);
-    p.parts = (int)(parts < 1 ? 1 : (parts > kScanMaxSlices ? kScanMaxSlices : parts));
-    p.lds = (size_t)lists_lds_bytes(N * K, P);
-    p.ws_bytes = align256((size_t)Q * p.parts * kRangeListWaves * 8);
-    return p;
+    const int parts = lists_parts(Q);
+    return {parts, (size_t)lists_lds_bytes(N * K, P), align256((size_t)Q * parts * kRangeListWaves * 8)};
 }
 
-struct RangeListsArgs : RangeArgs {
-    const int64_t *list_offsets;
-    long L;
-    const int32_t *probes;
-    int P;
-};
-
 template <bool FILL>
-int launch_range_lists(const RangeListsPlan &p, hipStream_t st, const RangeListsArgs &a) {
+int launch_range_lists(const RangeListsPlan &p, hipStream_t st, const RangeArgs &a, const ListsIn &li) {
     return pick<1, 2, 4, 8>(a.N < 8 ? a.N : 8, [&](auto ch) {
         return pick_bool(a.mask != nullptr, [&](auto masked) {
             constexpr int CH = decltype(ch)::value;
@@ -1150,38 +1179,72 @@ int launch_range_lists(const RangeListsPlan &p, hipStream_t st, const RangeLists
                                                  lists_lds_bytes(64 * 256, kListMaxProbes)))
                 return rc;
             hipLaunchKernelGGL((k_range_lists<CH, FILL, MASKED>), dim3((unsigned)a.Q * (unsigned)p.parts), dim3(64 * kRangeListWaves),
-                               p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts, a.list_offsets, a.L, a.probes,
-                               a.P, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity, reinterpret_cast<const u64 *>(a.mask));
+                               p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts, li.list_offsets, li.L, li.probes,
+                               li.P, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity, reinterpret_cast<const u64 *>(a.mask));
             return launch_rc();
         });
     });
 }
 
-// rule 19: what both entry points of the range search list by list reject, in rule 16's order without k; nothing touches
-// the device.  *empty: the call has no candidate anywhere (Q, B, L or P is 0) and looked at no input but lims.
-int range_lists_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
-                      const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes, int P, const float *thr,
-                      const int64_t *lims, const void *workspace, size_t workspace_bytes, bool *empty) {
-    *empty = false;
-    if (const int rc = search_domain(N, K, 1)) return rc;
-    if (Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
-    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
-    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
-    if (P < 0 || L < 0) return MCQ_EINVAL;
-    if (P > kListMaxProbes) return MCQ_EUNSUPPORTED;
-    if (!lims) return MCQ_EINVAL;                                          // (lims is always needed, as in rule 9)
-    if (Q == 0 || B == 0 || L == 0 || P == 0) {
-        *empty = true;
-        return 0;
-    }
-    if (!tables || !codes || !workspace || !list_offsets || !probes) return MCQ_EINVAL;
-    if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;
-    const int need = N >= 16 ? 16 : N;
-    if (reinterpret_cast<uintptr_t>(codes) % need != 0 || reinterpret_cast<uintptr_t>(mask) % 8 != 0) return MCQ_EINVAL;
-    if (reinterpret_cast<uintptr_t>(list_offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(probes) % 4 != 0) return MCQ_EINVAL;
-    if (!thr) return MCQ_EINVAL;
-    if (workspace_bytes < range_lists_plan(Q, P, N, K).ws_bytes) return MCQ_EWORKSPACE;
+// rules 9 and 19: what every range entry point rejects -- search_check without k (lims is written even by an empty call),
+// then thr and the size of the workspace; nothing touches the device
+int range_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+                const uint64_t *mask, const ListsIn *li, const float *thr, const int64_t *lims, const void *workspace,
+                size_t workspace_bytes, bool *empty) {
+    if (const int rc = search_check(tables, Q, codes, w, B, N, K, 1, metric, mask, li, lims != nullptr, workspace, empty)) return rc;
+    if (*empty) return 0;
+    if (!thr) return MCQ_EINVAL;                     // (after w and the alignment: all three are MCQ_EINVAL, no code moved)
+    if (workspace_bytes < (li ? range_lists_plan(Q, li->P, N, K).ws_bytes : range_plan(Q, B, N, K).ws_bytes)) return MCQ_EWORKSPACE;
     return 0;
+}
+
+// the launch of one sweep, over the whole store or list by list (li).  *per: the workspace entries of a query.
+template <bool FILL>
+int launch_range_any(hipStream_t st, const RangeArgs &a, const ListsIn *li, int *per = nullptr) {
+    if (li) {
+        const RangeListsPlan p = range_lists_plan(a.Q, li->P, a.N, a.K);
+        if (per) *per = p.parts * kRangeListWaves;
+        return launch_range_lists<FILL>(p, st, a, *li);
+    }
+    const RangePlan p = range_plan(a.Q, a.B, a.N, a.K);
+    if (per) *per = p.slices * kRangeWaves;
+    return launch_range<FILL>(p, st, a);
+}
+
+// every count entry point: the COUNT sweep, the counts -> offsets per query, the totals -> lims
+int range_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+                const uint64_t *mask, const ListsIn *li, const float *thr, int64_t *lims, void *workspace, size_t workspace_bytes,
+                void *stream) {
+    bool empty;
+    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, li, thr, lims, workspace, workspace_bytes, &empty))
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!empty) {
+        int64_t *ws = static_cast<int64_t *>(workspace);
+        const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr, ws, nullptr,
+                          nullptr, nullptr, 0, mask};
+        int per = 0;
+        if (const int rc = launch_range_any<false>(st, a, li, &per)) return rc;
+        hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)Q), dim3(64), 0, st, ws, per, lims);
+        if (const int rc = launch_rc()) return rc;
+    }
+    hipLaunchKernelGGL(k_range_lims, dim3(1), dim3(64), 0, st, lims, Q, empty ? 1 : 0);
+    return launch_rc();
+}
+
+// every fill entry point: the FILL sweep into out_score / out_index, `capacity` entries each
+int range_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+               const uint64_t *mask, const ListsIn *li, const float *thr, const int64_t *lims, float *out_score, int64_t *out_index,
+               long capacity, void *workspace, size_t workspace_bytes, void *stream) {
+    bool empty;
+    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, li, thr, lims, workspace, workspace_bytes, &empty))
+        return rc;
+    if (capacity < 0) return MCQ_EINVAL;
+    if (empty || capacity == 0) return 0;                                  // nothing can be stored
+    if (!out_score || !out_index) return MCQ_EINVAL;
+    const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
+                      static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity, mask};
+    return launch_range_any<true>(static_cast<hipStream_t>(stream), a, li);
 }
 
 }  // namespace
@@ -1796,22 +1859,8 @@ int mcq_search_scan_metric(const float *tables, long Q, const uint8_t *codes, co
 int mcq_search_scan_masked(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
                            int metric, const uint64_t *mask, float *out_score, int64_t *out_index, void *workspace,
                            size_t workspace_bytes, void *stream) {
-    if (const int rc = search_check(tables, Q, codes, w, B, N, K, k, metric, mask, Q == 0 || (out_score && out_index), workspace))
-        return rc;
-    if (Q == 0) return 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ScanPlan p{};
-    float *ws_s = nullptr;
-    int *ws_i = nullptr;
-    if (B > 0) {
-        p = scan_plan(Q, B, N, K, k);
-        if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
-        ws_s = static_cast<float *>(workspace);
-        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
-        if (const int rc = launch_scan(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, ws_s, ws_i, mask)) return rc;
-    }
-    hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, p.slices, k, out_score, out_index);
-    return launch_rc();
+    return search_topk(tables, Q, codes, w, B, N, K, k, metric, mask, nullptr, out_score, out_index, workspace, workspace_bytes,
+                       stream);
 }
 
 // rules 13-16: the search list by list.  The size depends on neither B nor L: the parts of a query are cut on the device.
@@ -1823,34 +1872,8 @@ size_t mcq_search_lists_workspace_bytes(long Q, int P, int N, int K, int k) {
 int mcq_search_scan_lists(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
                           int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes, int P,
                           float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
-    // the checks of search_check in its order, with rule 16's own between the limits and the pointers
-    if (const int rc = search_domain(N, K, 1)) return rc;
-    if (k > 64) return MCQ_EUNSUPPORTED;
-    if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
-    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
-    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
-    if (P < 0 || L < 0) return MCQ_EINVAL;
-    if (P > kListMaxProbes) return MCQ_EUNSUPPORTED;
-    if (Q == 0) return 0;
-    if (!out_score || !out_index) return MCQ_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (B == 0 || L == 0 || P == 0) {                                      // no candidate anywhere: the fill of rule 4
-        hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, nullptr, nullptr, 0, k, out_score, out_index);
-        return launch_rc();
-    }
-    if (!tables || !codes || !workspace || !list_offsets || !probes) return MCQ_EINVAL;
-    if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;
-    const int need = N >= 16 ? 16 : N;
-    if (reinterpret_cast<uintptr_t>(codes) % need != 0 || reinterpret_cast<uintptr_t>(mask) % 8 != 0) return MCQ_EINVAL;
-    if (reinterpret_cast<uintptr_t>(list_offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(probes) % 4 != 0) return MCQ_EINVAL;
-    const ListsPlan p = lists_plan(Q, P, N, K, k);
-    if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
-    float *ws_s = static_cast<float *>(workspace);
-    int *ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
-    if (const int rc = launch_lists(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, list_offsets, L, probes, P, ws_s, ws_i))
-        return rc;
-    hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, p.parts, k, out_score, out_index);
-    return launch_rc();
+    const ListsIn li{list_offsets, L, probes, P};
+    return search_topk(tables, Q, codes, w, B, N, K, k, metric, mask, &li, out_score, out_index, workspace, workspace_bytes, stream);
 }
 
 // ---- range search over stored codes: mcq_range_kernels.h (rules 7-9 of include/mcq.h)
@@ -1868,20 +1891,7 @@ int mcq_search_range_count(const float *tables, long Q, const uint8_t *codes, co
 int mcq_search_range_count_masked(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
                                   int metric, const uint64_t *mask, const float *thr, int64_t *lims, void *workspace,
                                   size_t workspace_bytes, void *stream) {
-    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, thr, lims, workspace, workspace_bytes)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool empty = Q == 0 || B == 0;
-    if (!empty) {
-        const RangePlan p = range_plan(Q, B, N, K);
-        int64_t *ws = static_cast<int64_t *>(workspace);
-        const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr, ws, nullptr,
-                          nullptr, nullptr, 0, mask};
-        if (const int rc = launch_range<false>(p, st, a)) return rc;
-        hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)Q), dim3(64), 0, st, ws, p.slices * kRangeWaves, lims);
-        if (const int rc = launch_rc()) return rc;
-    }
-    hipLaunchKernelGGL(k_range_lims, dim3(1), dim3(64), 0, st, lims, Q, empty ? 1 : 0);
-    return launch_rc();
+    return range_count(tables, Q, codes, w, B, N, K, metric, mask, nullptr, thr, lims, workspace, workspace_bytes, stream);
 }
 
 int mcq_search_range_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
@@ -1894,14 +1904,8 @@ int mcq_search_range_fill(const float *tables, long Q, const uint8_t *codes, con
 int mcq_search_range_fill_masked(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
                                  int metric, const uint64_t *mask, const float *thr, const int64_t *lims, float *out_score,
                                  int64_t *out_index, long capacity, void *workspace, size_t workspace_bytes, void *stream) {
-    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, thr, lims, workspace, workspace_bytes)) return rc;
-    if (capacity < 0) return MCQ_EINVAL;
-    if (Q == 0 || B == 0 || capacity == 0) return 0;                       // nothing can be stored
-    if (!out_score || !out_index) return MCQ_EINVAL;
-    const RangePlan p = range_plan(Q, B, N, K);
-    const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
-                      static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity, mask};
-    return launch_range<true>(p, static_cast<hipStream_t>(stream), a);
+    return range_fill(tables, Q, codes, w, B, N, K, metric, mask, nullptr, thr, lims, out_score, out_index, capacity, workspace,
+                      workspace_bytes, stream);
 }
 
 // ---- rules 17-20: the range search list by list.  The size depends on neither B nor L: the parts of a query are cut on the device.
@@ -1913,40 +1917,17 @@ size_t mcq_search_range_lists_workspace_bytes(long Q, int P, int N, int K) {
 int mcq_search_range_lists_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
                                  int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes,
                                  int P, const float *thr, int64_t *lims, void *workspace, size_t workspace_bytes, void *stream) {
-    bool empty = false;
-    if (const int rc = range_lists_check(tables, Q, codes, w, B, N, K, metric, mask, list_offsets, L, probes, P, thr, lims,
-                                         workspace, workspace_bytes, &empty))
-        return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!empty) {
-        const RangeListsPlan p = range_lists_plan(Q, P, N, K);
-        int64_t *ws = static_cast<int64_t *>(workspace);
-        const RangeListsArgs a{{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr, ws, nullptr,
-                                nullptr, nullptr, 0, mask}, list_offsets, L, probes, P};
-        if (const int rc = launch_range_lists<false>(p, st, a)) return rc;
-        hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)Q), dim3(64), 0, st, ws, p.parts * kRangeListWaves, lims);
-        if (const int rc = launch_rc()) return rc;
-    }
-    hipLaunchKernelGGL(k_range_lims, dim3(1), dim3(64), 0, st, lims, Q, empty ? 1 : 0);
-    return launch_rc();
+    const ListsIn li{list_offsets, L, probes, P};
+    return range_count(tables, Q, codes, w, B, N, K, metric, mask, &li, thr, lims, workspace, workspace_bytes, stream);
 }
 
 int mcq_search_range_lists_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
                                 int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes,
                                 int P, const float *thr, const int64_t *lims, float *out_score, int64_t *out_index, long capacity,
                                 void *workspace, size_t workspace_bytes, void *stream) {
-    bool empty = false;
-    if (const int rc = range_lists_check(tables, Q, codes, w, B, N, K, metric, mask, list_offsets, L, probes, P, thr, lims,
-                                         workspace, workspace_bytes, &empty))
-        return rc;
-    if (capacity < 0) return MCQ_EINVAL;
-    if (empty || capacity == 0) return 0;                                  // nothing can be stored
-    if (!out_score || !out_index) return MCQ_EINVAL;
-    const RangeListsPlan p = range_lists_plan(Q, P, N, K);
-    const RangeListsArgs a{{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
-                            static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity, mask},
-                           list_offsets, L, probes, P};
-    return launch_range_lists<true>(p, static_cast<hipStream_t>(stream), a);
+    const ListsIn li{list_offsets, L, probes, P};
+    return range_fill(tables, Q, codes, w, B, N, K, metric, mask, &li, thr, lims, out_score, out_index, capacity, workspace,
+                      workspace_bytes, stream);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

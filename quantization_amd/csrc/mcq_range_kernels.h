@@ -139,22 +139,19 @@ k_range_sweep(const float *__restrict__ tables, int Q, const uint8_t *__restrict
 }
 
 // ---------------------------------------------------------------- the range search list by list (rules 17-20 of include/mcq.h)
-// The sweep's hit logic over the step space of k_search_lists (mcq_search_kernels.h): a workgroup is ONE query and part s of S
-// of the steps of ITS probes -- per probe the range clamped to [0, B] (begin >= end, and a probe outside [0, L), are empty),
-// ceil(len / 64) steps, an exclusive int64 prefix sum over the probes, part s owning the steps [s*T/S, (s+1)*T/S).
+// The sweep's hit logic over the step space of k_search_lists: a workgroup is ONE query and part s of S of the steps of ITS
+// probes.  The step space, its cut into parts, ListWalk and ListCursor are described once, in mcq_search_kernels.h ("lists");
+// what differs here:
 //   * a wave owns a CONTIGUOUS run of its part's steps, run = ceil((hi - lo) / W), wave v the steps [lo + v*run, min(lo +
 //     (v+1)*run, hi)): the rule of k_range_sweep, not the interleaving of k_search_lists.  So (part, wave, step, lane)
 //     ascending IS the flattened step space -- the probe row's own order, ascending position within a list -- and the fill
 //     learns its slots from the counts alone, as in the sweep.
-//   * a wave finds its first step by bisection over `pre`, then ListWalk walks the pointer up; the next step's candidate,
-//     across a list boundary too, is the bnext of tile_step, and under a mask the lane's mask word travels with it (lists do
-//     not start at multiples of 64: every lane tests its own bit).
 //   * the score is tile_step<1, CH> + score_finish with the metric a wave-uniform runtime switch, the comparison, the ballot
 //     and the slot are k_range_sweep's.  One query per workgroup: the wave's base slot is one value in a register.
 //   * COUNT writes one int64 per (query, part, wave), zeros included (nobody clears the workspace): a part without a step
 //     writes its zeros and returns before it stages the table.  k_range_offsets (per = S * kRangeListWaves) and k_range_lims
 //     finish the count unchanged.  No atomics of any kind.
-// LDS: lists_lds_bytes of mcq_search_kernels.h -- [the table, N*K floats][pre: int64 P + 1][begin: int32 P][end: int32 P].
+// LDS: lists_lds_bytes of mcq_search_kernels.h.
 constexpr int kRangeListWaves = 4;        // k_range_lists: waves per workgroup (256 threads), as kListWaves: a table is N*K
                                           // floats (8 KiB at 8 x 256), so several workgroups share a CU and 4 waves each keep
                                           // 4 per SIMD at 4 workgroups per CU (not measured against 8 or 16)
@@ -171,57 +168,16 @@ k_range_lists(const float *__restrict__ tables, const uint8_t *__restrict__ code
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x / S, part = blockIdx.x % S;
     const int NK = N * K;
-    long long *pre = reinterpret_cast<long long *>(range_smem + lists_lds_head(NK));
-    int *lbeg = reinterpret_cast<int *>(pre + P + 1);
-    int *lend = lbeg + P;
-
-    // the query's step space, as k_search_lists forms it: clamped ranges and step counts, then the prefix sums in chunks of
-    // 64 through wave 0
-    for (int e = tid; e < P; e += THREADS) {
-        const int l = probes[(long)q * P + e];
-        long a = 0, z = 0;
-        if (l >= 0 && l < L) {
-            a = list_offsets[l];
-            z = list_offsets[l + 1];
-            a = a < 0 ? 0 : (a > B ? B : a);                 // (defence: a range never leaves [0, B], whatever the offsets hold)
-            z = z < 0 ? 0 : (z > B ? B : z);
-            if (a >= z) a = z = 0;
-        }
-        lbeg[e] = (int)a;
-        lend[e] = (int)z;
-        pre[e + 1] = (z - a + 63) / 64;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        long long carry = 0;
-        for (int c0 = 0; c0 < P; c0 += 64) {
-            const int e = c0 + lane;
-            long long v = e < P ? pre[e + 1] : 0;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const long long u = __shfl_up(v, d, 64);
-                if (lane >= d) v += u;
-            }
-            v += carry;
-            if (e < P) pre[e + 1] = v;
-            carry = __shfl(v, 63, 64);
-        }
-        if (lane == 0) pre[0] = 0;
-    }
-    __syncthreads();
-    const long long T = pre[P];
+    ListWalk walk;
+    const long long T = walk.build<THREADS>(range_smem, NK, list_offsets, L, probes + (long)q * P, P, B, tid);
     const long long lo = T * part / S, hi = T * (part + 1) / S;           // (T <= 2^37, S <= 256)
     int64_t *mine = ws + ((long)q * S + part) * kRangeListWaves;           // this part's kRangeListWaves entries
     if (lo >= hi) {                                          // no step: zeros (COUNT), and nothing is staged
         if (!FILL && tid < kRangeListWaves) mine[tid] = 0;
         return;
     }
-    // the query's table -> LDS.  tile_stage<1, 256> of k_search_lists written out (QT = 1: nothing to interleave, and q < Q by
-    // the grid): a second caller with another LDS array changes what hipcc makes of tile_stage inside every k_search_lists
-    float *stage = reinterpret_cast<float *>(range_smem);
-    for (int e = tid; e < NK; e += THREADS) stage[e] = tables[(long)q * NK + e];
-    __syncthreads();
-    const float *Tl = reinterpret_cast<const float *>(range_smem);
+    float *Tl = reinterpret_cast<float *>(range_smem);
+    tile_stage<1, THREADS>(Tl, tables, q + 1, q, NK, tid);                // (q < Q by the grid)
 
     const long long run = (hi - lo + kRangeListWaves - 1) / kRangeListWaves;   // steps per wave: wave v owns [lo + v*run, ..)
     long long step = lo + wave * run;
@@ -234,58 +190,29 @@ k_range_lists(const float *__restrict__ tables, const uint8_t *__restrict__ code
 
     CodeChunk<CH> cur;
     float t = 0.f;
-    ListWalk walk{pre, lbeg, lend, P, 0};
-    Slice sl{0, 1, 0};
-    long j = 0;
-    if (step < stop) {
-        int a = 0, z = P;                                    // pre[a] <= step < pre[z]
-        while (z - a > 1) {
-            const int mid = (a + z) >> 1;
-            if (pre[mid] <= step) a = mid; else z = mid;
-        }
-        walk.p = a;
-        sl = walk.at(step, j);
-    }
-    tile_first(cur, t, codes, w, metric, N, sl, j, step < stop ? j + 1 : j, lane);
-    long b = step_at(sl, j, lane);
-    bool live = sl.begin + j * 64 + lane < sl.end;
-    u64 word = 0;
-    if constexpr (MASKED) {
-        if (step < stop) word = mask[b >> 6];
-    }
+    ListCursor<MASKED> pos;
+    pos.start(walk, step, stop, cur, t, codes, w, metric, N, mask, lane);
     while (step < stop) {
         const long long nstep = step + 1;
-        long bnext = b;
-        bool live_next = false;
-        if (nstep < stop) {
-            sl = walk.at(nstep, j);
-            bnext = step_at(sl, j, lane);
-            live_next = sl.begin + j * 64 + lane < sl.end;
-        }
-        u64 word_next = 0;
-        if constexpr (MASKED) word_next = mask[bnext >> 6];
+        pos.peek(walk, nstep, stop, mask, lane);
         float tn = t;
         float acc[1];
-        tile_step<1, CH>(acc, cur, tn, Tl, codes, w, metric, N, K, b, bnext);
+        tile_step<1, CH>(acc, cur, tn, Tl, codes, w, metric, N, K, pos.b, pos.bnext);
         const float s = score_finish(acc[0], t, metric);
-        bool offer = live;
-        if constexpr (MASKED) offer = live && ((word >> (b & 63)) & 1);
-        const bool hit = offer && s <= th;                   // rules 7, 15 and 17 (a NaN compares false)
+        const bool hit = pos.offer() && s <= th;             // rules 7, 15 and 17 (a NaN compares false)
         const u64 m = __ballot(hit);
         if constexpr (FILL) {
             if (m) {                                         // (uniform) hits are rare
                 const long slot = base + cnt + __builtin_popcountll(m & below);
                 if (hit && (unsigned long)slot < (unsigned long)capacity) {
                     out_s[slot] = s;
-                    out_i[slot] = b;
+                    out_i[slot] = pos.b;
                 }
             }
         }
         cnt += __builtin_popcountll(m);
         t = tn;
-        b = bnext;
-        live = live_next;
-        word = word_next;
+        pos.advance();
         step = nstep;
     }
 

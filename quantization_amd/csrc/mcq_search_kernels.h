@@ -486,15 +486,122 @@ __host__ __device__ constexpr int lists_lds_head(int NK) {
 }
 __host__ __device__ constexpr int lists_lds_bytes(int NK, int P) { return lists_lds_head(NK) + (P + 1) * 8 + P * 8; }
 
-// the (probe, list) of a step: p walks up until pre[p] <= step < pre[p + 1] (step < pre[P]; probes without a step are passed)
+// The step space of one query, in LDS behind the first region, and the (probe, list) of a step.  build() is called by every
+// thread of a workgroup of THREADS: it lays out pre / begin / end, fills them from the query's row of `probes` and hands back T,
+// the number of steps.  seek() finds a wave's first step by bisection; at() walks p up from there until pre[p] <= step <
+// pre[p + 1] (step < T; probes without a step are passed).  j: the step's offset in its list, in steps.
 struct ListWalk {
-    const long long *pre;
-    const int *lbeg, *lend;
+    long long *pre;
+    int *lbeg, *lend;
     int P, p;
+
+    template <int THREADS>
+    __device__ __forceinline__ long long build(char *smem, int NK, const int64_t *__restrict__ list_offsets, long L,
+                                               const int *__restrict__ row, int P_, long B, int tid) {
+        const int lane = tid & 63, wave = tid >> 6;
+        pre = reinterpret_cast<long long *>(smem + lists_lds_head(NK));
+        lbeg = reinterpret_cast<int *>(pre + P_ + 1);
+        lend = lbeg + P_;
+        P = P_;
+        p = 0;
+        // clamped ranges and step counts, then the prefix sums in chunks of 64 through wave 0
+        for (int e = tid; e < P; e += THREADS) {
+            const int l = row[e];
+            long a = 0, z = 0;
+            if (l >= 0 && l < L) {
+                a = list_offsets[l];
+                z = list_offsets[l + 1];
+                a = a < 0 ? 0 : (a > B ? B : a);             // (defence: a range never leaves [0, B], whatever the offsets hold)
+                z = z < 0 ? 0 : (z > B ? B : z);
+                if (a >= z) a = z = 0;
+            }
+            lbeg[e] = (int)a;
+            lend[e] = (int)z;
+            pre[e + 1] = (z - a + 63) / 64;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            long long carry = 0;
+            for (int c0 = 0; c0 < P; c0 += 64) {
+                const int e = c0 + lane;
+                long long v = e < P ? pre[e + 1] : 0;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const long long u = __shfl_up(v, d, 64);
+                    if (lane >= d) v += u;
+                }
+                v += carry;
+                if (e < P) pre[e + 1] = v;
+                carry = __shfl(v, 63, 64);
+            }
+            if (lane == 0) pre[0] = 0;
+        }
+        __syncthreads();
+        return pre[P];
+    }
+    __device__ __forceinline__ Slice seek(long long step, long &j) {
+        int a = 0, z = P;                                    // pre[a] <= step < pre[z]
+        while (z - a > 1) {
+            const int mid = (a + z) >> 1;
+            if (pre[mid] <= step) a = mid; else z = mid;
+        }
+        p = a;
+        return at(step, j);
+    }
     __device__ __forceinline__ Slice at(long long step, long &j) {
         while (p + 1 < P && pre[p + 1] <= step) ++p;
         j = (long)(step - pre[p]);
         return {lbeg[p], lend[p], 0};
+    }
+};
+
+// This lane's candidate in the current step of a wave, and in the step the wave takes next: the position b (lanes past the
+// end of the list re-read its last candidate, step_at over the list as a Slice), whether it lies inside its list, and under
+// MASKED the mask word that holds its bit (lists do not start at multiples of 64: every lane tests its own).  The kernel owns
+// the steps -- which comes next, and where the wave stops -- and the score; the next step's b is the bnext of tile_step.
+template <bool MASKED>
+struct ListCursor {
+    long b, bnext;
+    bool live, live_next;
+    u64 word, word_next;
+
+    // the wave's first step: its digits and w go to cur and t (tile_first: one step, or none when step >= stop)
+    template <int CH>
+    __device__ __forceinline__ void start(ListWalk &walk, long long step, long long stop, CodeChunk<CH> &cur, float &t,
+                                          const uint8_t *__restrict__ codes, const float *__restrict__ w, int metric, int N,
+                                          const u64 *__restrict__ mask, int lane) {
+        Slice sl{0, 1, 0};
+        long j = 0;
+        if (step < stop) sl = walk.seek(step, j);
+        tile_first(cur, t, codes, w, metric, N, sl, j, step < stop ? j + 1 : j, lane);
+        b = step_at(sl, j, lane);
+        live = sl.begin + j * 64 + lane < sl.end;
+        word = 0;
+        if constexpr (MASKED) {
+            if (step < stop) word = mask[b >> 6];
+        }
+    }
+    // the step after the current one is nstep (none when nstep >= stop: b again, offering nothing)
+    __device__ __forceinline__ void peek(ListWalk &walk, long long nstep, long long stop, const u64 *__restrict__ mask, int lane) {
+        bnext = b;
+        live_next = false;
+        if (nstep < stop) {
+            long j;
+            const Slice sl = walk.at(nstep, j);
+            bnext = step_at(sl, j, lane);
+            live_next = sl.begin + j * 64 + lane < sl.end;
+        }
+        word_next = 0;
+        if constexpr (MASKED) word_next = mask[bnext >> 6];
+    }
+    __device__ __forceinline__ bool offer() const {
+        if constexpr (MASKED) return live && ((word >> (b & 63)) & 1);
+        return live;
+    }
+    __device__ __forceinline__ void advance() {
+        b = bnext;
+        live = live_next;
+        word = word_next;
     }
 };
 
@@ -508,44 +615,8 @@ k_search_lists(const float *__restrict__ tables, int Q, const uint8_t *__restric
     constexpr int THREADS = 64 * kListWaves;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x / S, part = blockIdx.x % S;
-    long long *pre = reinterpret_cast<long long *>(search_smem + lists_lds_head(N * K));
-    int *lbeg = reinterpret_cast<int *>(pre + P + 1);
-    int *lend = lbeg + P;
-
-    // the query's step space: clamped ranges and step counts, then the prefix sums in chunks of 64 through wave 0
-    for (int e = tid; e < P; e += THREADS) {
-        const int l = probes[(long)q * P + e];
-        long a = 0, z = 0;
-        if (l >= 0 && l < L) {
-            a = list_offsets[l];
-            z = list_offsets[l + 1];
-            a = a < 0 ? 0 : (a > B ? B : a);                 // (defence: a range never leaves [0, B], whatever the offsets hold)
-            z = z < 0 ? 0 : (z > B ? B : z);
-            if (a >= z) a = z = 0;
-        }
-        lbeg[e] = (int)a;
-        lend[e] = (int)z;
-        pre[e + 1] = (z - a + 63) / 64;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        long long carry = 0;
-        for (int c0 = 0; c0 < P; c0 += 64) {
-            const int e = c0 + lane;
-            long long v = e < P ? pre[e + 1] : 0;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const long long u = __shfl_up(v, d, 64);
-                if (lane >= d) v += u;
-            }
-            v += carry;
-            if (e < P) pre[e + 1] = v;
-            carry = __shfl(v, 63, 64);
-        }
-        if (lane == 0) pre[0] = 0;
-    }
-    __syncthreads();
-    const long long T = pre[P];
+    ListWalk walk;
+    const long long T = walk.build<THREADS>(search_smem, N * K, list_offsets, L, probes + (long)q * P, P, B, tid);
     const long long lo = T * part / S, hi = T * (part + 1) / S;           // (T <= 2^37, S <= 256)
     if (lo >= hi) {                                          // no step: the empty list, and nothing is staged
         if (tid < k) {
@@ -562,47 +633,18 @@ k_search_lists(const float *__restrict__ tables, int Q, const uint8_t *__restric
     int li = kNoIndex, tb = kNoIndex;
     CodeChunk<CH> cur;
     float t = 0.f;
+    ListCursor<MASKED> pos;
     long long step = lo + wave;
-    ListWalk walk{pre, lbeg, lend, P, 0};
-    Slice sl{0, 1, 0};
-    long j = 0;
-    if (step < hi) {
-        int a = 0, z = P;                                    // pre[a] <= step < pre[z]
-        while (z - a > 1) {
-            const int mid = (a + z) >> 1;
-            if (pre[mid] <= step) a = mid; else z = mid;
-        }
-        walk.p = a;
-        sl = walk.at(step, j);
-    }
-    tile_first(cur, t, codes, w, M, N, sl, j, step < hi ? j + 1 : j, lane);
-    long b = step_at(sl, j, lane);
-    bool live = sl.begin + j * 64 + lane < sl.end;
-    u64 word = 0;
-    if constexpr (MASKED) {
-        if (step < hi) word = mask[b >> 6];
-    }
+    pos.start(walk, step, hi, cur, t, codes, w, M, N, mask, lane);
     while (step < hi) {
         const long long nstep = step + kListWaves;
-        long bnext = b;
-        bool live_next = false;
-        if (nstep < hi) {
-            sl = walk.at(nstep, j);
-            bnext = step_at(sl, j, lane);
-            live_next = sl.begin + j * 64 + lane < sl.end;
-        }
-        u64 word_next = 0;
-        if constexpr (MASKED) word_next = mask[bnext >> 6];
+        pos.peek(walk, nstep, hi, mask, lane);
         float tn = t;
         float acc[1];
-        tile_step<1, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, b, bnext);
-        bool offer = live;
-        if constexpr (MASKED) offer = live && ((word >> (b & 63)) & 1);
-        list_insert(ls, li, ts, tb, score_finish(acc[0], t, M), (int)b, offer, k, lane);
+        tile_step<1, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, pos.b, pos.bnext);
+        list_insert(ls, li, ts, tb, score_finish(acc[0], t, M), (int)pos.b, pos.offer(), k, lane);
         t = tn;
-        b = bnext;
-        live = live_next;
-        word = word_next;
+        pos.advance();
         step = nstep;
     }
 
