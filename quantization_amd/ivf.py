@@ -13,6 +13,8 @@ Where the coarse centroids come from (k-means over a sample, a trained layer) is
 import torch
 from torch import Tensor
 
+from .search import check_metric
+
 __all__ = ["build_lists", "probe_lists"]
 
 
@@ -41,8 +43,7 @@ def probe_lists(queries: Tensor, centroids: Tensor, nprobe: int, metric: str = "
     """queries (*, dim), centroids (L, dim) -> int32 (*, nprobe): per query the nprobe best lists, best first -- the nearest
     centroids under "l2", the largest inner products under "ip", the largest cosines under "cosine".  One matmul and one
     topk; the rows hold distinct lists by construction."""
-    if metric not in ("l2", "ip", "cosine"):
-        raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
+    check_metric(metric)
     if not isinstance(centroids, Tensor) or centroids.ndim != 2 or queries.shape[-1] != centroids.shape[1]:
         raise ValueError(f"centroids: an (L, {queries.shape[-1]}) tensor, not {tuple(getattr(centroids, 'shape', ()))}")
     nprobe = int(nprobe)

@@ -17,6 +17,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
+from .search import SearchMixin
 
 
 # The derived device state (_prepared) is cached per parameter version.  torch's fused optimizers
@@ -80,7 +81,7 @@ def _scale_exp(scale: Tensor, speed: float) -> float:
     return float((scale.detach().to("cpu", torch.float32) * speed).exp())
 
 
-class Quantizer(nn.Module):
+class Quantizer(SearchMixin, nn.Module):
     """Trainable direct-sum (multi-codebook) vector quantizer; quantization.py:16-55."""
 
     def __init__(self, dim: int, codebook_size: int, num_codebooks: int):
@@ -472,437 +473,6 @@ class Quantizer(nn.Module):
                               N, K, D, out.data_ptr(), st)
         _lib.check(rc, "mcq_decode")
         return out
-
-    # ------------------------------------------------- search over stored codes
-    def _search_state(self, dev):
-        """(L, blob, stream) for the search entry points: any flavour of derived state will do (they read the scaled centers)."""
-        self._check_domain()
-        if self.codebook_size > 256:
-            raise _lib.McqError("quantization_amd: the search over stored codes takes one-byte codes (codebook_size <= 256)")
-        with torch.no_grad():
-            blob = self._prepared(any_flavour=True)
-        return _lib.lib(), blob, torch.cuda.current_stream(dev).cuda_stream
-
-    def _unpacked_codes(self, codes: Tensor) -> Tensor:
-        """codes as encode(..., as_bytes=True) returned them -> uint8 (B, num_codebooks), one digit per byte, on the device."""
-        if not codes.is_cuda:
-            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
-        N, K = self.num_codebooks, self.codebook_size
-        flat = codes.reshape(-1, codes.shape[-1])
-        if flat.dtype != torch.uint8:
-            raise _lib.McqError("quantization_amd: the search takes uint8 codes (encode(..., as_bytes=True))")
-        if flat.shape[1] != N:
-            if not (K == 16 and flat.shape[1] * 2 == N):
-                raise _lib.McqError(f"codes of {flat.shape[1]} bytes per vector do not belong to {N} codebooks of {K}")
-            flat = torch.stack([flat & 15, flat >> 4], dim=2).reshape(-1, N)     # low nibble = even codebook (encode's packing)
-        flat = flat.contiguous()
-        if flat.data_ptr() % 16:
-            flat = flat.clone()
-        return flat
-
-    def search_tables(self, queries: Tensor) -> Tensor:
-        """queries (*, dim) fp32 or fp16 -> fp32 (Q, num_codebooks, codebook_size): T[q][n][k] = -2 <q, C[n][k]> (mcq_search_tables)."""
-        if not queries.is_cuda:
-            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
-        N, K, D = self.num_codebooks, self.codebook_size, self.dim
-        q2d = queries.detach().reshape(-1, D)
-        q2d = q2d.contiguous() if q2d.dtype == torch.float16 else q2d.to(torch.float32).contiguous()
-        Q, dev = q2d.shape[0], q2d.device
-        with torch.no_grad(), torch.cuda.device(dev):
-            L, blob, st = self._search_state(dev)
-            out = torch.empty((Q, N, K), dtype=torch.float32, device=dev)
-            rc = L.mcq_search_tables(q2d.data_ptr(), int(q2d.dtype == torch.float16), Q, blob.data_ptr(), N, K, D,
-                                     out.data_ptr(), st)
-        _lib.check(rc, "mcq_search_tables")
-        return out
-
-    def _code_norms(self, codes: Tensor, entry: str) -> Tensor:
-        """code_norms and code_rnorms: `entry` names the library call (mcq_code_norms, mcq_code_rnorms)"""
-        N, K, D = self.num_codebooks, self.codebook_size, self.dim
-        flat = self._unpacked_codes(codes)
-        B, dev = flat.shape[0], flat.device
-        with torch.no_grad(), torch.cuda.device(dev):
-            L, blob, st = self._search_state(dev)
-            out = torch.empty((B,), dtype=torch.float32, device=dev)
-            rc = getattr(L, entry)(flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
-        _lib.check(rc, entry)
-        return out
-
-    def code_norms(self, codes: Tensor) -> Tensor:
-        """codes (*, num_codebooks) uint8 (or packed, codebook_size 16) -> fp32 (B,): |decode(codes[b])|^2 (mcq_code_norms).
-        Formed once per store of codes and handed to search(norms=...)."""
-        return self._code_norms(codes, "mcq_code_norms")
-
-    def code_rnorms(self, codes: Tensor) -> Tensor:
-        """codes as for code_norms -> fp32 (B,): 1 / sqrt(code_norms(codes)), 0 for an all-zero reconstruction (mcq_code_rnorms).
-        What the cosine search multiplies by: formed once per store and handed to search(metric="cosine", rnorms=...)."""
-        return self._code_norms(codes, "mcq_code_rnorms")
-
-    def rnorms_from_norms(self, norms: Tensor) -> Tensor:
-        """norms fp32 (B,) as code_norms returned them -> fp32 (B,): the same values code_rnorms gives, without a gather
-        (mcq_rnorms_from_norms)."""
-        if not norms.is_cuda:
-            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
-        norms = norms.detach().reshape(-1).to(torch.float32).contiguous()
-        dev = norms.device
-        with torch.no_grad(), torch.cuda.device(dev):
-            out = torch.empty_like(norms)
-            rc = _lib.lib().mcq_rnorms_from_norms(norms.data_ptr(), norms.numel(), out.data_ptr(),
-                                                  torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, "mcq_rnorms_from_norms")
-        return out
-
-    _METRICS = {"l2": _lib.MCQ_SEARCH_L2, "ip": _lib.MCQ_SEARCH_IP, "cosine": _lib.MCQ_SEARCH_COS}
-
-    def _search_inputs(self, tables: Tensor, codes: Tensor, w: Tensor, metric: str, *more: Tensor):
-        """What _search_scan and _search_range check and normalise alike: the metric, the per-candidate array it needs, that
-        every tensor (those of `more` too) is on the device -> (tables, codes, w, the ABI's metric value, Q, B, dev)."""
-        N, K = self.num_codebooks, self.codebook_size
-        if metric not in self._METRICS:
-            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
-        if metric == "ip":
-            w = None
-        elif w is None:
-            raise ValueError(f"metric {metric!r} needs the per-candidate array")
-        if not all(t.is_cuda for t in (tables, codes, *more) + (() if w is None else (w,))):
-            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
-        tables = tables.detach().to(torch.float32).contiguous()
-        if w is not None:
-            w = w.detach().to(torch.float32).contiguous()
-        codes = codes.contiguous()
-        if codes.data_ptr() % 16:
-            codes = codes.clone()
-        Q, B, dev = tables.shape[0], codes.shape[0], tables.device
-        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and codes.dtype == torch.uint8
-        assert w is None or tuple(w.shape) == (B,)
-        return tables, codes, w, self._METRICS[metric], Q, B, dev
-
-    @staticmethod
-    def _check_mask(mask, B: int) -> None:
-        """what search and range_search accept as `mask` over a store of B vectors: bool (B,) flags, or the int64 words
-        pack_mask made of them.  Looks at shape and dtype only, so it runs before any device work."""
-        if mask is None:
-            return
-        words = (B + 63) // 64
-        if not isinstance(mask, Tensor) or mask.dtype not in (torch.bool, torch.int64) or mask.ndim != 1:
-            raise ValueError(f"mask: a bool ({B},) tensor or the int64 ({words},) tensor pack_mask returned, not "
-                             f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
-        if mask.dtype == torch.bool and mask.numel() != B:
-            raise ValueError(f"mask of {mask.numel()} flags for a store of {B} vectors")
-        if mask.dtype == torch.int64 and mask.numel() != words:
-            raise ValueError(f"packed mask of {mask.numel()} words for a store of {B} vectors, which takes {words}")
-
-    def pack_mask(self, keep: Tensor) -> Tensor:
-        """keep bool or uint8 (B,), non-zero = the stored vector is a candidate -> int64 (ceil(B / 64),): bit b & 63 of word
-        b >> 6 (mcq_search_pack_mask).  What search(mask=...) and range_search(mask=...) take; pack once, search many times."""
-        if not isinstance(keep, Tensor) or keep.dtype not in (torch.bool, torch.uint8) or keep.ndim != 1:
-            raise ValueError(f"pack_mask: a bool or uint8 (B,) tensor, not {getattr(keep, 'dtype', type(keep))} "
-                             f"{tuple(getattr(keep, 'shape', ()))}")
-        if not keep.is_cuda:
-            raise _lib.McqError("quantization_amd: the search runs on HIP device tensors only (no CPU fallback)")
-        L = _lib.lib()
-        if not hasattr(L, "mcq_search_pack_mask"):
-            raise _lib.McqError(f"{_lib.LIB_PATH} has no masked search (mcq_search_pack_mask)")
-        flags = keep.detach().contiguous().view(torch.uint8)
-        B, dev = flags.numel(), flags.device
-        with torch.no_grad(), torch.cuda.device(dev):
-            out = torch.empty(((B + 63) // 64,), dtype=torch.int64, device=dev)
-            rc = L.mcq_search_pack_mask(flags.data_ptr(), B, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, "mcq_search_pack_mask")
-        return out
-
-    def _mask_words(self, mask):
-        """a mask that passed _check_mask and sits on the device -> its int64 words (None stays None)"""
-        if mask is None or mask.dtype == torch.int64:
-            return None if mask is None else mask.detach().contiguous()
-        return self.pack_mask(mask)
-
-    @staticmethod
-    def _check_lists(lists, Q: int) -> None:
-        """what search_lists accepts as (list_offsets, probes) for Q queries: int64 (L + 1,) and int32 or int64 (Q, P).  Looks
-        at shape and dtype only, so it runs before any device work."""
-        if lists is None:
-            return
-        offsets, probes = lists
-        if not isinstance(offsets, Tensor) or offsets.dtype != torch.int64 or offsets.ndim != 1 or offsets.numel() < 1:
-            raise ValueError(f"list_offsets: an int64 (L + 1,) tensor, not {getattr(offsets, 'dtype', type(offsets))} "
-                             f"{tuple(getattr(offsets, 'shape', ()))}")
-        if not isinstance(probes, Tensor) or probes.dtype not in (torch.int32, torch.int64) or probes.ndim < 1:
-            raise ValueError(f"probes: an int32 or int64 (*, P) tensor, not {getattr(probes, 'dtype', type(probes))} "
-                             f"{tuple(getattr(probes, 'shape', ()))}")
-        rows = torch.Size(probes.shape[:-1]).numel()                   # (a (P,) tensor is the one row of one query)
-        if rows != Q:
-            raise ValueError(f"probes of {rows} rows for {Q} queries")
-
-    @staticmethod
-    def _list_arrays(offsets: Tensor, probes: Tensor):
-        """(list_offsets, probes) that passed _check_lists and sit on the device -> (int64 (L + 1,), int32 (Q, P)) as the
-        library reads them; an int64 entry that names no list becomes -1 before it is narrowed"""
-        offsets = offsets.detach().contiguous()
-        probes = probes.detach().reshape(torch.Size(probes.shape[:-1]).numel(), probes.shape[-1])
-        if probes.dtype == torch.int64:
-            named = (probes >= 0) & (probes < offsets.numel() - 1)
-            probes = torch.where(named, probes, torch.full_like(probes, -1)).to(torch.int32)
-        return offsets, probes.contiguous()
-
-    def _metric_array(self, metric: str, flat: Tensor, norms, rnorms):
-        """the per-candidate array of a metric, from what the caller handed in or else from the codes: norms (l2), none (ip),
-        reciprocal roots (cosine: rnorms, or norms converted on the device, or code_rnorms)"""
-        if metric == "ip":
-            return None
-        if metric == "l2":
-            return self.code_norms(flat) if norms is None else norms.reshape(-1)
-        if rnorms is not None:
-            return rnorms.reshape(-1)
-        return self.code_rnorms(flat) if norms is None else self.rnorms_from_norms(norms)
-
-    def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int, metric: str = "l2", mask: Tensor = None,
-                     lists=None):
-        """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, norms fp32 (B,) -> (scores fp32 (Q, k), indexes int64 (Q, k)):
-        the k smallest score[q][b] = sum_n tables[q][n][codes[b][n]] + norms[b] under (score, b) ascending (mcq_search_scan).
-        metric "ip": the score is the sum alone and `norms` is not looked at (None will do); "cosine": `norms` holds the
-        reciprocal roots (code_rnorms) and the score is the sum times norms[b] (mcq_search_scan_metric).
-        mask: bool (B,) or the words of pack_mask: the k smallest among the positions whose bit is set
-        (mcq_search_scan_masked); None calls what it called before masks existed.
-        lists: (list_offsets int64 (L + 1,), probes (Q, P) int32 or int64) as search_lists takes them: the k smallest among
-        the positions of the lists row q of `probes` names, under the mask if there is one (mcq_search_scan_lists)."""
-        N, K = self.num_codebooks, self.codebook_size
-        self._check_mask(mask, codes.shape[0])
-        self._check_lists(lists, tables.shape[0])
-        more = (() if mask is None else (mask,)) + (() if lists is None else tuple(lists))
-        tables, codes, norms, m, Q, B, dev = self._search_inputs(tables, codes, norms, metric, *more)
-        L = _lib.lib()
-        if mask is not None and not hasattr(L, "mcq_search_scan_masked"):
-            raise _lib.McqError(f"{_lib.LIB_PATH} has no masked search (mcq_search_scan_masked)")
-        if lists is not None and not hasattr(L, "mcq_search_scan_lists"):
-            raise _lib.McqError(f"{_lib.LIB_PATH} has no search by lists (mcq_search_scan_lists)")
-        with torch.no_grad(), torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
-            indexes = torch.empty((Q, k), dtype=torch.int64, device=dev)
-            if lists is not None:
-                offsets, probes = self._list_arrays(*lists)
-                nl, P = offsets.numel() - 1, probes.shape[1]
-                ws = torch.empty(L.mcq_search_lists_workspace_bytes(Q, P, N, K, k), dtype=torch.uint8, device=dev)
-                words = self._mask_words(mask)
-                rc = L.mcq_search_scan_lists(tables.data_ptr(), Q, codes.data_ptr(), None if norms is None else norms.data_ptr(),
-                                             B, N, K, int(k), m, None if words is None else words.data_ptr(), offsets.data_ptr(),
-                                             nl, probes.data_ptr(), P, scores.data_ptr(), indexes.data_ptr(), ws.data_ptr(),
-                                             ws.numel(), st)
-                _lib.check(rc, "mcq_search_scan_lists")
-                return scores, indexes
-            ws = torch.empty(L.mcq_search_workspace_bytes(Q, B, N, K, k), dtype=torch.uint8, device=dev)
-            entry = "mcq_search_scan" if metric == "l2" else "mcq_search_scan_metric"
-            if mask is not None:
-                entry, words = "mcq_search_scan_masked", self._mask_words(mask)
-                rc = L.mcq_search_scan_masked(tables.data_ptr(), Q, codes.data_ptr(), None if norms is None else norms.data_ptr(),
-                                              B, N, K, int(k), m, words.data_ptr(), scores.data_ptr(), indexes.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), st)
-            elif metric == "l2":
-                rc = L.mcq_search_scan(tables.data_ptr(), Q, codes.data_ptr(), norms.data_ptr(), B, N, K, int(k),
-                                       scores.data_ptr(), indexes.data_ptr(), ws.data_ptr(), ws.numel(), st)
-            else:
-                rc = L.mcq_search_scan_metric(tables.data_ptr(), Q, codes.data_ptr(), None if norms is None else norms.data_ptr(),
-                                              B, N, K, int(k), m, scores.data_ptr(), indexes.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), st)
-        _lib.check(rc, entry)
-        return scores, indexes
-
-    def search(self, queries: Tensor, codes: Tensor, k: int = 10, norms: Tensor = None, metric: str = "l2",
-               rnorms: Tensor = None, mask: Tensor = None):
-        """The k stored vectors nearest to each query, from the codes alone (nothing is decoded).
-        queries (*, dim) fp32 or fp16; codes (B, num_codebooks) uint8 as encode(..., as_bytes=True) returned them (packed
-        16-entry codes are unpacked first); norms = code_norms(codes) when not given (pass them in when searching repeatedly).
-        -> (distances fp32 (*, k), indexes int64 (*, k)): |q - decode(codes[b])|^2 clamped at 0, nearest first, the lower
-        position first among equal scores; with fewer than k stored vectors the tail is (+inf, -1).  Not differentiable.
-        metric="ip": -> (similarities, indexes), <q, decode(codes[b])>, largest first; norms are neither needed nor formed.
-        metric="cosine": -> (similarities, indexes), cos(q, decode(codes[b])), largest first, 0 for a zero query or an
-        all-zero reconstruction; it multiplies by rnorms = code_rnorms(codes): pass them in when searching repeatedly, or pass
-        norms and they are converted on the device (rnorms_from_norms), else code_rnorms(codes) is run.
-        Under both the lower position comes first among equal scores and the tail of a short store is (-inf, -1).
-        mask: search only the stored vectors it keeps -- a bool (B,) tensor (packed for this call), or the int64 tensor
-        pack_mask made of one (reused across calls); B counts stored vectors, for packed 16-entry codes as well.  Indexes
-        stay positions in `codes`, the result is that of a search over codes[mask] mapped back, and with fewer than k kept
-        vectors the tail is the short store's.  Nothing is copied: steps of 64 vectors without a kept one are skipped."""
-        return self._search_topk(queries, codes, k, norms, metric, rnorms, mask)
-
-    def search_lists(self, queries: Tensor, codes: Tensor, list_offsets: Tensor, probes: Tensor, k: int = 10,
-                     norms: Tensor = None, metric: str = "l2", rnorms: Tensor = None, mask: Tensor = None):
-        """search() over an inverted file: the store is kept in list order and each query is scored against the lists it
-        probes and no others (quantization_amd.ivf.build_lists orders a store, probe_lists picks the lists).
-        list_offsets int64 (L + 1,): list l is the positions [list_offsets[l], list_offsets[l + 1]) of `codes`; probes (*, P)
-        int32 or int64, one row per query with the leading dimensions of `queries`: an entry in [0, L) names a list, any
-        other value (-1 is the padding) names none, and a row holds distinct lists.
-        Everything else is search()'s: the arguments, the three metrics, the return values, the clamping, the order among
-        equal scores, the tail of a query with fewer than k candidates, and the mask (a stored vector is a candidate iff it
-        lies in a probed list AND the mask keeps it: a delete clears one bit, whatever list the vector sits in).  Indexes
-        are positions in `codes`, that is in list order (map them through build_lists' `order` for the original ones).
-        Row q equals search(queries[q], ..., mask=the union of its lists); the cost falls with the probed share."""
-        return self._search_topk(queries, codes, k, norms, metric, rnorms, mask, (list_offsets, probes))
-
-    def _search_topk(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask, lists=None):
-        """search() and search_lists(): `lists` is None or (list_offsets, probes)"""
-        if metric not in self._METRICS:
-            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
-        self._check_mask(mask, codes.reshape(-1, codes.shape[-1]).shape[0])
-        self._check_lists(lists, queries.numel() // max(queries.shape[-1], 1))
-        if metric != "l2":
-            return self._search_similarity(queries, codes, k, norms, metric, rnorms, mask, lists)
-        with torch.no_grad():
-            flat = self._unpacked_codes(codes)
-            w = self._metric_array("l2", flat, norms, None)
-            tables = self.search_tables(queries)
-            scores, indexes = self._search_scan(tables, flat, w, k, mask=mask, lists=lists)
-            q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
-            dist = (scores + (q2d * q2d).sum(dim=1, keepdim=True)).clamp_(min=0.0)
-        lead = queries.shape[:-1]
-        return dist.reshape(*lead, k), indexes.reshape(*lead, k)
-
-    def _search_similarity(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask=None, lists=None):
-        """search() under "ip" and "cosine": the scan's scores are -2 <q, x^> and -2 |q| cos; halving is exact"""
-        with torch.no_grad():
-            flat = self._unpacked_codes(codes)
-            w = self._metric_array(metric, flat, norms, rnorms)
-            tables = self.search_tables(queries)
-            scores, indexes = self._search_scan(tables, flat, w, k, metric=metric, mask=mask, lists=lists)
-            sim = scores * -0.5
-            if metric == "cosine":
-                q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
-                qn = (q2d * q2d).sum(dim=1, keepdim=True).sqrt_()
-                sim = sim / qn.masked_fill_(qn == 0, 1.0)          # (a zero query: every score is a zero, and so is 0 / 1)
-        lead = queries.shape[:-1]
-        return sim.reshape(*lead, k), indexes.reshape(*lead, k)
-
-    # ------------------------------------------------- range search over stored codes
-    def _search_range(self, tables: Tensor, codes: Tensor, w: Tensor, thr: Tensor, metric: str = "l2",
-                      max_results: int = None, mask: Tensor = None, lists=None):
-        """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, w as _search_scan takes it under the metric (norms, None,
-        reciprocal roots), thr fp32 (Q,) -> (lims int64 (Q + 1,), scores fp32 (total,), indexes int64 (total,)): every b with
-        score[q][b] <= thr[q], the entries of query q at [lims[q], lims[q+1]) in ascending position (mcq_search_range_count,
-        one host synchronisation to read lims[Q], mcq_search_range_fill).  More than max_results entries: McqError.
-        mask as _search_scan takes it: only positions whose bit is set are listed (mcq_search_range_count_masked and
-        mcq_search_range_fill_masked, with the same words).
-        lists: (list_offsets, probes) as _search_scan takes them: every such b among the positions of the lists row q of
-        `probes` names, under the mask if there is one, IN THE ORDER OF THE ROW -- slot 0's list first, ascending position
-        within a list (mcq_search_range_lists_count and mcq_search_range_lists_fill)."""
-        N, K = self.num_codebooks, self.codebook_size
-        self._check_mask(mask, codes.shape[0])
-        self._check_lists(lists, tables.shape[0])
-        more = (() if mask is None else (mask,)) + (() if lists is None else tuple(lists))
-        tables, codes, w, m, Q, B, dev = self._search_inputs(tables, codes, w, metric, thr, *more)
-        L = _lib.lib()
-        count, fill = "mcq_search_range_count", "mcq_search_range_fill"
-        if lists is not None:
-            count, fill = "mcq_search_range_lists_count", "mcq_search_range_lists_fill"
-            if not hasattr(L, count):
-                raise _lib.McqError(f"{_lib.LIB_PATH} has no range search by lists ({count})")
-        elif mask is not None:
-            count, fill = count + "_masked", fill + "_masked"
-        if not hasattr(L, count):
-            raise _lib.McqError(f"{_lib.LIB_PATH} has no {'masked ' if mask is not None else ''}range search ({count})")
-        thr = thr.detach().reshape(-1).to(torch.float32).contiguous()
-        assert tuple(thr.shape) == (Q,)
-        with torch.no_grad(), torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            lims = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
-            args = (tables.data_ptr(), Q, codes.data_ptr(), None if w is None else w.data_ptr(), B, N, K, m)
-            words = self._mask_words(mask)                        # (alive until the fill has been enqueued)
-            if lists is not None:
-                offsets, probes = self._list_arrays(*lists)       # (alive likewise)
-                nl, P = offsets.numel() - 1, probes.shape[1]
-                ws = torch.empty(L.mcq_search_range_lists_workspace_bytes(Q, P, N, K), dtype=torch.uint8, device=dev)
-                args += (None if words is None else words.data_ptr(), offsets.data_ptr(), nl, probes.data_ptr(), P)
-            else:
-                ws = torch.empty(L.mcq_search_range_workspace_bytes(Q, B, N, K), dtype=torch.uint8, device=dev)
-                if mask is not None:
-                    args += (words.data_ptr(),)
-            args += (thr.data_ptr(), lims.data_ptr())
-            _lib.check(getattr(L, count)(*args, ws.data_ptr(), ws.numel(), st), count)
-            total = int(lims[Q])                                  # the one host synchronisation: the result is allocated next
-            if max_results is not None and total > max_results:
-                raise _lib.McqError(f"range search: {total} results exceed max_results = {max_results}")
-            scores = torch.empty((total,), dtype=torch.float32, device=dev)
-            indexes = torch.empty((total,), dtype=torch.int64, device=dev)
-            _lib.check(getattr(L, fill)(*args, scores.data_ptr(), indexes.data_ptr(), total, ws.data_ptr(), ws.numel(), st), fill)
-        return lims, scores, indexes
-
-    def range_search(self, queries: Tensor, codes: Tensor, radius, norms: Tensor = None, metric: str = "l2",
-                     rnorms: Tensor = None, max_results: int = 1 << 26, mask: Tensor = None):
-        """Every stored vector within `radius` of each query, from the codes alone (nothing is decoded).
-        queries (*, dim) fp32 or fp16, flattened to Q rows; codes, norms and rnorms exactly as search takes them; radius a
-        Python float or a tensor of Q values.
-        -> (lims int64 (Q + 1,), values fp32 (total,), indexes int64 (total,)): CSR, the results of query q are
-        values[lims[q]:lims[q+1]] and indexes[lims[q]:lims[q+1]], IN ASCENDING POSITION (sort a query's values within its
-        lims for nearest first); values are what search reports for the same (query, position).
-        metric="l2": radius is a SQUARED distance, as search returns them; a vector is listed iff its score
-        sum_n T[n][code] + norm <= radius - |q|^2 in fp32, so a reported distance may exceed radius by the rounding of |q|^2.
-        metric="ip": listed iff <q, decode(codes[b])> >= radius.  metric="cosine": listed iff cos >= radius; a zero query has
-        every similarity 0: everything is listed when radius <= 0 and nothing otherwise.
-        One host synchronisation (reading lims[Q]) separates counting from filling; more than max_results entries raise
-        McqError, naming the count, before anything is allocated for them.  Not differentiable.
-        mask: as search takes it; only stored vectors it keeps are listed, at their positions in `codes`."""
-        return self._range_search(queries, codes, radius, norms, metric, rnorms, max_results, mask)
-
-    def range_search_lists(self, queries: Tensor, codes: Tensor, list_offsets: Tensor, probes: Tensor, radius,
-                           norms: Tensor = None, metric: str = "l2", rnorms: Tensor = None, max_results: int = 1 << 26,
-                           mask: Tensor = None):
-        """range_search() over an inverted file: every stored vector within `radius` of each query AMONG THE LISTS IT PROBES
-        (quantization_amd.ivf.build_lists orders a store, probe_lists picks the lists).
-        list_offsets and probes exactly as search_lists takes them: int64 (L + 1,), and (*, P) int32 or int64 with one row
-        per query, an entry in [0, L) naming a list and any other value (-1 is the padding) none.  Everything else is
-        range_search()'s: radius (float or a tensor of Q values) and what it means under each metric, the thresholds, the
-        returned values and their clamping, max_results, the one host synchronisation, and the mask (a stored vector is listed
-        iff it lies in a probed list AND the mask keeps it AND it is within the radius).
-        -> (lims int64 (Q + 1,), values fp32 (total,), indexes int64 (total,)): CSR; indexes are positions in `codes`, that
-        is in list order (map them through build_lists' `order` for the original ones).
-        This method sorts each probe row ascending before the call (entries that name no list stay out of the way), so the
-        results of a query are IN ASCENDING POSITION and row q equals range_search(queries[q], ..., mask=the union of its
-        lists).  The C entry (mcq_search_range_lists_count / _fill) keeps the row's own order: slot 0's list first.  A list
-        named twice in a row is listed twice.  The cost falls with the probed share; nothing sweeps the whole store."""
-        self._check_lists((list_offsets, probes), queries.numel() // max(queries.shape[-1], 1))
-        offsets, rows = self._list_arrays(list_offsets, probes)
-        return self._range_search(queries, codes, radius, norms, metric, rnorms, max_results, mask,
-                                  (offsets, torch.sort(rows, dim=1).values))
-
-    def _range_search(self, queries: Tensor, codes: Tensor, radius, norms, metric: str, rnorms, max_results, mask, lists=None):
-        """range_search() and range_search_lists(): `lists` is None or (list_offsets, probes)"""
-        if metric not in self._METRICS:
-            raise ValueError(f"metric {metric!r}: one of 'l2', 'ip', 'cosine'")
-        self._check_mask(mask, codes.reshape(-1, codes.shape[-1]).shape[0])
-        self._check_lists(lists, queries.numel() // max(queries.shape[-1], 1))
-        with torch.no_grad():
-            flat = self._unpacked_codes(codes)
-            tables = self.search_tables(queries)
-            Q, dev = tables.shape[0], tables.device
-            if isinstance(radius, Tensor):
-                if radius.numel() != Q:
-                    raise ValueError(f"radius of {radius.numel()} values for {Q} queries")
-                rad = radius.detach().reshape(-1).to(device=dev, dtype=torch.float32)
-            else:
-                rad = torch.full((Q,), float(radius), dtype=torch.float32, device=dev)
-            q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
-            qq = (q2d * q2d).sum(dim=1, keepdim=True)
-            w = self._metric_array(metric, flat, norms, rnorms)
-            qn = None
-            if metric == "l2":
-                thr = rad - qq[:, 0]
-            elif metric == "ip":
-                thr = rad * -2.0
-            else:
-                qn = qq.sqrt()
-                thr = rad * -2.0 * qn[:, 0]
-                zero = qn[:, 0] == 0                               # every similarity of a zero query is 0
-                thr = torch.where(zero, torch.where(rad <= 0, float("inf"), float("-inf")).to(thr.dtype), thr)
-                qn = qn.masked_fill(qn == 0, 1.0)
-            lims, scores, indexes = self._search_range(tables, flat, w, thr, metric, max_results, mask, lists)
-            rows = torch.repeat_interleave(torch.arange(Q, device=dev), lims[1:] - lims[:-1], output_size=scores.numel())
-            if metric == "l2":
-                values = (scores + qq[:, 0][rows]).clamp_(min=0.0)
-            else:
-                values = scores * -0.5
-                if metric == "cosine":
-                    values = values / qn[:, 0][rows]
-        return lims, values, indexes
 
     def logits_kernel(self, x: Tensor) -> Tensor:
         """Logits as the index-search kernel forms them (test hook; mcq_logits)."""
