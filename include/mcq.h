@@ -495,6 +495,12 @@ int mcq_search_range_lists_fill(const float *tables, long Q, const uint8_t *code
                                 const float *thr, const int64_t *lims, float *out_score, int64_t *out_index, long capacity,
                                 void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- residual codes list by list: include/mcq_residual.h -----------------------------
+ * An inverted file whose lists keep the codes of x - centroid takes one more operand per (query, probe slot) and norms
+ * formed over a base row.  Those entry points -- the list-by-list calls of rules 13-20 with a probe_bias argument, and the
+ * code norms with a base row -- and rules 21-23 of the contract are declared in include/mcq_residual.h, which includes this
+ * header.  Nothing declared here changes: MCQ_ABI_VERSION stays 7.                                                         */
+
 /* ---- test / profiling hooks -------------------------------------------------
  * Logits of Quantizer._logits (:277-279) for a batch, fp32 [B][N*K]; used by the
  * parity tests to localise a divergence.                                       */

@@ -8,6 +8,6 @@ from .quantizer import Quantizer  # noqa: F401
 from .trainer import QuantizerTrainer  # noqa: F401
 from .prediction import JointCodebookLoss  # noqa: F401   (the consumer of the codes, quantization/__init__.py:4)
 from .hdf5_data import read_hdf5_data  # noqa: F401      (the data helper, quantization/__init__.py:3)
-from .ivf import build_lists, probe_lists  # noqa: F401   (an inverted file over a store of codes: Quantizer.search_lists, range_search_lists)
+from .ivf import build_lists, probe_lists, probe_bias, list_assign  # noqa: F401   (an inverted file over a store of codes: Quantizer.search_lists, range_search_lists)
 
-__all__ = ["Quantizer", "QuantizerTrainer", "JointCodebookLoss", "read_hdf5_data", "build_lists", "probe_lists"]
+__all__ = ["Quantizer", "QuantizerTrainer", "JointCodebookLoss", "read_hdf5_data", "build_lists", "probe_lists", "probe_bias", "list_assign"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h).
+"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companion include/mcq_residual.h).
 
 The library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950).  There
 is no CPU fallback: a missing library or a non-HIP tensor is an error.
@@ -90,6 +90,17 @@ SIGNATURES = {
 }
 SYMBOLS = tuple(SIGNATURES)     # every symbol include/mcq.h declares
 
+# include/mcq_residual.h, the companion header of the search over residual codes, in the same form and in its order
+# (tests/test_search_bias_host.py parses that header and compares)
+RESIDUAL_SIGNATURES = {
+    "mcq_search_scan_lists_bias": _sig("i", "plppliiiipplpippppzp"),
+    "mcq_search_range_lists_bias_count": _sig("i", "plppliiipplpippppzp"),
+    "mcq_search_range_lists_bias_fill": _sig("i", "plppliiipplpippppplpzp"),
+    "mcq_code_norms_based": _sig("i", "plpiiiplppp"),
+    "mcq_code_rnorms_based": _sig("i", "plpiiiplppp"),
+}
+RESIDUAL_SYMBOLS = tuple(RESIDUAL_SIGNATURES)
+
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
 MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
@@ -109,7 +120,7 @@ def lib():
         raise McqError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950); quantization_amd has no CPU fallback")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES}.items():
         # an older build loaded through the A/B hook above may lack a symbol: it stays unbound, and calling it raises.
         # Without the hook a missing symbol fails here, at load
         if _ALT and not hasattr(L, name):

@@ -2,6 +2,7 @@
 // trainer's loss and update kernels, search and range search over stored codes.  Host side only: argument checks, launch
 // arithmetic, kernel selection; every entry point enqueues on the caller's stream and returns (mcq.h has the contract).
 #include "../../include/mcq.h"
+#include "../../include/mcq_residual.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
 #include "mcq_loss_kernels.h"
@@ -919,6 +920,7 @@ struct ListsIn {
     long L;
     const int32_t *probes;
     int P;
+    const float *bias = nullptr;              // rule 21: float[Q][P], one value per (query, probe slot); NULL: none
 };
 
 // What every scan, sweep and list-by-list entry point rejects, in this order (tests/test_search_host.py, test_search_metric_host.py,
@@ -926,7 +928,8 @@ struct ListsIn {
 // nothing touches the device.  k: 1 where the entry has none.  outs_ok: the outputs this call writes are there (the caller
 // knows which of them an empty call still writes).  *empty: the call has no candidate anywhere (Q or B is 0; with lists, L or
 // P) -- it reads no input, so none is looked at.  mask: NULL where the call has none (rule 12); one that is there is read as
-// 8-byte words.  li: the limits of rule 16 come between B's and the outputs, its pointers and alignments with the others.
+// 8-byte words.  li: the limits of rule 16 come between B's and the outputs, its pointers and alignments with the others
+// (a bias, rule 23, is optional: only its alignment is looked at, last).
 int search_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
                  const uint64_t *mask, const ListsIn *li, bool outs_ok, const void *workspace, bool *empty) {
     *empty = false;
@@ -948,6 +951,7 @@ int search_check(const float *tables, long Q, const uint8_t *codes, const float 
     if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
     if (reinterpret_cast<uintptr_t>(mask) % 8 != 0) return MCQ_EINVAL;
     if (li && (reinterpret_cast<uintptr_t>(li->list_offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(li->probes) % 4 != 0)) return MCQ_EINVAL;
+    if (li && reinterpret_cast<uintptr_t>(li->bias) % 4 != 0) return MCQ_EINVAL;
     return 0;
 }
 
@@ -962,6 +966,23 @@ int code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K,
     const Prepared P = prepared_view(prepared, N, K, D);
     hipLaunchKernelGGL(k_code_norms<RNORM>, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
                        static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), out);
+    return launch_rc();
+}
+
+// mcq_code_norms_based (t[b]) and mcq_code_rnorms_based (RNORM: r[b]): rule 22, the norms of base[assign[b]] + decode(codes[b])
+template <bool RNORM>
+int code_norms_based(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, const float *base, long L,
+                     const int32_t *assign, float *out, void *stream) {
+    if (const int rc = search_domain(N, K, D)) return rc;
+    if (B < 0) return MCQ_EINVAL;
+    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (L < 0) return MCQ_EINVAL;
+    if (B == 0) return 0;
+    if (!codes || !prepared || !out || !base || !assign) return MCQ_EINVAL;
+    if (reinterpret_cast<uintptr_t>(base) % 4 != 0 || reinterpret_cast<uintptr_t>(assign) % 4 != 0) return MCQ_EINVAL;
+    const Prepared P = prepared_view(prepared, N, K, D);
+    hipLaunchKernelGGL(k_code_norms_based<RNORM>, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
+                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), base, L, D, assign, out);
     return launch_rc();
 }
 
@@ -1068,6 +1089,28 @@ int launch_lists(const ListsPlan &p, hipStream_t st, const float *tables, int Q,
     });
 }
 
+// launch_lists with a bias (li.bias != NULL; rules 21 and 23): the sibling kernel over the same selection -- tests/search_bias_grid.py
+// reads these value lists as tests/search_selection_grid.py reads those above
+int launch_lists_bias(const ListsPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
+                      int N, int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
+    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
+            return pick_bool(mask != nullptr, [&](auto masked) {
+                constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
+                constexpr bool MASKED = masked;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_lists_bias<NN, M, MASKED>),
+                                                     lists_lds_bytes(64 * 256, kListMaxProbes)))
+                    return rc;
+                hipLaunchKernelGGL((k_search_lists_bias<NN, M, MASKED>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kListWaves),
+                                   p.lds, st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, li.list_offsets, li.L,
+                                   li.probes, li.P, li.bias, ws_s, ws_i, reinterpret_cast<const u64 *>(mask));
+                return launch_rc();
+            });
+        });
+    });
+}
+
 // every top-k entry point: the scan over the whole store (rules 1-6 and 10-12), or list by list (li; rules 13-16)
 int search_topk(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
                 const uint64_t *mask, const ListsIn *li, float *out_score, int64_t *out_index, void *workspace,
@@ -1089,7 +1132,9 @@ int search_topk(const float *tables, long Q, const uint8_t *codes, const float *
     if (!empty && li) {
         const ListsPlan p = lists_plan(Q, li->P, N, K, k);
         if (!split(p.ws_half)) return MCQ_EWORKSPACE;
-        if (const int rc = launch_lists(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, *li, ws_s, ws_i)) return rc;
+        if (const int rc = (li->bias ? launch_lists_bias : launch_lists)(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, *li,
+                                                                           ws_s, ws_i))
+            return rc;
         S = p.parts;
     } else if (!empty) {
         const ScanPlan p = scan_plan(Q, B, N, K, k);
@@ -1186,6 +1231,26 @@ int launch_range_lists(const RangeListsPlan &p, hipStream_t st, const RangeArgs 
     });
 }
 
+// launch_range_lists with a bias (li.bias != NULL; rules 21 and 23): the sibling kernel over the same selection
+template <bool FILL>
+int launch_range_lists_bias(const RangeListsPlan &p, hipStream_t st, const RangeArgs &a, const ListsIn &li) {
+    return pick<1, 2, 4, 8>(a.N < 8 ? a.N : 8, [&](auto ch) {
+        return pick_bool(a.mask != nullptr, [&](auto masked) {
+            constexpr int CH = decltype(ch)::value;
+            constexpr bool MASKED = masked;
+            static bool allowed[64] = {};
+            if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_lists_bias<CH, FILL, MASKED>),
+                                                 lists_lds_bytes(64 * 256, kListMaxProbes)))
+                return rc;
+            hipLaunchKernelGGL((k_range_lists_bias<CH, FILL, MASKED>), dim3((unsigned)a.Q * (unsigned)p.parts),
+                               dim3(64 * kRangeListWaves), p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts,
+                               li.list_offsets, li.L, li.probes, li.P, li.bias, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity,
+                               reinterpret_cast<const u64 *>(a.mask));
+            return launch_rc();
+        });
+    });
+}
+
 // rules 9 and 19: what every range entry point rejects -- search_check without k (lims is written even by an empty call),
 // then thr and the size of the workspace; nothing touches the device
 int range_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
@@ -1204,7 +1269,7 @@ int launch_range_any(hipStream_t st, const RangeArgs &a, const ListsIn *li, int 
     if (li) {
         const RangeListsPlan p = range_lists_plan(a.Q, li->P, a.N, a.K);
         if (per) *per = p.parts * kRangeListWaves;
-        return launch_range_lists<FILL>(p, st, a, *li);
+        return li->bias ? launch_range_lists_bias<FILL>(p, st, a, *li) : launch_range_lists<FILL>(p, st, a, *li);
     }
     const RangePlan p = range_plan(a.Q, a.B, a.N, a.K);
     if (per) *per = p.slices * kRangeWaves;
@@ -1928,6 +1993,42 @@ int mcq_search_range_lists_fill(const float *tables, long Q, const uint8_t *code
     const ListsIn li{list_offsets, L, probes, P};
     return range_fill(tables, Q, codes, w, B, N, K, metric, mask, &li, thr, lims, out_score, out_index, capacity, workspace,
                       workspace_bytes, stream);
+}
+
+// ---- rules 21-23: residual codes list by list.  probe_bias == NULL is the entry without one: the same launches
+int mcq_search_scan_lists_bias(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
+                               int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes, int P,
+                               const float *probe_bias, float *out_score, int64_t *out_index, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+    const ListsIn li{list_offsets, L, probes, P, probe_bias};
+    return search_topk(tables, Q, codes, w, B, N, K, k, metric, mask, &li, out_score, out_index, workspace, workspace_bytes, stream);
+}
+
+int mcq_search_range_lists_bias_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                      int metric, const uint64_t *mask, const int64_t *list_offsets, long L,
+                                      const int32_t *probes, int P, const float *probe_bias, const float *thr, int64_t *lims,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
+    const ListsIn li{list_offsets, L, probes, P, probe_bias};
+    return range_count(tables, Q, codes, w, B, N, K, metric, mask, &li, thr, lims, workspace, workspace_bytes, stream);
+}
+
+int mcq_search_range_lists_bias_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
+                                     int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes,
+                                     int P, const float *probe_bias, const float *thr, const int64_t *lims, float *out_score,
+                                     int64_t *out_index, long capacity, void *workspace, size_t workspace_bytes, void *stream) {
+    const ListsIn li{list_offsets, L, probes, P, probe_bias};
+    return range_fill(tables, Q, codes, w, B, N, K, metric, mask, &li, thr, lims, out_score, out_index, capacity, workspace,
+                      workspace_bytes, stream);
+}
+
+int mcq_code_norms_based(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, const float *base, long L,
+                         const int32_t *assign, float *norms_out, void *stream) {
+    return code_norms_based<false>(codes, B, prepared, N, K, D, base, L, assign, norms_out, stream);
+}
+
+int mcq_code_rnorms_based(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, const float *base, long L,
+                          const int32_t *assign, float *rnorms_out, void *stream) {
+    return code_norms_based<true>(codes, B, prepared, N, K, D, base, L, assign, rnorms_out, stream);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

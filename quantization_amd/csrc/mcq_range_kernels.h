@@ -221,6 +221,74 @@ k_range_lists(const float *__restrict__ tables, const uint8_t *__restrict__ code
     }
 }
 
+// k_range_lists with probe_bias float[Q][P] (rules 21-23; ListCursorBias of mcq_search_kernels.h): a sibling, so that the
+// kernel above keeps its text.  The same step space, runs, counts and slots; s = score_finish(S + bias of the step's slot, w).
+template <int CH, bool FILL, bool MASKED>
+__global__ void __launch_bounds__(64 * kRangeListWaves)
+k_range_lists_bias(const float *__restrict__ tables, const uint8_t *__restrict__ codes, const float *__restrict__ w, long B,
+                   int N, int K, int metric, int S, const int64_t *__restrict__ list_offsets, long L,
+                   const int *__restrict__ probes, int P, const float *__restrict__ probe_bias, const float *__restrict__ thr,
+                   int64_t *__restrict__ ws, const int64_t *__restrict__ lims, float *__restrict__ out_s,
+                   int64_t *__restrict__ out_i, long capacity, const u64 *__restrict__ mask) {
+    extern __shared__ __attribute__((aligned(16))) char range_smem[];
+    constexpr int THREADS = 64 * kRangeListWaves;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x / S, part = blockIdx.x % S;
+    const int NK = N * K;
+    ListWalk walk;
+    const long long T = walk.build<THREADS>(range_smem, NK, list_offsets, L, probes + (long)q * P, P, B, tid);
+    const long long lo = T * part / S, hi = T * (part + 1) / S;           // (T <= 2^37, S <= 256)
+    int64_t *mine = ws + ((long)q * S + part) * kRangeListWaves;           // this part's kRangeListWaves entries
+    if (lo >= hi) {                                          // no step: zeros (COUNT), and nothing is staged
+        if (!FILL && tid < kRangeListWaves) mine[tid] = 0;
+        return;
+    }
+    float *Tl = reinterpret_cast<float *>(range_smem);
+    tile_stage<1, THREADS>(Tl, tables, q + 1, q, NK, tid);                // (q < Q by the grid)
+    const float *brow = probe_bias + (long)q * P;
+
+    const long long run = (hi - lo + kRangeListWaves - 1) / kRangeListWaves;   // steps per wave: wave v owns [lo + v*run, ..)
+    long long step = lo + wave * run;
+    const long long stop = step + run < hi ? step + run : hi;
+    const float th = thr[q];
+    const u64 below = (1ull << lane) - 1;
+    long base = 0;                                           // FILL: the slot of this wave's first hit
+    if constexpr (FILL) base = lims[q] + mine[wave];
+    long cnt = 0;                                            // (uniform) this wave's hits so far (a list named twice counts twice)
+
+    CodeChunk<CH> cur;
+    float t = 0.f;
+    ListCursorBias<MASKED> pos;
+    pos.start(walk, step, stop, cur, t, codes, w, metric, N, mask, brow, lane);
+    while (step < stop) {
+        const long long nstep = step + 1;
+        pos.peek(walk, nstep, stop, mask, brow, lane);
+        float tn = t;
+        float acc[1];
+        tile_step<1, CH>(acc, cur, tn, Tl, codes, w, metric, N, K, pos.b, pos.bnext);
+        const float s = score_finish(acc[0] + pos.bias, t, metric);
+        const bool hit = pos.offer() && s <= th;             // rules 7, 15 and 17 (a NaN compares false)
+        const u64 m = __ballot(hit);
+        if constexpr (FILL) {
+            if (m) {                                         // (uniform) hits are rare
+                const long slot = base + cnt + __builtin_popcountll(m & below);
+                if (hit && (unsigned long)slot < (unsigned long)capacity) {
+                    out_s[slot] = s;
+                    out_i[slot] = pos.b;
+                }
+            }
+        }
+        cnt += __builtin_popcountll(m);
+        t = tn;
+        pos.advance();
+        step = nstep;
+    }
+
+    if constexpr (!FILL) {
+        if (lane == 0) mine[wave] = cnt;
+    }
+}
+
 // inclusive prefix sum over the 64 lanes of a wave (integers: any order gives the same sum)
 __device__ __forceinline__ long wave_scan_incl(long v, int lane) {
 #pragma unroll

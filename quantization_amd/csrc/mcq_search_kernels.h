@@ -156,6 +156,44 @@ k_code_norms(const uint8_t *__restrict__ codes, long B, const float *__restrict_
     if (lane == 0) norms[b] = RNORM ? rnorm_of(part) : part;
 }
 
+// t[b] = |base[assign[b]] + sum_n C[n][code[b][n]]|^2 (rule 22): the norms of a store of RESIDUAL codes, whose vector b is
+// its list's coarse centroid plus the decode of its code.  k_code_norms with one more addition per feature: the codebook
+// rows n ascending as there, THEN the base element, then the same per-lane chains and butterfly.  base is float[L][D] with
+// row stride D (not the padded Dp; a row need not be 16-byte aligned, so it is read element by element), features d >= D
+// get no base (the pad columns of C are zero: they contribute zero).  assign[b] outside [0, L) adds no base row.
+// A sibling of k_code_norms, which keeps its text.
+template <bool RNORM>
+__global__ void __launch_bounds__(64 * kNormWaves)
+k_code_norms_based(const uint8_t *__restrict__ codes, long B, const float *__restrict__ C, int N, int K, int Dp,
+                   const float *__restrict__ base, long L, int D, const int *__restrict__ assign, float *__restrict__ norms) {
+    const long b = (long)blockIdx.x * kNormWaves + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = lane_id();
+    const int mine = (lane < N) ? (codes[b * N + lane] & (K - 1)) : 0;     // lane n holds digit n (N <= 64)
+    const int a = assign[b];
+    const bool based = a >= 0 && a < L;                      // (uniform: one stored vector per wave)
+    const float *row = base + (based ? (long)a * D : 0);
+    float part = 0.f;
+    for (int g0 = 0; g0 < Dp / 4; g0 += 64) {                // (uniform trip count: the digits are read from ALL lanes below)
+        const int g = g0 + lane;
+        const bool live = g < Dp / 4;
+        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < N; ++n) {
+            const int kk = __builtin_amdgcn_readlane(mine, n);
+            const f32x4 c = live ? *reinterpret_cast<const f32x4 *>(C + ((long)n * K + kk) * Dp + 4 * g) : v;
+            v = (n == 0) ? c : v + c;
+        }
+        if (!live) v = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (based && 4 * g + c < D) v[c] = v[c] + row[4 * g + c];
+            part = part + v[c] * v[c];
+        }
+    }
+    part = wave_sum_butterfly(part);
+    if (lane == 0) norms[b] = RNORM ? rnorm_of(part) : part;
+}
+
 // r[b] from t[b] a store already keeps (code_norms): no center is gathered again
 __global__ void __launch_bounds__(256)
 k_rnorms_from_norms(const float *__restrict__ norms, long B, float *__restrict__ rnorms) {
@@ -643,6 +681,113 @@ k_search_lists(const float *__restrict__ tables, int Q, const uint8_t *__restric
         float acc[1];
         tile_step<1, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, pos.b, pos.bnext);
         list_insert(ls, li, ts, tb, score_finish(acc[0], t, M), (int)pos.b, pos.offer(), k, lane);
+        t = tn;
+        pos.advance();
+        step = nstep;
+    }
+
+    // the waves' lists -> LDS -> the list of (query, part)
+    __syncthreads();
+    float *Ls = reinterpret_cast<float *>(search_smem);
+    int *Li = reinterpret_cast<int *>(search_smem + (size_t)kListWaves * 64 * 4);
+    Ls[wave * 64 + lane] = ls;
+    Li[wave * 64 + lane] = li;
+    __syncthreads();
+    if (wave == 0) {
+        float ms = __builtin_inff(), mts = __builtin_inff();
+        int mi = kNoIndex, mtb = kNoIndex;
+        for (int v = 0; v < kListWaves; ++v) {
+            const float s = Ls[v * 64 + lane];
+            const int c = Li[v * 64 + lane];
+            list_insert(ms, mi, mts, mtb, s, c, lane < k && c != kNoIndex, k, lane);
+        }
+        if (lane < k) {
+            const long at = ((long)q * S + part) * k + lane;
+            ws_s[at] = ms;
+            ws_i[at] = mi;
+        }
+    }
+}
+
+// ------------------------------------------------------------ lists with a bias
+// Residual codes (rules 21-23 of include/mcq_residual.h): list l keeps the codes of x - c_l, so a candidate's score lacks the share
+// of its list's centroid, bias[q][p] = -2 <q, c_{probes[q][p]}>: one value per (query, probe slot), added to the table sum
+// of every candidate of that slot's list BEFORE the metric's finishing operation,
+//     score = score_finish(S + bias[q*P + p], w[b], metric)         S: the chain tile_step leaves (rule 3)
+// and w then holds |c_l + r^_b|^2 or its reciprocal root (k_code_norms_based).
+// The kernels with a bias are SIBLINGS of k_search_lists and k_range_lists, not a flag on them: the kernels without one keep
+// their text (their argument lists too), and a call without a bias launches them.
+//
+// The bias of a step belongs to the step's probe slot, walk.p as seek() or at() left it.  peek() moves walk.p on to the NEXT
+// step's slot before the current step's score is finished, so the bias travels as b, live and word do: bias for the current
+// step, bias_next set in peek() and moved in advance().  It is read from global memory (one address per wave: the row is
+// P floats, hot in L2 after the first part of a query) one step ahead of its use, as the codes and w are; a slot that names
+// no list has no step, so its bias is never read.
+template <bool MASKED>
+struct ListCursorBias : ListCursor<MASKED> {
+    float bias, bias_next;
+
+    template <int CH>
+    __device__ __forceinline__ void start(ListWalk &walk, long long step, long long stop, CodeChunk<CH> &cur, float &t,
+                                          const uint8_t *__restrict__ codes, const float *__restrict__ w, int metric, int N,
+                                          const u64 *__restrict__ mask, const float *__restrict__ brow, int lane) {
+        ListCursor<MASKED>::start(walk, step, stop, cur, t, codes, w, metric, N, mask, lane);
+        bias = 0.f;
+        if (step < stop) bias = brow[walk.p];                // (walk.p < P: seek() found the step's slot)
+    }
+    __device__ __forceinline__ void peek(ListWalk &walk, long long nstep, long long stop, const u64 *__restrict__ mask,
+                                         const float *__restrict__ brow, int lane) {
+        ListCursor<MASKED>::peek(walk, nstep, stop, mask, lane);
+        bias_next = bias;
+        if (nstep < stop) bias_next = brow[walk.p];          // (at() moved walk.p to the slot of nstep)
+    }
+    __device__ __forceinline__ void advance() {
+        ListCursor<MASKED>::advance();
+        bias = bias_next;
+    }
+};
+
+// k_search_lists with probe_bias float[Q][P]: the same step space, parts, lists and merge; the score takes one more addition
+template <int N, int M, bool MASKED>
+__global__ void __launch_bounds__(64 * kListWaves)
+k_search_lists_bias(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w,
+                    long B, int K, int k, int S, const int64_t *__restrict__ list_offsets, long L,
+                    const int *__restrict__ probes, int P, const float *__restrict__ probe_bias, float *__restrict__ ws_s,
+                    int *__restrict__ ws_i, const u64 *__restrict__ mask) {
+    extern __shared__ __attribute__((aligned(16))) char search_smem[];
+    constexpr int CH = N < 8 ? N : 8;
+    constexpr int THREADS = 64 * kListWaves;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x / S, part = blockIdx.x % S;
+    ListWalk walk;
+    const long long T = walk.build<THREADS>(search_smem, N * K, list_offsets, L, probes + (long)q * P, P, B, tid);
+    const long long lo = T * part / S, hi = T * (part + 1) / S;           // (T <= 2^37, S <= 256)
+    if (lo >= hi) {                                          // no step: the empty list, and nothing is staged
+        if (tid < k) {
+            const long at = ((long)q * S + part) * k + tid;
+            ws_s[at] = __builtin_inff();
+            ws_i[at] = kNoIndex;
+        }
+        return;
+    }
+    tile_stage<1, THREADS>(reinterpret_cast<float *>(search_smem), tables, Q, q, N * K, tid);
+    const float *Tl = reinterpret_cast<const float *>(search_smem);
+    const float *brow = probe_bias + (long)q * P;
+
+    float ls = __builtin_inff(), ts = __builtin_inff();
+    int li = kNoIndex, tb = kNoIndex;
+    CodeChunk<CH> cur;
+    float t = 0.f;
+    ListCursorBias<MASKED> pos;
+    long long step = lo + wave;
+    pos.start(walk, step, hi, cur, t, codes, w, M, N, mask, brow, lane);
+    while (step < hi) {
+        const long long nstep = step + kListWaves;
+        pos.peek(walk, nstep, hi, mask, brow, lane);
+        float tn = t;
+        float acc[1];
+        tile_step<1, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, pos.b, pos.bnext);
+        list_insert(ls, li, ts, tb, score_finish(acc[0] + pos.bias, t, M), (int)pos.b, pos.offer(), k, lane);
         t = tn;
         pos.advance();
         step = nstep;

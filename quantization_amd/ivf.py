@@ -9,13 +9,26 @@
     lims, dist, idx = quantizer.range_search_lists(queries, codes, list_offsets, probes, radius, norms=norms)
     original = order[idx]                                      # every hit within the radius in the probed lists, as CSR
 
+A store of RESIDUAL codes (IVFADC): list l keeps the codes of x - centroids[l], so the bytes spend their precision inside the
+cell.  The centroid's share of a score comes back as one value per (query, probe), and the norms are those of centroid + decode:
+
+    codes = quantizer.encode(x - centroids[assign], as_bytes=True)              # the residuals' codes
+    order, list_offsets = build_lists(assign, num_lists)
+    codes = codes[order]                                                          # in list order
+    norms = quantizer.code_norms(codes, base=centroids, assign=list_assign(list_offsets, B))
+    probes = probe_lists(queries, centroids, nprobe)
+    dist, idx = quantizer.search_lists(queries, codes, list_offsets, probes, k=10, norms=norms,
+                                       probe_bias=probe_bias(queries, centroids, probes))
+    lims, dist, idx = quantizer.range_search_lists(queries, codes, list_offsets, probes, radius, norms=norms,
+                                                   probe_bias=probe_bias(queries, centroids, probes))
+
 Where the coarse centroids come from (k-means over a sample, a trained layer) is the caller's business."""
 import torch
 from torch import Tensor
 
 from .search import check_metric
 
-__all__ = ["build_lists", "probe_lists"]
+__all__ = ["build_lists", "probe_lists", "probe_bias", "list_assign"]
 
 
 def build_lists(assign: Tensor, num_lists: int):
@@ -60,3 +73,42 @@ def probe_lists(queries: Tensor, centroids: Tensor, nprobe: int, metric: str = "
             sim = sim / cn.masked_fill(cn == 0, 1.0)[None, :]
         top = torch.topk(sim, nprobe, dim=1).indices.to(torch.int32)
     return top.reshape(*queries.shape[:-1], nprobe)
+
+
+def probe_bias(queries: Tensor, centroids: Tensor, probes: Tensor) -> Tensor:
+    """queries (*, dim), centroids (L, dim), probes (*, P) integer as search_lists takes them -> fp32 (*, P):
+    -2 <queries[q], centroids[probes[q][p]]>, and 0 where an entry names no list.  What search_lists(probe_bias=...) adds to
+    the table sums of a store of residual codes.  One matmul and one gather."""
+    if not isinstance(centroids, Tensor) or centroids.ndim != 2 or queries.shape[-1] != centroids.shape[1]:
+        raise ValueError(f"centroids: an (L, {queries.shape[-1]}) tensor, not {tuple(getattr(centroids, 'shape', ()))}")
+    if not isinstance(probes, Tensor) or probes.dtype.is_floating_point or probes.dtype == torch.bool or probes.ndim < 1 or \
+            tuple(probes.shape[:-1]) != tuple(queries.shape[:-1]):
+        raise ValueError(f"probes: an integer {tuple(queries.shape[:-1])} + (P,) tensor, not "
+                         f"{getattr(probes, 'dtype', type(probes))} {tuple(getattr(probes, 'shape', ()))}")
+    with torch.no_grad():
+        q = queries.detach().reshape(-1, queries.shape[-1]).to(torch.float32)
+        c = centroids.detach().to(torch.float32)
+        p = probes.detach().reshape(q.shape[0], probes.shape[-1]).to(torch.int64)
+        named = (p >= 0) & (p < c.shape[0])
+        if c.shape[0] == 0:
+            return torch.zeros(probes.shape, dtype=torch.float32, device=q.device)
+        dots = torch.gather(q @ c.t(), 1, p.clamp(0, c.shape[0] - 1))
+        out = torch.where(named, -2.0 * dots, torch.zeros_like(dots))
+    return out.reshape(probes.shape)
+
+
+def list_assign(list_offsets: Tensor, B: int) -> Tensor:
+    """list_offsets int64 (L + 1,) as build_lists returned them, B the length of the store -> int32 (B,): the list of each
+    position of the store in list order, -1 for a position outside every list.  What code_norms(base=centroids, assign=...)
+    takes for a store of residual codes."""
+    if not isinstance(list_offsets, Tensor) or list_offsets.dtype != torch.int64 or list_offsets.ndim != 1 or list_offsets.numel() < 1:
+        raise ValueError(f"list_offsets: an int64 (L + 1,) tensor, not {getattr(list_offsets, 'dtype', type(list_offsets))} "
+                         f"{tuple(getattr(list_offsets, 'shape', ()))}")
+    B = int(B)
+    if B < 0:
+        raise ValueError(f"a store of {B} vectors")
+    off = list_offsets.detach()
+    pos = torch.arange(B, dtype=torch.int64, device=off.device)
+    l = torch.searchsorted(off, pos, right=True) - 1                # the last l with off[l] <= b: an empty list is passed
+    inside = (l >= 0) & (l < off.numel() - 1)
+    return torch.where(inside, l, torch.full_like(l, -1)).to(torch.int32)

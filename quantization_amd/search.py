@@ -1,5 +1,5 @@
 """The search over stored codes (not in the reference): top-k and range search, under a mask, list by list; include/mcq.h
-rules 1-20.  `SearchMixin` holds the methods `Quantizer` offers for it.  It has no state of its own: it uses num_codebooks,
+rules 1-20 and include/mcq_residual.h rules 21-23.  `SearchMixin` holds the methods `Quantizer` offers for it.  It has no state of its own: it uses num_codebooks,
 codebook_size, dim, _prepared and _check_domain of the class it is mixed into.
 
 Each rule of the layer is written once here: the device check (_on_device), the metric check (check_metric), the choice of
@@ -16,6 +16,8 @@ METRICS = {"l2": _lib.MCQ_SEARCH_L2, "ip": _lib.MCQ_SEARCH_IP, "cosine": _lib.MC
 # A/B hook of _lib serves every call it knows: the first row whose condition the call meets.
 # (the call has, top-k scan, its workspace query, range count, range fill, their workspace query)
 _ENTRIES = (
+    ("bias", "mcq_search_scan_lists_bias", "mcq_search_lists_workspace_bytes",
+     "mcq_search_range_lists_bias_count", "mcq_search_range_lists_bias_fill", "mcq_search_range_lists_workspace_bytes"),
     ("lists", "mcq_search_scan_lists", "mcq_search_lists_workspace_bytes",
      "mcq_search_range_lists_count", "mcq_search_range_lists_fill", "mcq_search_range_lists_workspace_bytes"),
     ("mask", "mcq_search_scan_masked", "mcq_search_workspace_bytes",
@@ -82,13 +84,29 @@ def _check_lists(lists, Q: int) -> None:
         raise ValueError(f"probes of {rows} rows for {Q} queries")
 
 
-def _checked(metric, mask, B: int, lists, Q: int, sort_probes: bool = False):
+def _check_bias(bias, lists) -> None:
+    """what search_lists accepts as probe_bias beside (list_offsets, probes): a floating tensor with the shape of probes.
+    Looks at shape and dtype only, so it runs before any device work."""
+    if bias is None:
+        return
+    if lists is None:
+        raise ValueError("probe_bias: there is one value per probe, and this call has no probes")
+    probes = lists[1]
+    if not isinstance(bias, Tensor) or not bias.dtype.is_floating_point or tuple(bias.shape) != tuple(probes.shape):
+        raise ValueError(f"probe_bias: a floating {tuple(probes.shape)} tensor, one value per entry of probes, not "
+                         f"{getattr(bias, 'dtype', type(bias))} {tuple(getattr(bias, 'shape', ()))}")
+
+
+def _checked(metric, mask, B: int, lists, Q: int, sort_probes: bool = False, bias=None):
     """the shape and dtype checks of a call over B stored vectors and Q queries (ValueError, before any device work, on CPU
     tensors too) -> `lists` as the library reads them, None staying None: (int64 (L + 1,), int32 (Q, P)); an int64 entry
-    that names no list becomes -1 before it is narrowed.  sort_probes: each row ascending (range_search_lists)."""
+    that names no list becomes -1 before it is narrowed.  sort_probes: each row ascending (range_search_lists).
+    bias: the probe_bias of the call, or None; with one the tuple has a third entry, fp32 (Q, P), each row permuted as
+    its row of probes was."""
     check_metric(metric)
     _check_mask(mask, B)
     _check_lists(lists, Q)
+    _check_bias(bias, lists)
     if lists is None:
         return None
     offsets, probes = lists
@@ -96,7 +114,14 @@ def _checked(metric, mask, B: int, lists, Q: int, sort_probes: bool = False):
     if probes.dtype == torch.int64:
         named = (probes >= 0) & (probes < offsets.numel() - 1)
         probes = torch.where(named, probes, torch.full_like(probes, -1)).to(torch.int32)
-    return offsets.detach().contiguous(), torch.sort(probes, dim=1).values if sort_probes else probes.contiguous()
+    if bias is not None:
+        bias = bias.detach().reshape(Q, probes.shape[1]).to(torch.float32)
+    if sort_probes:
+        probes, perm = torch.sort(probes, dim=1, stable=True)
+        if bias is not None:
+            bias = torch.gather(bias, 1, perm.to(bias.device))
+    out = (offsets.detach().contiguous(), probes.contiguous())
+    return out if bias is None else out + (bias.contiguous(),)
 
 
 def _reported(scores: Tensor, metric: str, qq: Tensor, rows: Tensor = None) -> Tensor:
@@ -154,26 +179,52 @@ class SearchMixin:
             _call(_TABLES, q2d.data_ptr(), int(q2d.dtype == torch.float16), Q, blob.data_ptr(), N, K, D, out.data_ptr(), st)
         return out
 
-    def _code_norms(self, codes: Tensor, entry: str) -> Tensor:
-        """code_norms and code_rnorms: `entry` names the library call"""
+    def _code_norms(self, codes: Tensor, entry: str, base=None, assign=None) -> Tensor:
+        """code_norms and code_rnorms: `entry` names the library call; with base and assign its _based twin (rule 22)"""
         N, K, D = self.num_codebooks, self.codebook_size, self.dim
+        if (base is None) != (assign is None):
+            raise ValueError("code_norms: base and assign come together (base[assign[b]] is added to the decode of codes[b])")
+        if base is not None:
+            if not isinstance(base, Tensor) or base.ndim != 2 or base.shape[1] != D or not base.dtype.is_floating_point:
+                raise ValueError(f"base: a floating (L, {D}) tensor, not {getattr(base, 'dtype', type(base))} "
+                                 f"{tuple(getattr(base, 'shape', ()))}")
+            rows = codes.reshape(-1, codes.shape[-1]).shape[0]
+            if not isinstance(assign, Tensor) or assign.dtype.is_floating_point or assign.dtype == torch.bool or \
+                    tuple(assign.shape) != (rows,):
+                raise ValueError(f"assign: an integer ({rows},) tensor, not {getattr(assign, 'dtype', type(assign))} "
+                                 f"{tuple(getattr(assign, 'shape', ()))}")
         flat = self._unpacked_codes(codes)
         B, dev = flat.shape[0], flat.device
         with torch.no_grad(), torch.cuda.device(dev):
             blob, st = self._search_state(dev)
             out = torch.empty((B,), dtype=torch.float32, device=dev)
-            _call(entry, flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
+            if base is None:
+                _call(entry, flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
+            else:
+                _on_device(base, assign)
+                base = base.detach().to(torch.float32).contiguous()
+                L = base.shape[0]
+                a = assign.detach()
+                if a.dtype != torch.int32:                         # (a value that names no row stays one after narrowing)
+                    a = torch.where((a >= 0) & (a < L), a, torch.full_like(a, -1)).to(torch.int32)
+                a = a.contiguous()
+                _call(entry + "_based", flat.data_ptr(), B, blob.data_ptr(), N, K, D, base.data_ptr(), L, a.data_ptr(),
+                      out.data_ptr(), st)
         return out
 
-    def code_norms(self, codes: Tensor) -> Tensor:
+    def code_norms(self, codes: Tensor, base: Tensor = None, assign: Tensor = None) -> Tensor:
         """codes (*, num_codebooks) uint8 (or packed, codebook_size 16) -> fp32 (B,): |decode(codes[b])|^2 (mcq_code_norms).
-        Formed once per store of codes and handed to search(norms=...)."""
-        return self._code_norms(codes, "mcq_code_norms")
+        Formed once per store of codes and handed to search(norms=...).
+        base (L, dim) and assign integer (B,), both or neither: |base[assign[b]] + decode(codes[b])|^2
+        (mcq_code_norms_based) -- the norms of a store of RESIDUAL codes, base the coarse centroids and assign[b] the list of
+        position b (quantization_amd.ivf.list_assign); an assign[b] outside [0, L) adds no row."""
+        return self._code_norms(codes, "mcq_code_norms", base, assign)
 
-    def code_rnorms(self, codes: Tensor) -> Tensor:
+    def code_rnorms(self, codes: Tensor, base: Tensor = None, assign: Tensor = None) -> Tensor:
         """codes as for code_norms -> fp32 (B,): 1 / sqrt(code_norms(codes)), 0 for an all-zero reconstruction (mcq_code_rnorms).
-        What the cosine search multiplies by: formed once per store and handed to search(metric="cosine", rnorms=...)."""
-        return self._code_norms(codes, "mcq_code_rnorms")
+        What the cosine search multiplies by: formed once per store and handed to search(metric="cosine", rnorms=...).
+        base and assign as code_norms takes them (mcq_code_rnorms_based): the same bits as rnorms_from_norms of its result."""
+        return self._code_norms(codes, "mcq_code_rnorms", base, assign)
 
     def rnorms_from_norms(self, norms: Tensor) -> Tensor:
         """norms fp32 (B,) as code_norms returned them -> fp32 (B,): the same values code_rnorms gives, without a gather
@@ -211,12 +262,13 @@ class SearchMixin:
             return rnorms.reshape(-1)
         return self.code_rnorms(flat) if norms is None else self.rnorms_from_norms(norms)
 
-    def _operands(self, queries: Tensor, codes: Tensor, metric: str, norms, rnorms, mask, lists, sort_probes: bool = False):
+    def _operands(self, queries: Tensor, codes: Tensor, metric: str, norms, rnorms, mask, lists, sort_probes: bool = False,
+                  bias=None):
         """What search, search_lists, range_search and range_search_lists prepare alike, in this order: the checks of metric,
         mask and lists; the unpacked codes; the per-candidate array; the tables and |q|^2.
-        -> (tables, codes uint8 (B, N), w, |q|^2 fp32 (Q, 1), lists as _run takes them)"""
+        -> (tables, codes uint8 (B, N), w, |q|^2 fp32 (Q, 1), lists as _run takes them: with `bias` as their third entry)"""
         lists = _checked(metric, mask, codes.reshape(-1, codes.shape[-1]).shape[0], lists,
-                         queries.numel() // max(queries.shape[-1], 1), sort_probes)
+                         queries.numel() // max(queries.shape[-1], 1), sort_probes, bias)
         flat = self._unpacked_codes(codes)
         w = self._metric_array(metric, flat, norms, rnorms)
         tables = self.search_tables(queries)
@@ -242,7 +294,8 @@ class SearchMixin:
         Q, B, dev = tables.shape[0], codes.shape[0], tables.device
         assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and codes.dtype == torch.uint8
         assert w is None or tuple(w.shape) == (B,)
-        has = {"lists": lists is not None, "mask": mask is not None, "metric": metric != "l2", None: True}
+        has = {"bias": lists is not None and len(lists) == 3, "lists": lists is not None, "mask": mask is not None,
+               "metric": metric != "l2", None: True}
         first, scan, scan_bytes, count, fill, range_bytes = next(row for row in _ENTRIES if has[row[0]])
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
@@ -254,9 +307,11 @@ class SearchMixin:
                 args += (METRICS[metric],)
             words = None if mask is None else mask.detach().contiguous() if mask.dtype == torch.int64 else self.pack_mask(mask)
             if lists is not None:
-                offsets, probes = lists
+                offsets, probes = lists[:2]
                 args += (None if words is None else words.data_ptr(), offsets.data_ptr(), offsets.numel() - 1,
                          probes.data_ptr(), probes.shape[1])
+                if first == "bias":
+                    args += (lists[2].data_ptr(),)
             elif mask is not None:
                 args += (words.data_ptr(),)
             size = (Q, B if lists is None else probes.shape[1], N, K) + (() if k is None else (k,))
@@ -280,7 +335,7 @@ class SearchMixin:
         return lims, scores, indexes
 
     def _search_scan(self, tables: Tensor, codes: Tensor, norms: Tensor, k: int, metric: str = "l2", mask: Tensor = None,
-                     lists=None):
+                     lists=None, bias: Tensor = None):
         """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, norms fp32 (B,) -> (scores fp32 (Q, k), indexes int64 (Q, k)):
         the k smallest score[q][b] = sum_n tables[q][n][codes[b][n]] + norms[b] under (score, b) ascending (mcq_search_scan).
         metric "ip": the score is the sum alone and `norms` is not looked at (None will do); "cosine": `norms` holds the
@@ -288,8 +343,11 @@ class SearchMixin:
         mask: bool (B,) or the words of pack_mask: the k smallest among the positions whose bit is set
         (mcq_search_scan_masked); None calls what it called before masks existed.
         lists: (list_offsets int64 (L + 1,), probes (Q, P) int32 or int64) as search_lists takes them: the k smallest among
-        the positions of the lists row q of `probes` names, under the mask if there is one (mcq_search_scan_lists)."""
-        return self._run(tables, codes, norms, metric, mask, _checked(metric, mask, codes.shape[0], lists, tables.shape[0]), k=k)
+        the positions of the lists row q of `probes` names, under the mask if there is one (mcq_search_scan_lists).
+        bias: floating, the shape of `probes`: bias[q][p] is added to the sum of every candidate of the list slot p of row q
+        names, before norms[b] is added or multiplied (mcq_search_scan_lists_bias); None calls what it called before."""
+        return self._run(tables, codes, norms, metric, mask,
+                         _checked(metric, mask, codes.shape[0], lists, tables.shape[0], bias=bias), k=k)
 
     def search(self, queries: Tensor, codes: Tensor, k: int = 10, norms: Tensor = None, metric: str = "l2",
                rnorms: Tensor = None, mask: Tensor = None):
@@ -310,7 +368,8 @@ class SearchMixin:
         return self._topk(queries, codes, k, norms, metric, rnorms, mask)
 
     def search_lists(self, queries: Tensor, codes: Tensor, list_offsets: Tensor, probes: Tensor, k: int = 10,
-                     norms: Tensor = None, metric: str = "l2", rnorms: Tensor = None, mask: Tensor = None):
+                     norms: Tensor = None, metric: str = "l2", rnorms: Tensor = None, mask: Tensor = None,
+                     probe_bias: Tensor = None):
         """search() over an inverted file: the store is kept in list order and each query is scored against the lists it
         probes and no others (quantization_amd.ivf.build_lists orders a store, probe_lists picks the lists).
         list_offsets int64 (L + 1,): list l is the positions [list_offsets[l], list_offsets[l + 1]) of `codes`; probes (*, P)
@@ -320,13 +379,18 @@ class SearchMixin:
         equal scores, the tail of a query with fewer than k candidates, and the mask (a stored vector is a candidate iff it
         lies in a probed list AND the mask keeps it: a delete clears one bit, whatever list the vector sits in).  Indexes
         are positions in `codes`, that is in list order (map them through build_lists' `order` for the original ones).
-        Row q equals search(queries[q], ..., mask=the union of its lists); the cost falls with the probed share."""
-        return self._topk(queries, codes, k, norms, metric, rnorms, mask, (list_offsets, probes))
+        Row q equals search(queries[q], ..., mask=the union of its lists); the cost falls with the probed share.
+        probe_bias: a floating tensor with the shape of `probes`, for a store of RESIDUAL codes (list l keeps the codes of
+        x - centroids[l]): probe_bias[q][p] = -2 <q, centroids[probes[q][p]]> (quantization_amd.ivf.probe_bias) is added
+        to the table sum of every candidate of that slot's list, and norms / rnorms are those of centroid + decode
+        (code_norms(codes, base=centroids, assign=ivf.list_assign(list_offsets, B))).  The values reported are then the
+        distances and similarities to centroid + decode(code).  The value of an entry that names no list is not read."""
+        return self._topk(queries, codes, k, norms, metric, rnorms, mask, (list_offsets, probes), probe_bias)
 
-    def _topk(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask, lists=None):
-        """search() and search_lists(): `lists` is None or (list_offsets, probes)"""
+    def _topk(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask, lists=None, bias=None):
+        """search() and search_lists(): `lists` is None or (list_offsets, probes), `bias` the probe_bias beside them"""
         with torch.no_grad():
-            tables, flat, w, qq, lists = self._operands(queries, codes, metric, norms, rnorms, mask, lists)
+            tables, flat, w, qq, lists = self._operands(queries, codes, metric, norms, rnorms, mask, lists, bias=bias)
             scores, indexes = self._run(tables, flat, w, metric, mask, lists, k=k)
             values = _reported(scores, metric, qq)
         lead = queries.shape[:-1]
@@ -334,7 +398,7 @@ class SearchMixin:
 
     # ------------------------------------------------- range search over stored codes
     def _search_range(self, tables: Tensor, codes: Tensor, w: Tensor, thr: Tensor, metric: str = "l2",
-                      max_results: int = None, mask: Tensor = None, lists=None):
+                      max_results: int = None, mask: Tensor = None, lists=None, bias: Tensor = None):
         """tables fp32 (Q, N, K), codes uint8 (B, N) unpacked, w as _search_scan takes it under the metric (norms, None,
         reciprocal roots), thr fp32 (Q,) -> (lims int64 (Q + 1,), scores fp32 (total,), indexes int64 (total,)): every b with
         score[q][b] <= thr[q], the entries of query q at [lims[q], lims[q+1]) in ascending position (mcq_search_range_count,
@@ -343,8 +407,10 @@ class SearchMixin:
         mcq_search_range_fill_masked, with the same words).
         lists: (list_offsets, probes) as _search_scan takes them: every such b among the positions of the lists row q of
         `probes` names, under the mask if there is one, IN THE ORDER OF THE ROW -- slot 0's list first, ascending position
-        within a list (mcq_search_range_lists_count and mcq_search_range_lists_fill)."""
-        return self._run(tables, codes, w, metric, mask, _checked(metric, mask, codes.shape[0], lists, tables.shape[0]),
+        within a list (mcq_search_range_lists_count and mcq_search_range_lists_fill).
+        bias: as _search_scan takes it (mcq_search_range_lists_bias_count and _fill); the row's own order is kept."""
+        return self._run(tables, codes, w, metric, mask,
+                         _checked(metric, mask, codes.shape[0], lists, tables.shape[0], bias=bias),
                          thr=thr, max_results=max_results)
 
     def range_search(self, queries: Tensor, codes: Tensor, radius, norms: Tensor = None, metric: str = "l2",
@@ -366,7 +432,7 @@ class SearchMixin:
 
     def range_search_lists(self, queries: Tensor, codes: Tensor, list_offsets: Tensor, probes: Tensor, radius,
                            norms: Tensor = None, metric: str = "l2", rnorms: Tensor = None, max_results: int = 1 << 26,
-                           mask: Tensor = None):
+                           mask: Tensor = None, probe_bias: Tensor = None):
         """range_search() over an inverted file: every stored vector within `radius` of each query AMONG THE LISTS IT PROBES
         (quantization_amd.ivf.build_lists orders a store, probe_lists picks the lists).
         list_offsets and probes exactly as search_lists takes them: int64 (L + 1,), and (*, P) int32 or int64 with one row
@@ -379,13 +445,18 @@ class SearchMixin:
         This method sorts each probe row ascending before the call (entries that name no list stay out of the way), so the
         results of a query are IN ASCENDING POSITION and row q equals range_search(queries[q], ..., mask=the union of its
         lists).  The C entry (mcq_search_range_lists_count / _fill) keeps the row's own order: slot 0's list first.  A list
-        named twice in a row is listed twice.  The cost falls with the probed share; nothing sweeps the whole store."""
-        return self._within(queries, codes, radius, norms, metric, rnorms, max_results, mask, (list_offsets, probes))
+        named twice in a row is listed twice.  The cost falls with the probed share; nothing sweeps the whole store.
+        probe_bias: as search_lists takes it, for a store of residual codes; each of its rows is permuted as the row of
+        probes is when that is sorted.  The L2 threshold stays radius - |q|^2."""
+        return self._within(queries, codes, radius, norms, metric, rnorms, max_results, mask, (list_offsets, probes), probe_bias)
 
-    def _within(self, queries: Tensor, codes: Tensor, radius, norms, metric: str, rnorms, max_results, mask, lists=None):
-        """range_search() and range_search_lists(): `lists` is None or (list_offsets, probes), whose rows are sorted here"""
+    def _within(self, queries: Tensor, codes: Tensor, radius, norms, metric: str, rnorms, max_results, mask, lists=None,
+                bias=None):
+        """range_search() and range_search_lists(): `lists` is None or (list_offsets, probes), whose rows are sorted here
+        (and the rows of `bias`, the probe_bias beside them, with them)"""
         with torch.no_grad():
-            tables, flat, w, qq, lists = self._operands(queries, codes, metric, norms, rnorms, mask, lists, sort_probes=True)
+            tables, flat, w, qq, lists = self._operands(queries, codes, metric, norms, rnorms, mask, lists, sort_probes=True,
+                                                        bias=bias)
             Q, dev = tables.shape[0], tables.device
             if isinstance(radius, Tensor):
                 if radius.numel() != Q:

@@ -1,0 +1,200 @@
+"""Residual codes list by list (mcq_search_scan_lists_bias, mcq_search_range_lists_bias_count / _fill, mcq_code_norms_based;
+include/mcq_residual.h rules 21-23): the numpy restatement of the biased score and of the based norms, the bias of a GPU case, and
+the value lists of the two launchers of the biased kernels, read from quantization_amd/csrc/mcq_api.hip.
+
+    score[q][b] = finish((S[q][b] + bias[q][p]), w[b])     p: the slot of row q whose list holds b
+                  S: restate_sums of tests/search_metric_grid.py (rule 3's chain); then ONE float32 addition; then
+                  finish = (.. + w[b]) under l2, nothing under ip, (.. * w[b]) under cosine, each one float32 operation
+    norms[b]    = sum_d (base[assign[b]][d] + sum_n C[n][code[b][n]][d])^2: rows n ascending, then the base element, then
+                  the lane chains and the butterfly of rule 2 (restate_norms_based spells them out)
+
+The top-k restatement is lists_grid.restate_lists over the matrix biased_scores() gives (rows hold distinct lists, so every
+candidate has ONE slot); the range restatement walks the slots of a row in order, as rule 18 lists them, so a list named twice
+is listed twice, each time with the bias of that naming's slot.
+
+The GPU cases are the case tables of tests/search_lists_grid.py and tests/search_range_lists_grid.py themselves: whatever
+those tables claim to reach (cut lists, list boundaries inside a wave's run, empty parts, padding rows, 4,096 probes) is
+checked against the launch arithmetic by their own host tests, and that arithmetic does not depend on a bias."""
+import re
+
+import numpy as np
+
+import search_grid as sg
+import search_lists_grid as lg
+import search_metric_grid as mg
+import search_selection_grid as sel
+
+ME = "tests/search_bias_grid.py"
+METRICS = lg.METRICS
+PATTERNS = (None, "half")                       # the masks of the GPU cases: none, and `half` of tests/search_mask_grid.py
+
+# launcher -> (what each of its pick<...> lists selects, in source order; the number of pick_bool calls)
+DISPATCHERS = {
+    "launch_lists_bias": (("metric", "N"), 1),
+    "launch_range_lists_bias": (("CH",), 1),
+}
+
+
+# ------------------------------------------------------------------ rule 21 in numpy
+def finish(Sb, w, metric):
+    """the metric's finishing operation of rule 3' on float32 (S + bias): one float32 operation, none under ip"""
+    Sb = np.asarray(Sb, dtype=np.float32)
+    if metric == "ip":
+        return Sb
+    with np.errstate(invalid="ignore", over="ignore"):
+        w = np.asarray(w, dtype=np.float32)
+        return (Sb + w).astype(np.float32) if metric == "l2" else (Sb * w).astype(np.float32)
+
+
+def slot_scores(S_row, list_offsets, row, bias_row, w, metric):
+    """per slot of one query's row, in the row's order: (positions of the named list, their biased scores); a slot that
+    names no list has none"""
+    L = len(list_offsets) - 1
+    out = []
+    for p, l in enumerate(row):
+        if not 0 <= int(l) < L:
+            continue
+        pos = np.arange(list_offsets[int(l)], list_offsets[int(l) + 1], dtype=np.int64)
+        Sb = (S_row[pos] + np.float32(bias_row[p])).astype(np.float32)
+        out.append((pos, finish(Sb, None if w is None else w[pos], metric)))
+    return out
+
+
+def biased_scores(S, list_offsets, probes, bias, w, metric):
+    """(Q, B) float32: at the candidates of query q their biased scores (of the LAST slot naming their list, where a row
+    names one twice), NaN everywhere else -- the matrix lists_grid.restate_lists and range_lists_grid.thresholds_for take"""
+    out = np.full(S.shape, np.nan, dtype=np.float32)
+    for q, row in enumerate(probes):
+        for pos, val in slot_scores(S[q], list_offsets, row, bias[q], w, metric):
+            out[q, pos] = val
+    return out
+
+
+def restate_range_lists_bias(S, list_offsets, probes, bias, w, metric, thr, keep=None):
+    """rules 17, 18 and 21: -> (lims int64 (Q + 1,), positions int64, scores float32), the slots of a row in order"""
+    thr = np.asarray(thr, dtype=np.float32)
+    lims = np.zeros(len(probes) + 1, dtype=np.int64)
+    pos_out, val_out = [np.zeros(0, np.int64)], [np.zeros(0, np.float32)]
+    for q, row in enumerate(probes):
+        n = 0
+        for pos, val in slot_scores(S[q], list_offsets, row, bias[q], w, metric):
+            with np.errstate(invalid="ignore"):
+                hit = val <= thr[q]                                  # a NaN compares false
+            if keep is not None:
+                hit &= keep[pos]
+            pos_out.append(pos[hit])
+            val_out.append(val[hit])
+            n += int(hit.sum())
+        lims[q + 1] = lims[q] + n
+    return lims, np.concatenate(pos_out), np.concatenate(val_out)
+
+
+def named_slots(list_offsets, probes):
+    """the (q, p) whose entry names a list that is not empty: the slots whose bias some candidate takes"""
+    L = len(list_offsets) - 1
+    return [(q, p) for q, row in enumerate(probes) for p, l in enumerate(row)
+            if 0 <= int(l) < L and list_offsets[int(l) + 1] > list_offsets[int(l)]]
+
+
+def bias_for(S, list_offsets, probes, seed=1):
+    """the bias of a GPU case, float32 with the shape of probes: fixed-seed normal values scaled to the spread of the case's
+    table sums (so that a bias reorders candidates of different lists without drowning the sums); of the slots that name a
+    list that is not empty every fifth holds +0.0 and the last -0.0; negatives occur by themselves (asserted)"""
+    rs = np.random.RandomState(seed + 7 * probes.shape[1])
+    spread = float(np.std(S.astype(np.float64))) or 1.0
+    bias = (rs.standard_normal(probes.shape) * spread).astype(np.float32)
+    named = named_slots(list_offsets, probes)
+    for q, p in named[::5]:
+        bias[q, p] = 0.0
+    if len(named) > 1:
+        bias[named[-1]] = -0.0
+    if len(named) > 2:
+        bias[named[1]] = -abs(bias[named[1]]) - np.float32(spread)
+    return bias
+
+
+def rows_with_two_lists(list_offsets, probes):
+    """the queries whose row names two or more lists that are not empty: where a bias can change the ORDER of the result"""
+    count = {}
+    for q, _ in named_slots(list_offsets, probes):
+        count[q] = count.get(q, 0) + 1
+    return [q for q, n in count.items() if n >= 2]
+
+
+# ------------------------------------------------------------------ rule 22 in numpy
+def restate_norms_based(C, codes, base, assign, D):
+    """C (N, K, Dp) float32 -- the PADDED rows of `prepared` --, codes (B, N), base (L, D) float32, assign (B,) integer ->
+    float32 (B,).  base None: rule 2 itself."""
+    N, K, Dp = C.shape
+    B = codes.shape[0]
+    v = C[0][codes[:, 0].astype(np.int64) & (K - 1)].astype(np.float32)
+    for n in range(1, N):
+        v = (v + C[n][codes[:, n].astype(np.int64) & (K - 1)]).astype(np.float32)
+    if base is not None:
+        ok = (assign >= 0) & (assign < len(base))
+        add = np.zeros((B, D), dtype=np.float32)
+        add[ok] = base[assign[ok]]
+        head = (v[:, :D] + add).astype(np.float32)
+        v[:, :D] = np.where(ok[:, None], head, v[:, :D])             # (no row: nothing is added, not even a zero)
+    sq = (v * v).astype(np.float32)
+    groups = Dp // 4
+    part = np.zeros((B, 64), dtype=np.float32)
+    lanes = np.arange(64)
+    for g0 in range(0, groups, 64):                                  # lane l: the float4 groups l, l + 64, ... in turn
+        g = g0 + lanes
+        live = g < groups
+        for c in range(4):
+            term = np.zeros((B, 64), dtype=np.float32)
+            term[:, live] = sq[:, 4 * g[live] + c]
+            part = (part + term).astype(np.float32)
+    for m in (32, 16, 8, 4, 2, 1):                                   # the xor butterfly: every lane ends with the same sum
+        part = (part + part[:, lanes ^ m]).astype(np.float32)
+    return part[:, 0].copy()
+
+
+# ------------------------------------------------------------------ the launchers' value lists, and their cells
+def pick_lists(launcher, path=sel.API):
+    """the value lists of the pick<...> calls inside `launcher`, as search_selection_grid.pick_lists reads them"""
+    with open(path) as f:
+        src = f.read()
+    with open(sg.HDR) as f:
+        names = {m.group(1): int(m.group(2)) for m in re.finditer(r"constexpr\s+int\s+(kMetric\w+)\s*=\s*([0-9]+);", f.read())}
+    m = re.search(r"^int\s+" + launcher + r"\s*\(", src, re.M)
+    assert m, f"{launcher} moved out of mcq_api.hip or was renamed: update {ME}"
+    end = src.find("\n}\n", m.end())
+    assert end > 0
+    body = src[m.end():end]
+    what, bools = DISPATCHERS[launcher]
+    lists = re.findall(r"\bpick<([^<>]*)>\s*\(", body)
+    assert len(lists) == len(what) and len(re.findall(r"\bpick_bool\s*\(", body)) == bools, \
+        f"{launcher} no longer selects {what} and {bools} flag(s): update {ME}"
+    out = {}
+    for name, text in zip(what, lists):
+        vals = [names[t.strip()] if t.strip() in names else int(t.strip()) for t in text.split(",")]
+        assert len(set(vals)) == len(vals), f"{launcher}: pick<{text}> repeats a value"
+        out[name] = tuple(vals)
+    if launcher == "launch_range_lists_bias":
+        m = re.search(r"\(\s*a\.N\s*<\s*([0-9]+)\s*\?\s*a\.N\s*:\s*([0-9]+)\s*,", body)
+        assert m and m.group(1) == m.group(2), f"{launcher} no longer picks its chunk as min(N, cap): update {ME}"
+        out["cap"] = int(m.group(1))
+    return out
+
+
+# the cells tests/test_gpu_search_lists_bias.py and test_gpu_search_range_lists_bias.py launch: the layout and the shapes of
+# the lists cells of tests/search_selection_grid.py (K = 16, one N per test), three metrics, mask or none; the range kernel
+# at every N as well, count and fill
+CELL_NS = sel.NS
+CELL_MASKS = (False, True)
+CELL_SWEEPS = ("count", "fill")
+
+
+def coverage(path=sel.API):
+    """assert that the product of each launcher's value lists is exactly what the cells above launch -> cells per launcher"""
+    top = pick_lists("launch_lists_bias", path)
+    assert set(top["metric"]) == {mg.CODE[m] for m in METRICS}, f"launch_lists_bias: metrics {top['metric']}: update {ME}"
+    assert set(top["N"]) == set(CELL_NS), f"launch_lists_bias: N {top['N']} against the cells {CELL_NS}: update {ME}"
+    rng = pick_lists("launch_range_lists_bias", path)
+    assert set(rng["CH"]) == {min(N, rng["cap"]) for N in CELL_NS}, \
+        f"launch_range_lists_bias: CH {rng['CH']} against the cells {CELL_NS}: update {ME}"
+    return {"launch_lists_bias": len(top["N"]) * len(top["metric"]) * len(CELL_MASKS),
+            "launch_range_lists_bias": len(rng["CH"]) * len(CELL_SWEEPS) * len(CELL_MASKS)}
