@@ -955,34 +955,22 @@ int search_check(const float *tables, long Q, const uint8_t *codes, const float 
     return 0;
 }
 
-// mcq_code_norms (t[b]) and mcq_code_rnorms (RNORM: r[b])
-template <bool RNORM>
-int code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *out, void *stream) {
+// mcq_code_norms (t[b]) and mcq_code_rnorms (RNORM: r[b]); BASED: mcq_code_norms_based and mcq_code_rnorms_based, rule 22, the
+// norms of base[assign[b]] + decode(codes[b]) -- its checks of L, base and assign run only then
+template <bool RNORM, bool BASED = false>
+int code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *out, void *stream,
+               const float *base = nullptr, long L = 0, const int32_t *assign = nullptr) {
     if (const int rc = search_domain(N, K, D)) return rc;
     if (B < 0) return MCQ_EINVAL;
     if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (BASED && L < 0) return MCQ_EINVAL;
     if (B == 0) return 0;
     if (!codes || !prepared || !out) return MCQ_EINVAL;
+    if (BASED && (!base || !assign)) return MCQ_EINVAL;
+    if (BASED && (reinterpret_cast<uintptr_t>(base) % 4 != 0 || reinterpret_cast<uintptr_t>(assign) % 4 != 0)) return MCQ_EINVAL;
     const Prepared P = prepared_view(prepared, N, K, D);
-    hipLaunchKernelGGL(k_code_norms<RNORM>, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
-                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), out);
-    return launch_rc();
-}
-
-// mcq_code_norms_based (t[b]) and mcq_code_rnorms_based (RNORM: r[b]): rule 22, the norms of base[assign[b]] + decode(codes[b])
-template <bool RNORM>
-int code_norms_based(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, const float *base, long L,
-                     const int32_t *assign, float *out, void *stream) {
-    if (const int rc = search_domain(N, K, D)) return rc;
-    if (B < 0) return MCQ_EINVAL;
-    if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
-    if (L < 0) return MCQ_EINVAL;
-    if (B == 0) return 0;
-    if (!codes || !prepared || !out || !base || !assign) return MCQ_EINVAL;
-    if (reinterpret_cast<uintptr_t>(base) % 4 != 0 || reinterpret_cast<uintptr_t>(assign) % 4 != 0) return MCQ_EINVAL;
-    const Prepared P = prepared_view(prepared, N, K, D);
-    hipLaunchKernelGGL(k_code_norms_based<RNORM>, dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
-                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), base, L, D, assign, out);
+    hipLaunchKernelGGL((k_code_norms<RNORM, BASED>), dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
+                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), out, base, L, D, assign);
     return launch_rc();
 }
 
@@ -1069,43 +1057,24 @@ ListsPlan lists_plan(long Q, int P, int N, int K, int k) {
     return {parts, (size_t)lists_lds_bytes(N * K, P), align256((size_t)Q * parts * k * 4)};   // scores, then positions
 }
 
+// a bias (li.bias != NULL; rules 21 and 23) is one more flag of the same kernel: a call moves between the two by its bias alone
 int launch_lists(const ListsPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
                  int N, int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
     return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
         return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
             return pick_bool(mask != nullptr, [&](auto masked) {
-                constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
-                constexpr bool MASKED = masked;
-                static bool allowed[64] = {};
-                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_lists<NN, M, MASKED>),
-                                                     lists_lds_bytes(64 * 256, kListMaxProbes)))
-                    return rc;
-                hipLaunchKernelGGL((k_search_lists<NN, M, MASKED>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kListWaves), p.lds,
-                                   st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, li.list_offsets, li.L, li.probes,
-                                   li.P, ws_s, ws_i, reinterpret_cast<const u64 *>(mask));
-                return launch_rc();
-            });
-        });
-    });
-}
-
-// launch_lists with a bias (li.bias != NULL; rules 21 and 23): the sibling kernel over the same selection -- tests/search_bias_grid.py
-// reads these value lists as tests/search_selection_grid.py reads those above
-int launch_lists_bias(const ListsPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
-                      int N, int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
-    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
-        return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
-            return pick_bool(mask != nullptr, [&](auto masked) {
-                constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
-                constexpr bool MASKED = masked;
-                static bool allowed[64] = {};
-                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_lists_bias<NN, M, MASKED>),
-                                                     lists_lds_bytes(64 * 256, kListMaxProbes)))
-                    return rc;
-                hipLaunchKernelGGL((k_search_lists_bias<NN, M, MASKED>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kListWaves),
-                                   p.lds, st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, li.list_offsets, li.L,
-                                   li.probes, li.P, li.bias, ws_s, ws_i, reinterpret_cast<const u64 *>(mask));
-                return launch_rc();
+                return pick_bool(li.bias != nullptr, [&](auto biased) {
+                    constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
+                    constexpr bool MASKED = masked, BIAS = biased;
+                    static bool allowed[64] = {};
+                    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_lists<NN, M, MASKED, BIAS>),
+                                                         lists_lds_bytes(64 * 256, kListMaxProbes)))
+                        return rc;
+                    hipLaunchKernelGGL((k_search_lists<NN, M, MASKED, BIAS>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kListWaves),
+                                       p.lds, st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, li.list_offsets, li.L,
+                                       li.probes, li.P, ws_s, ws_i, reinterpret_cast<const u64 *>(mask), li.bias);
+                    return launch_rc();
+                });
             });
         });
     });
@@ -1132,9 +1101,7 @@ int search_topk(const float *tables, long Q, const uint8_t *codes, const float *
     if (!empty && li) {
         const ListsPlan p = lists_plan(Q, li->P, N, K, k);
         if (!split(p.ws_half)) return MCQ_EWORKSPACE;
-        if (const int rc = (li->bias ? launch_lists_bias : launch_lists)(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, *li,
-                                                                           ws_s, ws_i))
-            return rc;
+        if (const int rc = launch_lists(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, *li, ws_s, ws_i)) return rc;
         S = p.parts;
     } else if (!empty) {
         const ScanPlan p = scan_plan(Q, B, N, K, k);
@@ -1213,40 +1180,24 @@ RangeListsPlan range_lists_plan(long Q, int P, int N, int K) {
     return {parts, (size_t)lists_lds_bytes(N * K, P), align256((size_t)Q * parts * kRangeListWaves * 8)};
 }
 
+// (a bias, li.bias != NULL, is a flag here as in launch_lists)
 template <bool FILL>
 int launch_range_lists(const RangeListsPlan &p, hipStream_t st, const RangeArgs &a, const ListsIn &li) {
     return pick<1, 2, 4, 8>(a.N < 8 ? a.N : 8, [&](auto ch) {
         return pick_bool(a.mask != nullptr, [&](auto masked) {
-            constexpr int CH = decltype(ch)::value;
-            constexpr bool MASKED = masked;
-            static bool allowed[64] = {};
-            if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_lists<CH, FILL, MASKED>),
-                                                 lists_lds_bytes(64 * 256, kListMaxProbes)))
-                return rc;
-            hipLaunchKernelGGL((k_range_lists<CH, FILL, MASKED>), dim3((unsigned)a.Q * (unsigned)p.parts), dim3(64 * kRangeListWaves),
-                               p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts, li.list_offsets, li.L, li.probes,
-                               li.P, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity, reinterpret_cast<const u64 *>(a.mask));
-            return launch_rc();
-        });
-    });
-}
-
-// launch_range_lists with a bias (li.bias != NULL; rules 21 and 23): the sibling kernel over the same selection
-template <bool FILL>
-int launch_range_lists_bias(const RangeListsPlan &p, hipStream_t st, const RangeArgs &a, const ListsIn &li) {
-    return pick<1, 2, 4, 8>(a.N < 8 ? a.N : 8, [&](auto ch) {
-        return pick_bool(a.mask != nullptr, [&](auto masked) {
-            constexpr int CH = decltype(ch)::value;
-            constexpr bool MASKED = masked;
-            static bool allowed[64] = {};
-            if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_lists_bias<CH, FILL, MASKED>),
-                                                 lists_lds_bytes(64 * 256, kListMaxProbes)))
-                return rc;
-            hipLaunchKernelGGL((k_range_lists_bias<CH, FILL, MASKED>), dim3((unsigned)a.Q * (unsigned)p.parts),
-                               dim3(64 * kRangeListWaves), p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts,
-                               li.list_offsets, li.L, li.probes, li.P, li.bias, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity,
-                               reinterpret_cast<const u64 *>(a.mask));
-            return launch_rc();
+            return pick_bool(li.bias != nullptr, [&](auto biased) {
+                constexpr int CH = decltype(ch)::value;
+                constexpr bool MASKED = masked, BIAS = biased;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_lists<CH, FILL, MASKED, BIAS>),
+                                                     lists_lds_bytes(64 * 256, kListMaxProbes)))
+                    return rc;
+                hipLaunchKernelGGL((k_range_lists<CH, FILL, MASKED, BIAS>), dim3((unsigned)a.Q * (unsigned)p.parts),
+                                   dim3(64 * kRangeListWaves), p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts,
+                                   li.list_offsets, li.L, li.probes, li.P, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity,
+                                   reinterpret_cast<const u64 *>(a.mask), li.bias);
+                return launch_rc();
+            });
         });
     });
 }
@@ -1269,7 +1220,7 @@ int launch_range_any(hipStream_t st, const RangeArgs &a, const ListsIn *li, int 
     if (li) {
         const RangeListsPlan p = range_lists_plan(a.Q, li->P, a.N, a.K);
         if (per) *per = p.parts * kRangeListWaves;
-        return li->bias ? launch_range_lists_bias<FILL>(p, st, a, *li) : launch_range_lists<FILL>(p, st, a, *li);
+        return launch_range_lists<FILL>(p, st, a, *li);
     }
     const RangePlan p = range_plan(a.Q, a.B, a.N, a.K);
     if (per) *per = p.slices * kRangeWaves;
@@ -2023,12 +1974,12 @@ int mcq_search_range_lists_bias_fill(const float *tables, long Q, const uint8_t 
 
 int mcq_code_norms_based(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, const float *base, long L,
                          const int32_t *assign, float *norms_out, void *stream) {
-    return code_norms_based<false>(codes, B, prepared, N, K, D, base, L, assign, norms_out, stream);
+    return code_norms<false, true>(codes, B, prepared, N, K, D, norms_out, stream, base, L, assign);
 }
 
 int mcq_code_rnorms_based(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, const float *base, long L,
                           const int32_t *assign, float *rnorms_out, void *stream) {
-    return code_norms_based<true>(codes, B, prepared, N, K, D, base, L, assign, rnorms_out, stream);
+    return code_norms<true, true>(codes, B, prepared, N, K, D, rnorms_out, stream, base, L, assign);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

@@ -151,18 +151,21 @@ k_range_sweep(const float *__restrict__ tables, int Q, const uint8_t *__restrict
 //   * COUNT writes one int64 per (query, part, wave), zeros included (nobody clears the workspace): a part without a step
 //     writes its zeros and returns before it stages the table.  k_range_offsets (per = S * kRangeListWaves) and k_range_lims
 //     finish the count unchanged.  No atomics of any kind.
+//   * with a bias (BIAS; rules 21-23): s = score_finish(S + the bias of the step's slot, w), the bias travelling with the
+//     cursor as in k_search_lists; the same step space, runs, counts and slots.
 // LDS: lists_lds_bytes of mcq_search_kernels.h.
 constexpr int kRangeListWaves = 4;        // k_range_lists: waves per workgroup (256 threads), as kListWaves: a table is N*K
                                           // floats (8 KiB at 8 x 256), so several workgroups share a CU and 4 waves each keep
                                           // 4 per SIMD at 4 workgroups per CU (not measured against 8 or 16)
 
 // ws: int64 [Q][S][kRangeListWaves] -- counts out (COUNT), start offsets relative to lims[q] in (FILL).
-template <int CH, bool FILL, bool MASKED>
+template <int CH, bool FILL, bool MASKED, bool BIAS>
 __global__ void __launch_bounds__(64 * kRangeListWaves)
 k_range_lists(const float *__restrict__ tables, const uint8_t *__restrict__ codes, const float *__restrict__ w, long B,
               int N, int K, int metric, int S, const int64_t *__restrict__ list_offsets, long L, const int *__restrict__ probes,
               int P, const float *__restrict__ thr, int64_t *__restrict__ ws, const int64_t *__restrict__ lims,
-              float *__restrict__ out_s, int64_t *__restrict__ out_i, long capacity, const u64 *__restrict__ mask) {
+              float *__restrict__ out_s, int64_t *__restrict__ out_i, long capacity, const u64 *__restrict__ mask,
+              const float *__restrict__ probe_bias) {
     extern __shared__ __attribute__((aligned(16))) char range_smem[];
     constexpr int THREADS = 64 * kRangeListWaves;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -178,6 +181,7 @@ k_range_lists(const float *__restrict__ tables, const uint8_t *__restrict__ code
     }
     float *Tl = reinterpret_cast<float *>(range_smem);
     tile_stage<1, THREADS>(Tl, tables, q + 1, q, NK, tid);                // (q < Q by the grid)
+    const float *brow = BIAS ? probe_bias + (long)q * P : nullptr;
 
     const long long run = (hi - lo + kRangeListWaves - 1) / kRangeListWaves;   // steps per wave: wave v owns [lo + v*run, ..)
     long long step = lo + wave * run;
@@ -190,75 +194,7 @@ k_range_lists(const float *__restrict__ tables, const uint8_t *__restrict__ code
 
     CodeChunk<CH> cur;
     float t = 0.f;
-    ListCursor<MASKED> pos;
-    pos.start(walk, step, stop, cur, t, codes, w, metric, N, mask, lane);
-    while (step < stop) {
-        const long long nstep = step + 1;
-        pos.peek(walk, nstep, stop, mask, lane);
-        float tn = t;
-        float acc[1];
-        tile_step<1, CH>(acc, cur, tn, Tl, codes, w, metric, N, K, pos.b, pos.bnext);
-        const float s = score_finish(acc[0], t, metric);
-        const bool hit = pos.offer() && s <= th;             // rules 7, 15 and 17 (a NaN compares false)
-        const u64 m = __ballot(hit);
-        if constexpr (FILL) {
-            if (m) {                                         // (uniform) hits are rare
-                const long slot = base + cnt + __builtin_popcountll(m & below);
-                if (hit && (unsigned long)slot < (unsigned long)capacity) {
-                    out_s[slot] = s;
-                    out_i[slot] = pos.b;
-                }
-            }
-        }
-        cnt += __builtin_popcountll(m);
-        t = tn;
-        pos.advance();
-        step = nstep;
-    }
-
-    if constexpr (!FILL) {
-        if (lane == 0) mine[wave] = cnt;
-    }
-}
-
-// k_range_lists with probe_bias float[Q][P] (rules 21-23; ListCursorBias of mcq_search_kernels.h): a sibling, so that the
-// kernel above keeps its text.  The same step space, runs, counts and slots; s = score_finish(S + bias of the step's slot, w).
-template <int CH, bool FILL, bool MASKED>
-__global__ void __launch_bounds__(64 * kRangeListWaves)
-k_range_lists_bias(const float *__restrict__ tables, const uint8_t *__restrict__ codes, const float *__restrict__ w, long B,
-                   int N, int K, int metric, int S, const int64_t *__restrict__ list_offsets, long L,
-                   const int *__restrict__ probes, int P, const float *__restrict__ probe_bias, const float *__restrict__ thr,
-                   int64_t *__restrict__ ws, const int64_t *__restrict__ lims, float *__restrict__ out_s,
-                   int64_t *__restrict__ out_i, long capacity, const u64 *__restrict__ mask) {
-    extern __shared__ __attribute__((aligned(16))) char range_smem[];
-    constexpr int THREADS = 64 * kRangeListWaves;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q = blockIdx.x / S, part = blockIdx.x % S;
-    const int NK = N * K;
-    ListWalk walk;
-    const long long T = walk.build<THREADS>(range_smem, NK, list_offsets, L, probes + (long)q * P, P, B, tid);
-    const long long lo = T * part / S, hi = T * (part + 1) / S;           // (T <= 2^37, S <= 256)
-    int64_t *mine = ws + ((long)q * S + part) * kRangeListWaves;           // this part's kRangeListWaves entries
-    if (lo >= hi) {                                          // no step: zeros (COUNT), and nothing is staged
-        if (!FILL && tid < kRangeListWaves) mine[tid] = 0;
-        return;
-    }
-    float *Tl = reinterpret_cast<float *>(range_smem);
-    tile_stage<1, THREADS>(Tl, tables, q + 1, q, NK, tid);                // (q < Q by the grid)
-    const float *brow = probe_bias + (long)q * P;
-
-    const long long run = (hi - lo + kRangeListWaves - 1) / kRangeListWaves;   // steps per wave: wave v owns [lo + v*run, ..)
-    long long step = lo + wave * run;
-    const long long stop = step + run < hi ? step + run : hi;
-    const float th = thr[q];
-    const u64 below = (1ull << lane) - 1;
-    long base = 0;                                           // FILL: the slot of this wave's first hit
-    if constexpr (FILL) base = lims[q] + mine[wave];
-    long cnt = 0;                                            // (uniform) this wave's hits so far (a list named twice counts twice)
-
-    CodeChunk<CH> cur;
-    float t = 0.f;
-    ListCursorBias<MASKED> pos;
+    ListCursor<MASKED, BIAS> pos;
     pos.start(walk, step, stop, cur, t, codes, w, metric, N, mask, brow, lane);
     while (step < stop) {
         const long long nstep = step + 1;
@@ -266,7 +202,7 @@ k_range_lists_bias(const float *__restrict__ tables, const uint8_t *__restrict__
         float tn = t;
         float acc[1];
         tile_step<1, CH>(acc, cur, tn, Tl, codes, w, metric, N, K, pos.b, pos.bnext);
-        const float s = score_finish(acc[0] + pos.bias, t, metric);
+        const float s = score_finish(pos.biased(acc[0]), t, metric);
         const bool hit = pos.offer() && s <= th;             // rules 7, 15 and 17 (a NaN compares false)
         const u64 m = __ballot(hit);
         if constexpr (FILL) {

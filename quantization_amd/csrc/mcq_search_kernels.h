@@ -14,7 +14,7 @@
 //        kMetricL2   w[b] = t[b]                                   score = S + w[b]      (the line above)
 //        kMetricIP   no w: the pointer is never read               score = S             (= -2 <q, x^_b>)
 //        kMetricCos  w[b] = r[b] = 1 / sqrt(t[b]), 0 where t == 0  score = S * w[b]      (= -2 |q| cos(q, x^_b); one fp32 product)
-//      r[b] is formed by k_code_norms<true> / k_rnorms_from_norms: a correctly rounded square root, then a correctly rounded
+//      r[b] is formed by k_code_norms<RNORM = true> / k_rnorms_from_norms: a correctly rounded square root, then a correctly rounded
 //      division (no v_rsq_f32, no fast-math: the tests restate it as float32(1) / sqrt(t) in numpy and compare bits).
 //   4. the result lists are the k smallest under "(s, b) ascending", listed in that order: pair_less below is the ONLY comparison
 //      of the scan and of the merge, so the k indexes are a function of the scores alone.  No floating-point atomics anywhere.
@@ -130,49 +130,27 @@ k_search_tables(const void *__restrict__ qv, int q_is_fp16, int Q, const float *
 __device__ __forceinline__ float rnorm_of(float t) { return t == 0.f ? 0.f : 1.0f / sqrtf(t); }
 
 // t[b] = |sum_n C[n][code[b][n]]|^2: the decode body without the store.  One wave per stored vector.  RNORM: r[b] leaves instead.
-template <bool RNORM>
+// BASED: t[b] = |base[assign[b]] + sum_n C[n][code[b][n]]|^2 (rule 22), the norms of a store of RESIDUAL codes, whose vector b
+// is its list's coarse centroid plus the decode of its code: one more addition per feature -- the codebook rows n ascending,
+// THEN the base element, then the same per-lane chains and butterfly.  base is float[L][D] with row stride D (not the padded
+// Dp; a row need not be 16-byte aligned, so it is read element by element), features d >= D get no base (the pad columns of
+// C are zero: they contribute zero).  assign[b] outside [0, L) adds no base row.  Without BASED the four last arguments are
+// never read.
+template <bool RNORM, bool BASED>
 __global__ void __launch_bounds__(64 * kNormWaves)
 k_code_norms(const uint8_t *__restrict__ codes, long B, const float *__restrict__ C, int N, int K, int Dp,
-             float *__restrict__ norms) {
+             float *__restrict__ norms, const float *__restrict__ base, long L, int D, const int *__restrict__ assign) {
     const long b = (long)blockIdx.x * kNormWaves + (threadIdx.x >> 6);
     if (b >= B) return;
     const int lane = lane_id();
     const int mine = (lane < N) ? (codes[b * N + lane] & (K - 1)) : 0;     // lane n holds digit n (N <= 64)
-    float part = 0.f;
-    for (int g0 = 0; g0 < Dp / 4; g0 += 64) {                // (uniform trip count: the digits are read from ALL lanes below)
-        const int g = g0 + lane;
-        const bool live = g < Dp / 4;
-        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int n = 0; n < N; ++n) {
-            const int kk = __builtin_amdgcn_readlane(mine, n);
-            const f32x4 c = live ? *reinterpret_cast<const f32x4 *>(C + ((long)n * K + kk) * Dp + 4 * g) : v;
-            v = (n == 0) ? c : v + c;
-        }
-        if (!live) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) part = part + v[c] * v[c];
+    bool based = false;                                      // (uniform: one stored vector per wave)
+    const float *row = nullptr;
+    if constexpr (BASED) {
+        const int a = assign[b];
+        based = a >= 0 && a < L;
+        row = base + (based ? (long)a * D : 0);
     }
-    part = wave_sum_butterfly(part);
-    if (lane == 0) norms[b] = RNORM ? rnorm_of(part) : part;
-}
-
-// t[b] = |base[assign[b]] + sum_n C[n][code[b][n]]|^2 (rule 22): the norms of a store of RESIDUAL codes, whose vector b is
-// its list's coarse centroid plus the decode of its code.  k_code_norms with one more addition per feature: the codebook
-// rows n ascending as there, THEN the base element, then the same per-lane chains and butterfly.  base is float[L][D] with
-// row stride D (not the padded Dp; a row need not be 16-byte aligned, so it is read element by element), features d >= D
-// get no base (the pad columns of C are zero: they contribute zero).  assign[b] outside [0, L) adds no base row.
-// A sibling of k_code_norms, which keeps its text.
-template <bool RNORM>
-__global__ void __launch_bounds__(64 * kNormWaves)
-k_code_norms_based(const uint8_t *__restrict__ codes, long B, const float *__restrict__ C, int N, int K, int Dp,
-                   const float *__restrict__ base, long L, int D, const int *__restrict__ assign, float *__restrict__ norms) {
-    const long b = (long)blockIdx.x * kNormWaves + (threadIdx.x >> 6);
-    if (b >= B) return;
-    const int lane = lane_id();
-    const int mine = (lane < N) ? (codes[b * N + lane] & (K - 1)) : 0;     // lane n holds digit n (N <= 64)
-    const int a = assign[b];
-    const bool based = a >= 0 && a < L;                      // (uniform: one stored vector per wave)
-    const float *row = base + (based ? (long)a * D : 0);
     float part = 0.f;
     for (int g0 = 0; g0 < Dp / 4; g0 += 64) {                // (uniform trip count: the digits are read from ALL lanes below)
         const int g = g0 + lane;
@@ -186,7 +164,9 @@ k_code_norms_based(const uint8_t *__restrict__ codes, long B, const float *__res
         if (!live) v = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            if (based && 4 * g + c < D) v[c] = v[c] + row[4 * g + c];
+            if constexpr (BASED) {
+                if (based && 4 * g + c < D) v[c] = v[c] + row[4 * g + c];
+            }
             part = part + v[c] * v[c];
         }
     }
@@ -510,6 +490,17 @@ k_search_merge(const float *__restrict__ ws_s, const int *__restrict__ ws_i, int
 //     is the bnext of tile_step, so codes and w still travel one step ahead.  Under a mask each lane tests its own bit.
 //   * the waves' lists are merged through LDS as in k_search_scan and leave as list (q, s) of the workspace: k_search_merge
 //     finishes the call.  No atomics of any kind.
+//   * with a bias (BIAS; residual codes, rules 21-23 of include/mcq_residual.h): list l keeps the codes of x - c_l, so a
+//     candidate's score lacks the share of its list's centroid, bias[q][p] = -2 <q, c_{probes[q][p]}>: one value per (query,
+//     probe slot), added to the table sum of every candidate of that slot's list BEFORE the metric's finishing operation,
+//         score = score_finish(S + bias[q*P + p], w[b], metric)         S: the chain tile_step leaves (rule 3)
+//     and w then holds |c_l + r^_b|^2 or its reciprocal root (k_code_norms<.., BASED>).  The bias is a flag of k_search_lists
+//     and k_range_lists: probe_bias is their last argument, and without the flag it is null and never read.
+//     The bias of a step belongs to the step's probe slot, walk.p as seek() or at() left it.  peek() moves walk.p on to the
+//     NEXT step's slot before the current step's score is finished, so the bias travels as b, live and word do: bias for the
+//     current step, bias_next set in peek() and moved in advance().  It is read from global memory (one address per wave:
+//     the row is P floats, hot in L2 after the first part of a query) one step ahead of its use, as the codes and w are; a
+//     slot that names no list has no step, so its bias is never read.
 // LDS: [the table, N*K floats; later the waves' lists][pre: int64 P + 1][begin: int32 P][end: int32 P].
 constexpr int kListWaves = 4;             // k_search_lists: waves per workgroup (256 threads)
 constexpr int kListTargetBlocks = 1024;   //                 workgroups that fill the chip once (4 per CU, 4 waves per SIMD)
@@ -597,17 +588,20 @@ struct ListWalk {
 // end of the list re-read its last candidate, step_at over the list as a Slice), whether it lies inside its list, and under
 // MASKED the mask word that holds its bit (lists do not start at multiples of 64: every lane tests its own).  The kernel owns
 // the steps -- which comes next, and where the wave stops -- and the score; the next step's b is the bnext of tile_step.
-template <bool MASKED>
+// BIAS: the bias of the step's probe slot (see "lists" above) travels as b, live and word do; brow is the query's row of
+// probe_bias, null and never read without one.
+template <bool MASKED, bool BIAS>
 struct ListCursor {
     long b, bnext;
     bool live, live_next;
     u64 word, word_next;
+    float bias, bias_next;
 
     // the wave's first step: its digits and w go to cur and t (tile_first: one step, or none when step >= stop)
     template <int CH>
     __device__ __forceinline__ void start(ListWalk &walk, long long step, long long stop, CodeChunk<CH> &cur, float &t,
                                           const uint8_t *__restrict__ codes, const float *__restrict__ w, int metric, int N,
-                                          const u64 *__restrict__ mask, int lane) {
+                                          const u64 *__restrict__ mask, const float *__restrict__ brow, int lane) {
         Slice sl{0, 1, 0};
         long j = 0;
         if (step < stop) sl = walk.seek(step, j);
@@ -618,9 +612,14 @@ struct ListCursor {
         if constexpr (MASKED) {
             if (step < stop) word = mask[b >> 6];
         }
+        if constexpr (BIAS) {
+            bias = 0.f;
+            if (step < stop) bias = brow[walk.p];            // (walk.p < P: seek() found the step's slot)
+        }
     }
     // the step after the current one is nstep (none when nstep >= stop: b again, offering nothing)
-    __device__ __forceinline__ void peek(ListWalk &walk, long long nstep, long long stop, const u64 *__restrict__ mask, int lane) {
+    __device__ __forceinline__ void peek(ListWalk &walk, long long nstep, long long stop, const u64 *__restrict__ mask,
+                                         const float *__restrict__ brow, int lane) {
         bnext = b;
         live_next = false;
         if (nstep < stop) {
@@ -631,23 +630,34 @@ struct ListCursor {
         }
         word_next = 0;
         if constexpr (MASKED) word_next = mask[bnext >> 6];
+        if constexpr (BIAS) {
+            bias_next = bias;
+            if (nstep < stop) bias_next = brow[walk.p];      // (at() moved walk.p to the slot of nstep)
+        }
     }
     __device__ __forceinline__ bool offer() const {
         if constexpr (MASKED) return live && ((word >> (b & 63)) & 1);
         return live;
     }
+    // the table sum S of the current step with its slot's bias: what score_finish takes
+    __device__ __forceinline__ float biased(float S) const {
+        if constexpr (BIAS) return S + bias;
+        return S;
+    }
     __device__ __forceinline__ void advance() {
         b = bnext;
         live = live_next;
         word = word_next;
+        if constexpr (BIAS) bias = bias_next;
     }
 };
 
-template <int N, int M, bool MASKED>
+template <int N, int M, bool MASKED, bool BIAS>
 __global__ void __launch_bounds__(64 * kListWaves)
 k_search_lists(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w,
                long B, int K, int k, int S, const int64_t *__restrict__ list_offsets, long L, const int *__restrict__ probes,
-               int P, float *__restrict__ ws_s, int *__restrict__ ws_i, const u64 *__restrict__ mask) {
+               int P, float *__restrict__ ws_s, int *__restrict__ ws_i, const u64 *__restrict__ mask,
+               const float *__restrict__ probe_bias) {
     extern __shared__ __attribute__((aligned(16))) char search_smem[];
     constexpr int CH = N < 8 ? N : 8;
     constexpr int THREADS = 64 * kListWaves;
@@ -666,119 +676,13 @@ k_search_lists(const float *__restrict__ tables, int Q, const uint8_t *__restric
     }
     tile_stage<1, THREADS>(reinterpret_cast<float *>(search_smem), tables, Q, q, N * K, tid);
     const float *Tl = reinterpret_cast<const float *>(search_smem);
+    const float *brow = BIAS ? probe_bias + (long)q * P : nullptr;
 
     float ls = __builtin_inff(), ts = __builtin_inff();
     int li = kNoIndex, tb = kNoIndex;
     CodeChunk<CH> cur;
     float t = 0.f;
-    ListCursor<MASKED> pos;
-    long long step = lo + wave;
-    pos.start(walk, step, hi, cur, t, codes, w, M, N, mask, lane);
-    while (step < hi) {
-        const long long nstep = step + kListWaves;
-        pos.peek(walk, nstep, hi, mask, lane);
-        float tn = t;
-        float acc[1];
-        tile_step<1, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, pos.b, pos.bnext);
-        list_insert(ls, li, ts, tb, score_finish(acc[0], t, M), (int)pos.b, pos.offer(), k, lane);
-        t = tn;
-        pos.advance();
-        step = nstep;
-    }
-
-    // the waves' lists -> LDS -> the list of (query, part)
-    __syncthreads();
-    float *Ls = reinterpret_cast<float *>(search_smem);
-    int *Li = reinterpret_cast<int *>(search_smem + (size_t)kListWaves * 64 * 4);
-    Ls[wave * 64 + lane] = ls;
-    Li[wave * 64 + lane] = li;
-    __syncthreads();
-    if (wave == 0) {
-        float ms = __builtin_inff(), mts = __builtin_inff();
-        int mi = kNoIndex, mtb = kNoIndex;
-        for (int v = 0; v < kListWaves; ++v) {
-            const float s = Ls[v * 64 + lane];
-            const int c = Li[v * 64 + lane];
-            list_insert(ms, mi, mts, mtb, s, c, lane < k && c != kNoIndex, k, lane);
-        }
-        if (lane < k) {
-            const long at = ((long)q * S + part) * k + lane;
-            ws_s[at] = ms;
-            ws_i[at] = mi;
-        }
-    }
-}
-
-// ------------------------------------------------------------ lists with a bias
-// Residual codes (rules 21-23 of include/mcq_residual.h): list l keeps the codes of x - c_l, so a candidate's score lacks the share
-// of its list's centroid, bias[q][p] = -2 <q, c_{probes[q][p]}>: one value per (query, probe slot), added to the table sum
-// of every candidate of that slot's list BEFORE the metric's finishing operation,
-//     score = score_finish(S + bias[q*P + p], w[b], metric)         S: the chain tile_step leaves (rule 3)
-// and w then holds |c_l + r^_b|^2 or its reciprocal root (k_code_norms_based).
-// The kernels with a bias are SIBLINGS of k_search_lists and k_range_lists, not a flag on them: the kernels without one keep
-// their text (their argument lists too), and a call without a bias launches them.
-//
-// The bias of a step belongs to the step's probe slot, walk.p as seek() or at() left it.  peek() moves walk.p on to the NEXT
-// step's slot before the current step's score is finished, so the bias travels as b, live and word do: bias for the current
-// step, bias_next set in peek() and moved in advance().  It is read from global memory (one address per wave: the row is
-// P floats, hot in L2 after the first part of a query) one step ahead of its use, as the codes and w are; a slot that names
-// no list has no step, so its bias is never read.
-template <bool MASKED>
-struct ListCursorBias : ListCursor<MASKED> {
-    float bias, bias_next;
-
-    template <int CH>
-    __device__ __forceinline__ void start(ListWalk &walk, long long step, long long stop, CodeChunk<CH> &cur, float &t,
-                                          const uint8_t *__restrict__ codes, const float *__restrict__ w, int metric, int N,
-                                          const u64 *__restrict__ mask, const float *__restrict__ brow, int lane) {
-        ListCursor<MASKED>::start(walk, step, stop, cur, t, codes, w, metric, N, mask, lane);
-        bias = 0.f;
-        if (step < stop) bias = brow[walk.p];                // (walk.p < P: seek() found the step's slot)
-    }
-    __device__ __forceinline__ void peek(ListWalk &walk, long long nstep, long long stop, const u64 *__restrict__ mask,
-                                         const float *__restrict__ brow, int lane) {
-        ListCursor<MASKED>::peek(walk, nstep, stop, mask, lane);
-        bias_next = bias;
-        if (nstep < stop) bias_next = brow[walk.p];          // (at() moved walk.p to the slot of nstep)
-    }
-    __device__ __forceinline__ void advance() {
-        ListCursor<MASKED>::advance();
-        bias = bias_next;
-    }
-};
-
-// k_search_lists with probe_bias float[Q][P]: the same step space, parts, lists and merge; the score takes one more addition
-template <int N, int M, bool MASKED>
-__global__ void __launch_bounds__(64 * kListWaves)
-k_search_lists_bias(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w,
-                    long B, int K, int k, int S, const int64_t *__restrict__ list_offsets, long L,
-                    const int *__restrict__ probes, int P, const float *__restrict__ probe_bias, float *__restrict__ ws_s,
-                    int *__restrict__ ws_i, const u64 *__restrict__ mask) {
-    extern __shared__ __attribute__((aligned(16))) char search_smem[];
-    constexpr int CH = N < 8 ? N : 8;
-    constexpr int THREADS = 64 * kListWaves;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q = blockIdx.x / S, part = blockIdx.x % S;
-    ListWalk walk;
-    const long long T = walk.build<THREADS>(search_smem, N * K, list_offsets, L, probes + (long)q * P, P, B, tid);
-    const long long lo = T * part / S, hi = T * (part + 1) / S;           // (T <= 2^37, S <= 256)
-    if (lo >= hi) {                                          // no step: the empty list, and nothing is staged
-        if (tid < k) {
-            const long at = ((long)q * S + part) * k + tid;
-            ws_s[at] = __builtin_inff();
-            ws_i[at] = kNoIndex;
-        }
-        return;
-    }
-    tile_stage<1, THREADS>(reinterpret_cast<float *>(search_smem), tables, Q, q, N * K, tid);
-    const float *Tl = reinterpret_cast<const float *>(search_smem);
-    const float *brow = probe_bias + (long)q * P;
-
-    float ls = __builtin_inff(), ts = __builtin_inff();
-    int li = kNoIndex, tb = kNoIndex;
-    CodeChunk<CH> cur;
-    float t = 0.f;
-    ListCursorBias<MASKED> pos;
+    ListCursor<MASKED, BIAS> pos;
     long long step = lo + wave;
     pos.start(walk, step, hi, cur, t, codes, w, M, N, mask, brow, lane);
     while (step < hi) {
@@ -787,7 +691,7 @@ k_search_lists_bias(const float *__restrict__ tables, int Q, const uint8_t *__re
         float tn = t;
         float acc[1];
         tile_step<1, CH, N>(acc, cur, tn, Tl, codes, w, M, N, K, pos.b, pos.bnext);
-        list_insert(ls, li, ts, tb, score_finish(acc[0] + pos.bias, t, M), (int)pos.b, pos.offer(), k, lane);
+        list_insert(ls, li, ts, tb, score_finish(pos.biased(acc[0]), t, M), (int)pos.b, pos.offer(), k, lane);
         t = tn;
         pos.advance();
         step = nstep;

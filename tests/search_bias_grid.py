@@ -1,6 +1,7 @@
 """Residual codes list by list (mcq_search_scan_lists_bias, mcq_search_range_lists_bias_count / _fill, mcq_code_norms_based;
 include/mcq_residual.h rules 21-23): the numpy restatement of the biased score and of the based norms, the bias of a GPU case, and
-the value lists of the two launchers of the biased kernels, read from quantization_amd/csrc/mcq_api.hip.
+the cells of the two list launchers that carry a bias (their value lists are read from quantization_amd/csrc/mcq_api.hip by
+tests/search_selection_grid.py).
 
     score[q][b] = finish((S[q][b] + bias[q][p]), w[b])     p: the slot of row q whose list holds b
                   S: restate_sums of tests/search_metric_grid.py (rule 3's chain); then ONE float32 addition; then
@@ -15,11 +16,8 @@ is listed twice, each time with the bias of that naming's slot.
 The GPU cases are the case tables of tests/search_lists_grid.py and tests/search_range_lists_grid.py themselves: whatever
 those tables claim to reach (cut lists, list boundaries inside a wave's run, empty parts, padding rows, 4,096 probes) is
 checked against the launch arithmetic by their own host tests, and that arithmetic does not depend on a bias."""
-import re
-
 import numpy as np
 
-import search_grid as sg
 import search_lists_grid as lg
 import search_metric_grid as mg
 import search_selection_grid as sel
@@ -27,12 +25,6 @@ import search_selection_grid as sel
 ME = "tests/search_bias_grid.py"
 METRICS = lg.METRICS
 PATTERNS = (None, "half")                       # the masks of the GPU cases: none, and `half` of tests/search_mask_grid.py
-
-# launcher -> (what each of its pick<...> lists selects, in source order; the number of pick_bool calls)
-DISPATCHERS = {
-    "launch_lists_bias": (("metric", "N"), 1),
-    "launch_range_lists_bias": (("CH",), 1),
-}
 
 
 # ------------------------------------------------------------------ rule 21 in numpy
@@ -152,49 +144,24 @@ def restate_norms_based(C, codes, base, assign, D):
     return part[:, 0].copy()
 
 
-# ------------------------------------------------------------------ the launchers' value lists, and their cells
-def pick_lists(launcher, path=sel.API):
-    """the value lists of the pick<...> calls inside `launcher`, as search_selection_grid.pick_lists reads them"""
-    with open(path) as f:
-        src = f.read()
-    with open(sg.HDR) as f:
-        names = {m.group(1): int(m.group(2)) for m in re.finditer(r"constexpr\s+int\s+(kMetric\w+)\s*=\s*([0-9]+);", f.read())}
-    m = re.search(r"^int\s+" + launcher + r"\s*\(", src, re.M)
-    assert m, f"{launcher} moved out of mcq_api.hip or was renamed: update {ME}"
-    end = src.find("\n}\n", m.end())
-    assert end > 0
-    body = src[m.end():end]
-    what, bools = DISPATCHERS[launcher]
-    lists = re.findall(r"\bpick<([^<>]*)>\s*\(", body)
-    assert len(lists) == len(what) and len(re.findall(r"\bpick_bool\s*\(", body)) == bools, \
-        f"{launcher} no longer selects {what} and {bools} flag(s): update {ME}"
-    out = {}
-    for name, text in zip(what, lists):
-        vals = [names[t.strip()] if t.strip() in names else int(t.strip()) for t in text.split(",")]
-        assert len(set(vals)) == len(vals), f"{launcher}: pick<{text}> repeats a value"
-        out[name] = tuple(vals)
-    if launcher == "launch_range_lists_bias":
-        m = re.search(r"\(\s*a\.N\s*<\s*([0-9]+)\s*\?\s*a\.N\s*:\s*([0-9]+)\s*,", body)
-        assert m and m.group(1) == m.group(2), f"{launcher} no longer picks its chunk as min(N, cap): update {ME}"
-        out["cap"] = int(m.group(1))
-    return out
-
-
-# the cells tests/test_gpu_search_lists_bias.py and test_gpu_search_range_lists_bias.py launch: the layout and the shapes of
-# the lists cells of tests/search_selection_grid.py (K = 16, one N per test), three metrics, mask or none; the range kernel
-# at every N as well, count and fill
+# ------------------------------------------------------------------ the launchers' cells with a bias
+# launch_lists and launch_range_lists select a kernel with a bias by one more flag over the value lists of the calls without
+# one (search_selection_grid.pick_lists reads them, and counts the flags).  The cells tests/test_gpu_search_lists_bias.py and
+# test_gpu_search_range_lists_bias.py launch: the layout and the shapes of the lists cells of tests/search_selection_grid.py
+# (K = 16, one N per test), three metrics, mask or none; the range kernel at every N as well, count and fill
 CELL_NS = sel.NS
 CELL_MASKS = (False, True)
 CELL_SWEEPS = ("count", "fill")
 
 
 def coverage(path=sel.API):
-    """assert that the product of each launcher's value lists is exactly what the cells above launch -> cells per launcher"""
-    top = pick_lists("launch_lists_bias", path)
-    assert set(top["metric"]) == {mg.CODE[m] for m in METRICS}, f"launch_lists_bias: metrics {top['metric']}: update {ME}"
-    assert set(top["N"]) == set(CELL_NS), f"launch_lists_bias: N {top['N']} against the cells {CELL_NS}: update {ME}"
-    rng = pick_lists("launch_range_lists_bias", path)
-    assert set(rng["CH"]) == {min(N, rng["cap"]) for N in CELL_NS}, \
-        f"launch_range_lists_bias: CH {rng['CH']} against the cells {CELL_NS}: update {ME}"
-    return {"launch_lists_bias": len(top["N"]) * len(top["metric"]) * len(CELL_MASKS),
-            "launch_range_lists_bias": len(rng["CH"]) * len(CELL_SWEEPS) * len(CELL_MASKS)}
+    """assert that the product of each launcher's value lists is exactly what the cells above launch -> the cells with a
+    bias per launcher"""
+    top = sel.pick_lists("launch_lists", path)
+    assert set(top["metric"]) == {mg.CODE[m] for m in METRICS}, f"launch_lists: metrics {top['metric']}: update {ME}"
+    assert set(top["N"]) == set(CELL_NS), f"launch_lists: N {top['N']} against the cells {CELL_NS}: update {ME}"
+    rng = sel.pick_lists("launch_range_lists", path)
+    cap = sel.range_chunk_cap(path, "launch_range_lists")
+    assert set(rng["CH"]) == {min(N, cap) for N in CELL_NS}, f"launch_range_lists: CH {rng['CH']} against the cells {CELL_NS}: update {ME}"
+    return {"launch_lists": len(top["N"]) * len(top["metric"]) * len(CELL_MASKS),
+            "launch_range_lists": len(rng["CH"]) * len(CELL_SWEEPS) * len(CELL_MASKS)}

@@ -7,7 +7,8 @@ template arguments.  Nothing here is new launch arithmetic: the (QT, tiles, slic
 through scan_plan and search_range_grid.range_plan, the parts of a lists cell from search_lists_grid.lists_plan.  The value
 lists are read from mcq_api.hip by regex (as search_grid.constants() reads its constants), and coverage() asserts that the
 product of the lists of every dispatcher is what the cells below -- and, for the decode, the named cells of other tests --
-launch, so that a value added to a pick<...> list fails tests/test_search_selection_host.py until it gets a cell.
+launch, so that a value added to a pick<...> list fails tests/test_search_selection_host.py until it gets a cell.  The lists of
+launch_range_lists, and the cells of both list launchers with a bias, are held against tests/search_bias_grid.py.
 
   scan, sweeps   base cells: all 35 (QT, N), K = 16 (the tile cap is 16 at every N), Q = 1, 2, 3, 6, 11 for QT = 1, 2, 4, 8, 16:
                  every tile of QT >= 4 has a padding query; the waves' lists fill the LDS (lds = max(tables, lists))
@@ -38,7 +39,8 @@ ME = "tests/search_selection_grid.py"
 DISPATCHERS = {
     "launch_scan": (("metric", "QT", "N"), 1),
     "launch_range": (("QT", "CH"), 1),
-    "launch_lists": (("metric", "N"), 1),
+    "launch_lists": (("metric", "N"), 2),                 # masked or not, with a bias or without
+    "launch_range_lists": (("CH",), 2),
     "launch_decode_sliced": (("CH", "LPV"), 0),
     "launch_decode_blk": (("N", "LPV"), 0),
 }
@@ -112,15 +114,15 @@ CELLS = [Cell(N, 16, Q_OF_QT[qt], qt, 1, False) for qt in Q_OF_QT for N in NS] +
         [Cell(N, K, 2 * qt + 1, qt, 3, True) for qt, N, K in CAPPED]
 
 
-def range_chunk_cap(path=API):
-    """the largest chunk of the sweeps, read from the value launch_range picks on: a.N < cap ? a.N : cap"""
+def range_chunk_cap(path=API, launcher="launch_range"):
+    """the largest chunk of the sweeps, read from the value `launcher` picks on: a.N < cap ? a.N : cap"""
     with open(path) as f:
         src = f.read()
-    m = re.search(r"^int\s+launch_range\s*\(", src, re.M)
-    assert m, f"launch_range moved out of mcq_api.hip or was renamed: update {ME}"
+    m = re.search(r"^int\s+" + launcher + r"\s*\(", src, re.M)
+    assert m, f"{launcher} moved out of mcq_api.hip or was renamed: update {ME}"
     body = src[m.end():src.find("\n}\n", m.end())]
     m = re.search(r"\(\s*a\.N\s*<\s*([0-9]+)\s*\?\s*a\.N\s*:\s*([0-9]+)\s*,", body)
-    assert m and m.group(1) == m.group(2), f"launch_range no longer picks its chunk as min(N, cap): update {ME}"
+    assert m and m.group(1) == m.group(2), f"{launcher} no longer picks its chunk as min(N, cap): update {ME}"
     return int(m.group(1))
 
 
@@ -252,7 +254,7 @@ def coverage(path=API):
     assert set(lists["metric"]) == {mg.CODE[m] for m in METRICS}, f"launch_lists: metrics {lists['metric']}: update {ME}"
     assert set(lists["N"]) == set(NS) | UNREACHABLE["launch_lists"], f"launch_lists: N {lists['N']} against the cells {NS}: update {ME}"
     assert lg.lists_plan(LISTS_Q, LISTS_P, max(NS), LISTS_K, KTOP, lc).parts >= 1
-    out["launch_lists"] = len(lists["N"]) * len(lists["metric"]) * 2
+    out["launch_lists"] = len(lists["N"]) * len(lists["metric"]) * 2        # without a bias; with one: tests/search_bias_grid.py
 
     sliced = pick_lists("launch_decode_sliced", path)
     got = {(decode_sliced_ch(N), decode_sliced_lpv(dim)) for N in SLICED_NS for dim in SLICED_DIMS}

@@ -9,7 +9,7 @@ search_bias_grid.bias_for (normal values scaled to the spread of the case's tabl
   * for at least one query that probes two lists the result differs from the call without a bias (else the case shows nothing);
   * a second call returns identical bytes;
   * bias = None through the new entry is the old entry, bit for bit.
-Then every cell of launch_lists_bias once (the lists cells of tests/search_selection_grid.py), and the calls without a
+Then every cell of launch_lists with a bias once (the lists cells of tests/search_selection_grid.py), and the calls without a
 candidate."""
 import numpy as np
 import pytest
@@ -104,7 +104,7 @@ def test_lists_bias_case(case, metric, pattern):
     assert torch.equal(d_i, gi) and torch.equal(_i32(d_s), _i32(gs))
 
 
-# ------------------------------------------------------------------ every cell of launch_lists_bias, one N per test
+# ------------------------------------------------------------------ every cell of launch_lists with a bias, one N per test
 _CELL = {}
 
 

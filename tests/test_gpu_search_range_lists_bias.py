@@ -10,7 +10,7 @@ the thresholds of the range grid applied to the BIASED scores (queries with no h
   * some query's hits differ from the call without a bias;
   * probe_bias == NULL through the new entries is the old pair, bit for bit;
   * a fill with half the room stores the first half and nothing else.
-Then every cell of launch_range_lists_bias once, and the public call: an unsorted probe row with its bias gives the CSR of the
+Then every cell of launch_range_lists with a bias once, and the public call: an unsorted probe row with its bias gives the CSR of the
 sorted row with the bias permuted alike."""
 import numpy as np
 import pytest

@@ -3,7 +3,7 @@ companion header are declared as _lib.RESIDUAL_SIGNATURES binds them, exported a
 biased score (tests/search_bias_grid.py) equals a plain loop over (query, slot, position); the restatement of the based
 norms equals exact arithmetic on dyadic data; every argument check of the new entries answers in the documented order
 before anything touches the device (fake pointers, no launch); the argument errors of the Python interface precede any
-device work; the value lists of the two new launchers are exactly the cells the GPU tests launch; and list_assign /
+device work; the value lists of the two list launchers are exactly the cells the GPU tests launch with a bias; and list_assign /
 probe_bias against numpy."""
 import ctypes
 
@@ -315,24 +315,34 @@ def test_a_call_without_a_bias_takes_the_entries_it_took():
 # ------------------------------------------------------------------ selection
 def test_the_launchers_of_the_biased_kernels_select_exactly_the_cells_the_gpu_tests_launch():
     got = bg.coverage()
-    assert got == {"launch_lists_bias": 7 * 3 * 2, "launch_range_lists_bias": 4 * 2 * 2}
-    # the same value lists as the launchers without a bias: a call moves between the two by its bias alone
-    assert bg.pick_lists("launch_lists_bias") == sel.pick_lists("launch_lists")
-    assert bg.pick_lists("launch_range_lists_bias")["cap"] == sel.range_chunk_cap()
+    assert got == {"launch_lists": 7 * 3 * 2, "launch_range_lists": 4 * 2 * 2}
+    # the same value lists as without a bias: a call moves between the two by its bias alone.  One launcher each, whose
+    # bias flag is the innermost selection, below every pick<...> list
+    with open(sel.API) as f:
+        src = f.read()
+    assert "launch_lists_bias" not in src and "launch_range_lists_bias" not in src
+    for launcher in ("launch_lists", "launch_range_lists"):
+        assert sel.DISPATCHERS[launcher][1] == 2
+        body = src[src.index("int " + launcher + "("):]
+        body = body[:body.index("\n}\n")]
+        assert body.count("pick_bool(li.bias != nullptr,") == 1
+        assert body.rindex("pick<") < body.index("pick_bool(li.bias != nullptr,") < body.index("hipLaunchKernelGGL(")
+    assert sel.range_chunk_cap(launcher="launch_range_lists") == sel.range_chunk_cap()
     # a value added to a list has no cell: coverage() says so
     import os
     import tempfile
-    with open(sel.API) as f:
-        src = f.read()
-    at = src.index("int launch_lists_bias(")
-    changed = src[:at] + src[at:].replace("pick<1, 2, 4, 8, 16, 32, 64>", "pick<1, 2, 4, 8, 16, 32, 64, 128>", 1)
-    assert changed != src
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "api.hip")
-        with open(path, "w") as f:
-            f.write(changed)
-        with pytest.raises(AssertionError, match="launch_lists_bias"):
-            bg.coverage(path)
+    for launcher, old, new in (("launch_lists", "pick<1, 2, 4, 8, 16, 32, 64>", "pick<1, 2, 4, 8, 16, 32, 64, 128>"),
+                               ("launch_lists", "pick<kMetricL2, kMetricIP, kMetricCos>", "pick<kMetricL2, kMetricIP, kMetricCos, 3>"),
+                               ("launch_range_lists", "pick<1, 2, 4, 8>", "pick<1, 2, 4, 8, 16>")):
+        at = src.index("int " + launcher + "(")
+        changed = src[:at] + src[at:].replace(old, new, 1)
+        assert changed != src
+        with tempfile.TemporaryDirectory() as d:
+            path = os.path.join(d, "api.hip")
+            with open(path, "w") as f:
+                f.write(changed)
+            with pytest.raises(AssertionError, match=launcher + ":"):
+                bg.coverage(path)
     # the cells exist: the lists layout of the selection grid has two lists that are not empty in every row
     off, probes = sel.lists_layout()
     assert sorted(bg.rows_with_two_lists(off, probes)) == [0, 1, 2]

@@ -46,7 +46,8 @@ def _doctored(tmp_path, launcher, old, new):
     ("launch_decode_sliced", "pick<4, 8, 16>(", "pick<4, 8, 16, 32>("),
     ("launch_decode_blk", "pick<4, 2>(", "pick<4, 2, 1>("),
     ("launch_decode_blk", "pick<4, 8, 16>(", "pick<4, 8, 16, 32>("),
-    ("launch_lists", "pick_bool(", "pick_flag("),
+    ("launch_lists", "pick_bool(mask != nullptr,", "pick_flag(mask != nullptr,"),
+    ("launch_lists", "pick_bool(li.bias != nullptr,", "pick_flag(li.bias != nullptr,"),
     ("launch_scan", "launch_rc();", "pick<1, 2>(0, [](auto) { return 0; });"),
 ])
 def test_a_changed_pick_list_fails_the_coverage(tmp_path, launcher, old, new):
