@@ -508,6 +508,27 @@ size_t mcq_logits_workspace_bytes(long B, int N, int D);   /* also what mcq_logi
 int mcq_logits(const float *x, long B, const void *prepared, float lscale_exp, int N, int K, int D,
                float *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Where every array of `prepared` starts (host only; what the tests of the fixed-point products read the blob by).
+ * offsets_out[i], i < min(cap, 13), receive the byte offsets in this fixed order:
+ *    0 C       fp32 [N][K][mcq_padded_dim(D)]   scaled centers          7 bias    fp32 [N*K]
+ *    1 Q       fp32 [N*K]   |C[n][k] - mu_n|^2                          8 scales  fp32 [2]  (mcq_prepare_dev / _params)
+ *    2 Cf      int8 limb planes of the centered rows                     9 mean    fp32 [mcq_padded_dim(D)]
+ *    3 Ce      int32 [Rp]   their row exponents                         10 cmean   fp32 [N][mcq_padded_dim(D)]  mu_n
+ *    4 Wf      int8 limb planes of to_logits.weight                     11 G       fp32 [N*K][N*K]
+ *    5 We      int32 [Rp]   their row exponents                         12 total   = mcq_prepared_bytes(N, K, D)
+ *    6 wmu     fp32 [N*K]   fixdot(W_r, mean)
+ * Rp = N*K rounded up to 128 rows; a plane set holds Rp rows of D rounded up to 128 columns, byte ((c * 4 + l) * Rp + row) * 16 + k % 16
+ * for column 16 c + k % 16 and limb l (most significant first).  Returns 13; a shape outside the domain MCQ_EUNSUPPORTED or
+ * MCQ_EINVAL as mcq_prepare does; offsets_out == NULL or cap < 0 MCQ_EINVAL.                                          */
+int mcq_test_prepared_layout(int N, int K, int D, size_t *offsets_out, int cap);
+
+/* The x.C product of the index search on its own: out[b][r] = fixdot(x_b - mean, C_r - mu_n), fp32 [B][N*K], r = n*K + k.
+ * Launches exactly what the encode does for a chunk (the frames less the data mean to limb planes, then the product against the
+ * centered rows of `prepared`).  workspace >= mcq_logits_workspace_bytes(B, N, D); flags: MCQ_ENCODE_X_FP16 or 0 (anything
+ * else MCQ_EINVAL); the argument checks are those of mcq_logits, in its order.                                         */
+int mcq_test_xc(const float *x, long B, const void *prepared, int N, int K, int D, float *out, void *workspace,
+                size_t workspace_bytes, void *stream, unsigned flags);
+
 /* The wave-level selection of the search on its own: `cases` independent problems of 64 * per_lane scores each
  * (per_lane 1, 4 or 16: key i of lane l at position per_lane * l + i; -4 / -16: the slot-major layout, position 64 * i + l; -1004:
  * four keys per lane handled as positions in no particular order); out_v / out_p [cases][64] receive the cnt smallest by

@@ -83,6 +83,8 @@ SIGNATURES = {
     "mcq_search_range_lists_fill": _sig("i", "plppliiipplpipppplpzp"),
     "mcq_logits_workspace_bytes": _sig("z", "lii"),
     "mcq_logits": _sig("i", "plpfiiippzp"),
+    "mcq_test_prepared_layout": _sig("i", "iiipi"),
+    "mcq_test_xc": _sig("i", "plpiiippzpu"),
     "mcq_test_select": _sig("i", "piiippp"),
     "mcq_last_encode_launches": _sig("i"),
     "mcq_profile_encode": _sig("i", "plpfiiiipzpFIi"),

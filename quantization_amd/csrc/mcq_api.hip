@@ -1573,6 +1573,31 @@ int mcq_logits(const float *x, long B, const void *prepared, float lscale_exp, i
     return run_logits(x, B, prepared, lscale_exp, N, K, D, out, nullptr, logits_ws(workspace, B, N, D), static_cast<hipStream_t>(stream), 0);
 }
 
+int mcq_test_prepared_layout(int N, int K, int D, size_t *offsets_out, int cap) {
+    if (!domain_ok(N, K, D)) return domain_err(N, K, D);
+    if (!offsets_out || cap < 0) return MCQ_EINVAL;
+    const PreparedLayout l = prepared_layout(N, K, D);
+    const size_t offs[] = {l.offC, l.offQ, l.offCf, l.offCe, l.offWf, l.offWe, l.offWmu, l.offBias, l.offScales, l.offMean,
+                           l.offCMean, l.offG, l.total};
+    constexpr int n = (int)(sizeof(offs) / sizeof(offs[0]));
+    for (int i = 0; i < n && i < cap; ++i) offsets_out[i] = offs[i];
+    return n;
+}
+
+// the x.C product as run_encode forms it for a chunk: launch_fix_rows with P.mean, then launch_xc
+int mcq_test_xc(const float *x, long B, const void *prepared, int N, int K, int D, float *out, void *workspace,
+                size_t workspace_bytes, void *stream, unsigned flags) {
+    if (!domain_ok(N, K, D)) return MCQ_EUNSUPPORTED;
+    if (B == 0) return 0;
+    if (!x || !prepared || !out || B < 0 || !workspace || (flags & ~MCQ_ENCODE_X_FP16)) return MCQ_EINVAL;
+    if (workspace_bytes < mcq_logits_workspace_bytes(B, N, D)) return MCQ_EWORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const Prepared P = prepared_view(prepared, N, K, D);
+    const LogitsWs w = logits_ws(workspace, B, N, D);
+    if (const int rc = launch_fix_rows(x, (flags & MCQ_ENCODE_X_FP16) ? 1 : 0, B, D, D, w.xf, w.xe, nullptr, st, P.mean)) return rc;
+    return launch_xc(w.xf, w.xe, B, P.Cf, P.Ce, (long)N * K, D, out, st);
+}
+
 // ------------------------------------------------------------------ trainer pieces
 int mcq_logits_argmax(const float *x, long B, const void *prepared, float lscale_exp, int N, int K, int D,
                       float *logits_out, int64_t *argmax_out, void *workspace, size_t workspace_bytes, void *stream,

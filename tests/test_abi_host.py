@@ -95,6 +95,22 @@ def test_rejections_of_the_decode_logits_trainer_and_encode_entry_points():
     assert L.mcq_logits(None, 0, None, 1.0, 8, 256, 64, None, None, 0, None) == 0
     assert L.mcq_logits(None, -1, None, 1.0, 8, 256, 64, None, None, 0, None) == EINVAL
     assert L.mcq_logits(None, 4, None, 1.0, 8, 256, 64, None, None, 0, None) == EINVAL
+    # mcq_test_xc(x, B, prepared, N, K, D, out, ws, ws_bytes, stream, flags): the checks of mcq_logits in its order, then the flags
+    assert L.mcq_test_xc(None, 4, None, 3, 256, 64, None, None, 0, None, 0) == EUNSUP
+    assert L.mcq_test_xc(None, 4, None, 8, 8, 64, None, None, 0, None, 0) == EUNSUP
+    assert L.mcq_test_xc(None, 0, None, 8, 256, 64, None, None, 0, None, 0) == 0
+    assert L.mcq_test_xc(None, -1, None, 8, 256, 64, None, None, 0, None, 0) == EINVAL
+    assert L.mcq_test_xc(None, 4, None, 8, 256, 64, None, None, 0, None, 0) == EINVAL
+    assert L.mcq_test_xc(p, 4, p, 8, 256, 64, p, None, 1 << 30, None, 0) == EINVAL                      # null workspace
+    assert L.mcq_test_xc(p, 4, p, 8, 256, 64, p, p, 1 << 30, None, 2) == EINVAL                         # a flag that is not X_FP16
+    assert L.mcq_test_xc(p, 4, p, 8, 256, 64, p, p, 0, None, 4) == m.MCQ_EWORKSPACE
+    assert L.mcq_test_xc(p, 4, p, 8, 256, 64, p, p, L.mcq_logits_workspace_bytes(4, 8, 64) - 1, None, 0) == m.MCQ_EWORKSPACE
+    # mcq_test_prepared_layout(N, K, D, offsets_out, cap): the domain first (as mcq_prepare), then the pointer
+    assert L.mcq_test_prepared_layout(8, 8, 64, None, 13) == EUNSUP
+    assert L.mcq_test_prepared_layout(3, 256, 64, None, 13) == EINVAL
+    assert L.mcq_test_prepared_layout(8, 256, 64, None, 13) == EINVAL
+    assert L.mcq_test_prepared_layout(8, 256, 64, p, -1) == EINVAL
+    assert L.mcq_test_prepared_layout(8, 256, 64, p, 0) == 13
     # mcq_logits_argmax(x, B, prepared, lscale, N, K, D, logits_out, argmax_out, ws, ws_bytes, stream, flags)
     assert L.mcq_logits_argmax(None, 4, None, 1.0, 4, 512, 64, None, None, None, 0, None, 0) == EUNSUP
     assert L.mcq_logits_argmax(None, 4, None, 1.0, 3, 256, 64, None, None, None, 0, None, 0) == EUNSUP

@@ -68,7 +68,7 @@ def mismatches(header, table):
 def test_signatures_are_the_header():
     from quantization_amd import _lib
     hdr = header_signatures()
-    assert len(hdr) == 62 and "mcq_abi_version" in hdr and "mcq_profile_category_name" in hdr
+    assert len(hdr) == 64 and "mcq_abi_version" in hdr and "mcq_profile_category_name" in hdr
     assert hdr["mcq_profile_category_name"] == (ctypes.c_char_p, (ctypes.c_int,))
     assert hdr["mcq_rnorms_from_norms"] == (ctypes.c_int, (POINTER, ctypes.c_long, POINTER, POINTER))
     assert mismatches(hdr, _lib.SIGNATURES) == []
