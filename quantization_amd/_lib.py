@@ -1,4 +1,4 @@
-"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companion include/mcq_residual.h).
+"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h and include/mcq_probe.h).
 
 The library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950).  There
 is no CPU fallback: a missing library or a non-HIP tensor is an error.
@@ -103,6 +103,15 @@ RESIDUAL_SIGNATURES = {
 }
 RESIDUAL_SYMBOLS = tuple(RESIDUAL_SIGNATURES)
 
+# include/mcq_probe.h, the companion header of the probes the tests run single steps of the encode through, in the same form
+# (tests/test_er_probe_host.py parses that header and compares)
+PROBE_SIGNATURES = {
+    "mcq_test_er_workspace_bytes": _sig("z", "li"),
+    "mcq_test_er": _sig("i", "piiippplppipppzp"),
+    "mcq_test_xc_xx": _sig("i", "plpiiipppzpu"),
+}
+PROBE_SYMBOLS = tuple(PROBE_SIGNATURES)
+
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
 MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
@@ -122,7 +131,7 @@ def lib():
         raise McqError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950); quantization_amd has no CPU fallback")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES, **PROBE_SIGNATURES}.items():
         # an older build loaded through the A/B hook above may lack a symbol: it stays unbound, and calling it raises.
         # Without the hook a missing symbol fails here, at load
         if _ALT and not hasattr(L, name):

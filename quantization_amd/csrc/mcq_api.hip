@@ -3,6 +3,7 @@
 // arithmetic, kernel selection; every entry point enqueues on the caller's stream and returns (mcq.h has the contract).
 #include "../../include/mcq.h"
 #include "../../include/mcq_residual.h"
+#include "../../include/mcq_probe.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
 #include "mcq_loss_kernels.h"
@@ -415,22 +416,35 @@ int launch_tf_stage0(int K, int N, const float *G, const float *XC, const CT *id
     }
 }
 
-// E / R of a pass's vectors; a codebook entry of two bytes means K >= 512, so no more than kMaxRows / 512 codebooks
+// E / R of a pass's vectors; a codebook entry of two bytes means K >= 512, so no more than kMaxRows / 512 codebooks.
+// Up to 8,192 vectors: one launch that gathers the Gram entries itself.  Above: two launches, the Gram terms XCD by XCD and
+// then the sums; 4, 8 and 16 codebooks of one-byte entries take the dense form of the pair (mcq_tf_kernels.h: a lane per
+// vector / per (vector, column), the unordered pairs only), the other shapes a wave per request.  `stride`: the vectors the
+// Gram-terms buffer was carved for
 template <typename CT>
 int launch_tf_er(int N, const float *G, const float *XC, const CT *idx, const float *xx, long B, int K, float *E, float *R,
-                 float *gterms, const int *nact, const int *map, hipStream_t st) {
+                 float *gterms, long stride, const int *nact, const int *map, hipStream_t st, int form = -1) {
     const dim3 grid((unsigned)((B + 3) / 4)), block(256);
-    const bool direct = B <= 8192;          // one launch instead of two (E / R of a trainer batch: 4.9 + 4.7 -> about 5 us)
+    // one launch instead of two (E / R of a trainer batch: 4.9 + 4.7 -> about 5 us); form 0 / 1: mcq_test_er asks for one of them
+    const bool direct = form < 0 ? B <= 8192 : form == 0;
     return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
-        constexpr int NN = nn, VG = 4 * (64 / NN);      // vectors per workgroup of k_tf_gram_terms
+        constexpr int NN = nn, VG = 4 * (64 / NN);      // vectors per workgroup of k_tf_gram_terms, and of the dense k_tf_er
         if constexpr (sizeof(CT) == 2 && NN * 512 > kMaxRows) return MCQ_EUNSUPPORTED;
         else {
+            constexpr bool DENSE = sizeof(CT) == 1 && (NN == 4 || NN == 8 || NN == 16);
             if (!direct) {
-                hipLaunchKernelGGL((k_tf_gram_terms<NN, CT>), dim3((unsigned)(((B + VG - 1) / VG) * NN)), block, 0, st, G, idx, B, K, gterms, nact);
+                const long per = DENSE ? 256 : VG;          // vectors per workgroup of k_tf_gram_terms (dense: a lane each)
+                hipLaunchKernelGGL((k_tf_gram_terms<NN, CT, DENSE>), dim3((unsigned)(((B + per - 1) / per) * NN)), block, 0, st, G, idx, B, K,
+                                   gterms, nact, stride);
                 if (const int rc = counted_launch_rc()) return rc;
+                if constexpr (DENSE) {
+                    hipLaunchKernelGGL((k_tf_er<NN, CT, true>), dim3((unsigned)((B + VG - 1) / VG)), block, 0, st, gterms, XC, idx, xx, B, K,
+                                       E, R, nact, map, static_cast<const float *>(nullptr), stride);
+                    return counted_launch_rc();
+                }
             }
             hipLaunchKernelGGL((k_tf_er<NN, CT>), grid, block, 0, st, gterms, XC, idx, xx, B, K, E, R, nact, map,
-                               direct ? G : static_cast<const float *>(nullptr));
+                               direct ? G : static_cast<const float *>(nullptr), stride);
             return counted_launch_rc();
         }
     });
@@ -505,7 +519,7 @@ const char *const kCatNames[CAT_COUNT] = {
     "combine_level2",             // k_tf_comb at level 2 (8 codebooks: the last combine, which also forms E / R of the next pass)
     "tables_upper_levels",        // k_tf_table1 / k_tf_up above level 2
     "combine_upper_levels",       // k_tf_comb / k_tf_comb3 above level 2
-    "residual_energies",          // k_tf_gram_terms + k_tf_er (first pass of a call; later passes: inside the last combine)
+    "residual_energies",          // k_tf_gram_terms + k_tf_er (first pass; later passes: inside the last combine, or the dense pair again)
     "level1_combines_and_tables", // k_tf_level1: the level-1 combines and the cousin tables of level 2 in one launch
     "encode_tail",                // k_finalize / k_import_indexes / k_compact
 };
@@ -527,6 +541,16 @@ inline bool pass16_enabled() {
 inline long skip_min_batch() {
     const char *v = getenv("MCQ_SKIP_MIN_BATCH");
     return v ? atol(v) : 8192;      // (4,096 vectors: 0.472 ms with compaction, 0.477 without; 8,192: 0.773 / 0.800)
+}
+// chunks of at least this many vectors of 4, 8 or 16 codebooks form E / R of EVERY pass with the dense pair of launch_tf_er
+// instead of in the emitting wave of the pass before; MCQ_ER_DENSE_MIN=<n> moves the threshold (read per call; 0: any chunk --
+// up to 8,192 vectors the pair is the one direct launch --, a huge value: none)
+// (unprofiled bench pairs, 8 x 256, dim 512: 16,384 vectors 1.311 against 1.332 ms, 32,768 2.361 against 2.415, ranges apart;
+// at 8,192 the pair is the one direct launch, 10.5 us a pass against the 6 us the emit costs there: profiles/r24_ab_er_dense.txt)
+constexpr long kErDenseMin = 16384;
+inline long er_dense_min() {
+    const char *v = getenv("MCQ_ER_DENSE_MIN");
+    return v ? atol(v) : kErDenseMin;
 }
 
 // the combines of one refinement pass
@@ -719,7 +743,8 @@ struct PassState {
     int *map_cur = nullptr, *map_nxt, *map_spare, *cnt;
     const int *nact = nullptr;
     // E / R of the active slots; under skipping with E / R formed in the emit they move with the indexes into the packed
-    // slots, between w.E / w.R and a second pair in the Gram-terms buffer (which only the first pass's k_tf_gram_terms uses)
+    // slots, between w.E / w.R and a second pair in the Gram-terms buffer (which only the first pass's k_tf_gram_terms uses).
+    // With E / R formed ahead of every pass (er_dense_min()) nothing moves: w.E / w.R throughout, the buffer is k_tf_gram_terms' own
     float *E_cur, *R_cur, *E_alt, *R_alt;
 
     PassState(const WorkspaceT<CT> &w, long Bc, bool skip)
@@ -752,7 +777,10 @@ int run_passes(const EncodeCall &c, const WorkspaceT<CT> &w, long Bc, bool skip,
     }
     // E / R of pass it + 1 can be formed by the wave that emits the indexes of pass it (tf_emit), which saves that pass
     // its two E / R launches (4, 8 or 16 codebooks); under skipping k_compact moves them into the packed slots
-    const bool er_in_emit = (N == 4 || N == 8 || N == 16);
+    // -- except in chunks of er_dense_min() vectors or more, where the two dense launches ahead of every pass cost less than the
+    // dependent memory phase at the end of every emitting wave's life: k_compact then moves no E / R, the Gram-terms buffer is
+    // never borrowed, and a retired vector has none formed
+    const bool er_in_emit = (N == 4 || N == 8 || N == 16) && !(sizeof(CT) == 1 && Bc >= er_dense_min());
     bool er_ready = false;
     for (int it = 0; it < c.iters; ++it) {
         const bool last_pass = (it + 1 == c.iters);
@@ -761,7 +789,7 @@ int run_passes(const EncodeCall &c, const WorkspaceT<CT> &w, long Bc, bool skip,
         const bool capped = skip && it >= 3;
         if (!er_ready) {
             Timed t(c.prof, CAT_ER);
-            if (const int rc = launch_tf_er<CT>(N, P.G, w.XC, s.idx_cur, w.xx, Bc, K, s.E_cur, s.R_cur, w.gterms, s.nact, s.map_cur, c.st))
+            if (const int rc = launch_tf_er<CT>(N, P.G, w.XC, s.idx_cur, w.xx, Bc, K, s.E_cur, s.R_cur, w.gterms, Bc, s.nact, s.map_cur, c.st))
                 return rc;
         }
         er_ready = false;
@@ -1411,6 +1439,8 @@ static int prepare_impl(const float *centers, float cscale_exp, const float *sca
                           writable(P.wmu)), st))
         return rc;
     // Gram matrix of the scaled centers: the x.C product with the centers themselves as the frames
+    // (the dense E / R kernels RELY on G[r][c] == G[c][r] bit for bit, mcq_tf_kernels.h: fixdot sums the same integer limb
+    // products for (r, c) and (c, r), and the exponent ea + eb commutes; tests/test_gpu_er_dense.py compares G with its transpose)
     return launch_xc(P.Cf, P.Ce, rows, P.Cf, P.Ce, rows, D, writable(P.G), st);
 }
 
@@ -1584,9 +1614,28 @@ int mcq_test_prepared_layout(int N, int K, int D, size_t *offsets_out, int cap) 
     return n;
 }
 
-// the x.C product as run_encode forms it for a chunk: launch_fix_rows with P.mean, then launch_xc
-int mcq_test_xc(const float *x, long B, const void *prepared, int N, int K, int D, float *out, void *workspace,
-                size_t workspace_bytes, void *stream, unsigned flags) {
+// include/mcq_probe.h: E / R of B slots through launch_tf_er, in the form asked for
+size_t mcq_test_er_workspace_bytes(long B, int N) { return (B > 0 && N > 0) ? align256((size_t)B * N * N * 4) : 256; }
+
+int mcq_test_er(const void *prepared, int N, int K, int D, const float *xc, const float *xx, const uint8_t *idx, long B,
+                const int *nact, const int *map, int form, float *E_out, float *R_out, void *workspace, size_t workspace_bytes,
+                void *stream) {
+    if (!domain_ok(N, K, D)) return domain_err(N, K, D);
+    if (K > 256) return MCQ_EUNSUPPORTED;
+    if (B < 0 || (form != 0 && form != 1)) return MCQ_EINVAL;
+    if (B == 0) return 0;
+    if (!prepared || !xc || !xx || !idx || !E_out || !R_out || !workspace) return MCQ_EINVAL;
+    if (reinterpret_cast<uintptr_t>(idx) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return MCQ_EINVAL;
+    if (workspace_bytes < mcq_test_er_workspace_bytes(B, N)) return MCQ_EWORKSPACE;
+    const Prepared P = prepared_view(prepared, N, K, D);
+    return launch_tf_er<uint8_t>(N, P.G, xc, idx, xx, B, K, E_out, R_out, static_cast<float *>(workspace), B, nact, map,
+                                 static_cast<hipStream_t>(stream), form);
+}
+
+// the x.C product as run_encode forms it for a chunk: launch_fix_rows with P.mean (which also leaves |x - mean|^2 where
+// `xx` asks for it), then launch_xc
+static int test_xc(const float *x, long B, const void *prepared, int N, int K, int D, float *out, float *xx, void *workspace,
+                   size_t workspace_bytes, void *stream, unsigned flags) {
     if (!domain_ok(N, K, D)) return MCQ_EUNSUPPORTED;
     if (B == 0) return 0;
     if (!x || !prepared || !out || B < 0 || !workspace || (flags & ~MCQ_ENCODE_X_FP16)) return MCQ_EINVAL;
@@ -1594,8 +1643,20 @@ int mcq_test_xc(const float *x, long B, const void *prepared, int N, int K, int 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Prepared P = prepared_view(prepared, N, K, D);
     const LogitsWs w = logits_ws(workspace, B, N, D);
-    if (const int rc = launch_fix_rows(x, (flags & MCQ_ENCODE_X_FP16) ? 1 : 0, B, D, D, w.xf, w.xe, nullptr, st, P.mean)) return rc;
+    if (const int rc = launch_fix_rows(x, (flags & MCQ_ENCODE_X_FP16) ? 1 : 0, B, D, D, w.xf, w.xe, xx, st, P.mean)) return rc;
     return launch_xc(w.xf, w.xe, B, P.Cf, P.Ce, (long)N * K, D, out, st);
+}
+
+int mcq_test_xc(const float *x, long B, const void *prepared, int N, int K, int D, float *out, void *workspace,
+                size_t workspace_bytes, void *stream, unsigned flags) {
+    return test_xc(x, B, prepared, N, K, D, out, nullptr, workspace, workspace_bytes, stream, flags);
+}
+
+// include/mcq_probe.h: mcq_test_xc with the frames' |x - mean|^2 as well
+int mcq_test_xc_xx(const float *x, long B, const void *prepared, int N, int K, int D, float *xc_out, float *xx_out, void *workspace,
+                   size_t workspace_bytes, void *stream, unsigned flags) {
+    if (B > 0 && !xx_out) return MCQ_EINVAL;
+    return test_xc(x, B, prepared, N, K, D, xc_out, xx_out, workspace, workspace_bytes, stream, flags);
 }
 
 // ------------------------------------------------------------------ trainer pieces

@@ -87,10 +87,21 @@ struct Stamps {
 // k_tf_gram_terms gathers them XCD by XCD instead: workgroup id mod N = m, a wave takes 64 / N vectors x the N entries of
 // row block m, so an XCD only ever touches the rows of its own codebooks (2 MB); the terms go to gterms[b][m][m2] and
 // k_tf_er reads its 64 terms as one coalesced line.
-template <int N, typename CT = uint8_t>
+// DENSE: the form for large batches further down (tf_gram_terms_dense / tf_er_dense, planes `stride` floats apart)
+template <int N, typename CT>
+__device__ __forceinline__ void tf_gram_terms_dense(const float *__restrict__ G, const CT *__restrict__ idx, long B, int K,
+                                                    float *__restrict__ gterms, const int *__restrict__ nact, long stride);
+template <int N, typename CT>
+__device__ __forceinline__ void tf_er_dense(const float *__restrict__ gterms, const float *__restrict__ XC, const CT *__restrict__ idx,
+                                            const float *__restrict__ xx, long B, int K, float *__restrict__ E_out,
+                                            float *__restrict__ R_out, const int *__restrict__ nact, const int *__restrict__ map,
+                                            long stride);
+
+template <int N, typename CT = uint8_t, bool DENSE = false>
 __global__ void __launch_bounds__(256)
 k_tf_gram_terms(const float *__restrict__ G, const CT *__restrict__ idx, long B, int K, float *__restrict__ gterms,
-                const int *__restrict__ nact) {
+                const int *__restrict__ nact, long stride) {
+    if constexpr (DENSE) { tf_gram_terms_dense<N, CT>(G, idx, B, K, gterms, nact, stride); return; }
     constexpr int VW = 64 / N;                     // vectors per wave
     if (nact) B = *nact;
     const int m = (int)(blockIdx.x % N);
@@ -151,16 +162,131 @@ __device__ __forceinline__ void tf_er_wave(long b, long bx, const CT *__restrict
     if (lane == 0) E_out[b] = E;
 }
 
-template <int N, typename CT = uint8_t>
+template <int N, typename CT = uint8_t, bool DENSE = false>
 __global__ void __launch_bounds__(256)
 k_tf_er(const float *__restrict__ gterms, const float *__restrict__ XC, const CT *__restrict__ idx,
         const float *__restrict__ xx, long B, int K, float *__restrict__ E_out, float *__restrict__ R_out,
-        const int *__restrict__ nact, const int *__restrict__ map, const float *__restrict__ Gdirect) {
+        const int *__restrict__ nact, const int *__restrict__ map, const float *__restrict__ Gdirect, long stride) {
+    if constexpr (DENSE) { tf_er_dense<N, CT>(gterms, XC, idx, xx, B, K, E_out, R_out, nact, map, stride); return; }
     if (nact) B = *nact;
     const long b = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
     const long bx = map ? (long)map[b] : b;          // row of the per-call arrays (XC, xx)
     tf_er_wave<N, false, CT>(b, bx, idx + b * N, 0, gterms, Gdirect, XC, xx, K, E_out, R_out);
+}
+
+// ------------------------------------------------------- E, R: the dense pair
+// Large batches of 4, 8 or 16 codebooks of one-byte entries.  The two kernels above are waves that issue one memory request
+// and leave (65,536 x N of them at the bench shape); these do the same arithmetic with one wave for 64 gathers' owners.
+//
+// G is exactly symmetric (fixdot sums the same integer limb products for (r, c) and (c, r), and ea + eb commutes), so a
+// vector needs its N (N + 1) / 2 unordered pairs only.  Row block m owns the pairs (m, (m + d) mod N), d = 0 .. N / 2, the last one for m < N / 2 only: every
+// pair once, the same number per block up to one.  The terms lie in PLANES, one per (m, d): plane (m, d)[b] = G[o_m][o_(m+d)].
+// (The x.C gathers of the second kernel cost the same in the first, as N more planes: 23.7 + 7.3 us against 13.7 + 17.8 at
+// 65,536 vectors of 8 x 256 -- the two kinds of gather do not hide each other.)
+constexpr int tf_gram_planes(int N) { return N / 2 + 1; }      // per row block; N * (N / 2 + 1) <= N * N floats per vector
+
+// the plane that holds G[o_m][o_n], or its mirror G[o_n][o_m]
+template <int N>
+__device__ __forceinline__ int tf_gram_plane(int m, int n) {
+    const int d = (n - m) & (N - 1);
+    const bool own = d < N / 2 || (d == N / 2 && m < N / 2);
+    return own ? m * tf_gram_planes(N) + d : n * tf_gram_planes(N) + (N - d);
+}
+
+// entry j of N one-byte codes held as N / 4 words (j need not be a compile-time value: no indexed registers)
+template <int NW>
+__device__ __forceinline__ int tf_code_at(const uint32_t (&w)[NW], int j) {
+    uint32_t x = w[0];
+#pragma unroll
+    for (int i = 1; i < NW; ++i) x = (j >> 2) == i ? w[i] : x;
+    return (int)((x >> ((j & 3) * 8)) & 0xffu);
+}
+
+// Workgroup id mod N = row block m (an XCD touches the rows of its own codebooks only, as above); a LANE takes a vector: its N
+// codes in one load, the block's N / 2 (+ 1) gathers in flight together, then one coalesced store per plane.  `stride`: floats
+// between planes (the chunk's vectors; B may be the smaller *nact)
+template <int N, typename CT>
+__device__ __forceinline__ void tf_gram_terms_dense(const float *__restrict__ G, const CT *__restrict__ idx, long B, int K,
+                                                    float *__restrict__ gterms, const int *__restrict__ nact, long stride) {
+    static_assert(sizeof(CT) == 1 && (N == 4 || N == 8 || N == 16), "the dense form: 4, 8 or 16 codebooks of one-byte entries");
+    constexpr int NW = N / 4, ND = tf_gram_planes(N);
+    if (nact) B = *nact;
+    const int m = (int)(blockIdx.x % N);
+    const long b = (long)(blockIdx.x / N) * 256 + threadIdx.x;
+    if (b >= B) return;
+    // (N bytes per vector and the array 16-byte aligned: one load of N / 4 words)
+    const uint32_t *src = static_cast<const uint32_t *>(__builtin_assume_aligned(idx + b * N, N));
+    uint32_t w[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) w[i] = src[i];
+    const size_t NK = (size_t)N * K;
+    const float *row = G + (size_t)(m * K + tf_code_at<NW>(w, m)) * NK;
+    const bool half = m < N / 2;                    // this block also owns the pairs at distance N / 2
+    float g[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const int m2 = (m + d) & (N - 1);
+        g[d] = (d < N / 2 || half) ? row[m2 * K + tf_code_at<NW>(w, m2)] : 0.f;
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+        if (d < N / 2 || half) gterms[(size_t)(m * ND + d) * stride + b] = g[d];
+}
+
+// A wave takes 64 / N vectors: lane = (vector, column n), registers = rows m.  The sums are tf_er_wave's bit for bit.  There
+// term t = m N + m2 sits in lane t % 64, slot t / 64, and gsum is the 64-lane xor butterfly (levels 32 .. 1) over the per-lane
+// chain of slots.  With R = 64 / N rows per slot the levels 32 .. N pair row r with row r ^ (level / N): here two registers of
+// one lane; the levels N / 2 .. 1 pair the columns: here lanes of a vector's group.  fp32 addition commutes, so both lanes
+// of a butterfly pair hold the same value after a level and every position reproduces the original lane's.  The butterfly's
+// zero lanes (4 codebooks: 48 of the 64; XC: 64 - N) are KEPT as additions of +0: x + (+0) is x except for x = -0.
+template <int N, typename CT>
+__device__ __forceinline__ void tf_er_dense(const float *__restrict__ gterms, const float *__restrict__ XC, const CT *__restrict__ idx,
+                                            const float *__restrict__ xx, long B, int K, float *__restrict__ E_out,
+                                            float *__restrict__ R_out, const int *__restrict__ nact, const int *__restrict__ map,
+                                            long stride) {
+    static_assert(sizeof(CT) == 1 && (N == 4 || N == 8 || N == 16), "the dense form: 4, 8 or 16 codebooks of one-byte entries");
+    constexpr int VW = 64 / N;                     // vectors per wave
+    constexpr int RS = 64 / N;                     // rows per slot of tf_er_wave's layout (4 codebooks: rows 4 .. 15 are zero lanes)
+    if (nact) B = *nact;
+    const int lane = lane_id(), n = lane % N;
+    const long b = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * VW + lane / N;
+    if (b >= B) return;                            // (a vector's N lanes leave together: the shuffles below stay inside the group)
+    const long bx = map ? (long)map[b] : b;
+    const float xt = XC[(size_t)bx * N * K + n * K + idx[b * N + n]];            // XC[o_n]: one sector from HBM
+    const float xxb = xx[bx];
+    float g[N];                                    // G[o_m][o_n], m = 0 .. N - 1
+#pragma unroll
+    for (int m = 0; m < N; ++m) g[m] = gterms[(size_t)tf_gram_plane<N>(m, n) * stride + b];
+    float p[RS];
+#pragma unroll
+    for (int r = 0; r < RS; ++r) {
+        p[r] = r < N ? g[r] : 0.f;
+#pragma unroll
+        for (int m = r + RS; m < N; m += RS) p[r] = p[r] + g[m];              // the chain of slots
+    }
+#pragma unroll
+    for (int h = RS / 2; h >= 1; h >>= 1)
+#pragma unroll
+        for (int r = 0; r < h; ++r) p[r] = p[r] + p[r + h];                  // levels 32 .. N
+    float gsum = p[0], xsum = xt;
+#pragma unroll
+    for (int s = 32; s >= N; s >>= 1) xsum = xsum + 0.f;
+#pragma unroll
+    for (int s = N / 2; s >= 1; s >>= 1) {
+        gsum = gsum + __shfl_xor(gsum, s, 64);
+        xsum = xsum + __shfl_xor(xsum, s, 64);
+    }
+    const float E = (gsum - 2.0f * xsum) + xxb;
+    float col = g[0], gnn = g[0];
+#pragma unroll
+    for (int m = 1; m < N; ++m) {
+        col = col + g[m];
+        gnn = (m == n) ? g[m] : gnn;
+    }
+    const float xo = col - xt;
+    R_out[b * N + n] = (E - 2.0f * xo) + gnn;
+    if (n == 0) E_out[b] = E;
 }
 
 // ------------------------------------------------------------------ stage 0
