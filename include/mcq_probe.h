@@ -39,6 +39,50 @@ int mcq_test_er(const void *prepared, int N, int K, int D, const float *xc, cons
 int mcq_test_xc_xx(const float *x, long B, const void *prepared, int N, int K, int D, float *xc_out, float *xx_out,
                    void *workspace, size_t workspace_bytes, void *stream, unsigned flags);
 
+
+/* Where the arrays of one chunk of B vectors lie in the encode's workspace (host only; reported by the function that lays the
+ * workspace out for the encode, not by a copy of its arithmetic).  out[i], i < min(cap, 64), receive, in this fixed order:
+ *   out[2 a], out[2 a + 1]   byte offset and byte size of array a; an array the shape does not have (a level without a list,
+ *                            the group tables of fewer than 8 codebooks) reports 0, 0
+ *      a = 0 idx   1 idxB   2 idxC   3 final_idx     codes, [B][N] of `code width` bytes (idx: the current codes, refined in place)
+ *          4, 5 map[0..1]  int32[B]      6 cnt  int32[64]                      (fixed-point skipping)
+ *          7 E  float[B]   8 R  float[B][N]   9 xx  float[B]   10 gterms  float[B][N][N]   11 XC  float[B][N*K]
+ *          12 xf  limb planes of the centered frames   13 xe  their exponents, int32 per padded row
+ *          14 ent            level-0 lists: [B][N][kc[0]] codebook entries of `code width` bytes
+ *          15 .. 19 pos[1..5]   level v: uint8[B][N >> v][kc[v]][2], the positions in the two halves' lists
+ *          20 .. 25 S[0..5]     level v: float[B][N >> v][kc[v]], the candidates' scores
+ *          26, 27 tabs[0..1]    group tables (two consecutive levels)
+ *   out[56 .. 61]  kc[0..5], the list length of every level (also of levels the shape has no list of)
+ *   out[62]        the code width: 1 byte up to 256 entries per codebook, 2 above
+ *   out[63]        the end of the last array rounded up to 256: what one chunk of B occupies
+ * Every offset is a multiple of 256.  Returns 64 (MCQ_TEST_PASS_LAYOUT_VALUES).  Checks in this order: the domain of (N, K, D) as
+ * the encode (MCQ_EUNSUPPORTED / MCQ_EINVAL); B < 1, out == NULL or cap < 0: MCQ_EINVAL.                                        */
+#define MCQ_TEST_PASS_LAYOUT_VALUES 64
+int mcq_test_pass_layout(long B, int N, int K, int D, size_t *out, int cap);
+
+/* ONE refinement pass of B vectors as ONE chunk, from caller-supplied codes, through the launchers of the encode's own pass loop
+ * (the chunk start with imported codes: frames to limb planes, k_import_indexes, the x.C product; then E / R, stage 0 and the
+ * combines as separate launches -- never the LDS-resident pass of 8 x 16 and 16 x 16, no fixed-point skipping of its own, E / R
+ * of a next pass not formed).  What the pass leaves in `workspace` is read by mcq_test_pass_layout(B, ...).
+ *   x            fp32 [B][D], the frames (row r)
+ *   idx_in       int64 [B][N], the current codes of the SLOTS, every one in [0, K)
+ *   idx_out      int64 [B][N]: the new codes of slot b go to row b, or to row map[b]; they are also left in the workspace's idx,
+ *                slot by slot.  May alias idx_in where map is NULL
+ *   nact         NULL, or a device int: only the slots below *nact are processed, nothing of the other slots is written
+ *   map          NULL (slot b is row b of x), or int32[B]: slot b holds the vector of row map[b] (its x.C products, its |x|^2,
+ *                its row of idx_out)
+ *   flags        MCQ_TEST_PASS_CAPPED: the capped launchers (grid-stride instantiations of stage 0, the level-0 and level-1
+ *                kernels and the last combine, as the encode takes them from the fourth pass of fixed-point skipping on)
+ *   workspace    256-byte aligned, large enough for the encode to take B vectors as one chunk
+ *                (mcq_encode_workspace_bytes(B, N, K, D) is, for every B up to the default chunk)
+ * mcq_last_encode_launches() counts the launches of the call.  Checks in this order: the domain of (N, K, D); N == 1 (no lists):
+ * MCQ_EUNSUPPORTED; B < 0 or an unknown flag: MCQ_EINVAL; B == 0 returns 0 and looks at nothing; NULL x / prepared / idx_in /
+ * idx_out / workspace or a misaligned workspace: MCQ_EINVAL; a workspace that does not hold B as one chunk: MCQ_EWORKSPACE.   */
+#define MCQ_TEST_PASS_CAPPED 1u
+int mcq_test_pass(const float *x, long B, const void *prepared, int N, int K, int D, const int64_t *idx_in, int64_t *idx_out,
+                  const int *nact /* may be NULL */, const int *map /* may be NULL */, unsigned flags, void *workspace,
+                  size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

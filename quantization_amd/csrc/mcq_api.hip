@@ -132,25 +132,40 @@ long default_chunk(int N, int K, int D) {
     return c & ~127L;
 }
 
+// The arrays carve() lays out, by number (mcq_test_pass_layout of include/mcq_probe.h reports them under these numbers; in
+// memory a level's positions and scores lie together).  A level has its slots whether it holds a list or not
+enum { CV_IDX = 0, CV_IDXB, CV_IDXC, CV_FINAL_IDX, CV_MAP0, CV_MAP1, CV_CNT, CV_E, CV_R, CV_XX, CV_GTERMS, CV_XC, CV_XF, CV_XE,
+       CV_ENT, CV_POS1, CV_S0 = CV_POS1 + kTfLevels - 1, CV_TABS0 = CV_S0 + kTfLevels, CV_TABS1, CV_COUNT };
+struct CarveExtents {
+    size_t off[CV_COUNT] = {}, bytes[CV_COUNT] = {};      // (an array carve did not lay out: 0, 0)
+    size_t total = 0;
+};
+
+// ext: where every array lies, for the probe (carve is the only place that knows)
 template <typename CT>
-WorkspaceT<CT> carve(void *ws, long Bc, int N, int K, int D) {
+WorkspaceT<CT> carve(void *ws, long Bc, int N, int K, int D, CarveExtents *ext = nullptr) {
     char *p = static_cast<char *>(ws);
     size_t off = 0;
-    auto take = [&](size_t bytes) { char *q = p + off; off = align256(off + bytes); return q; };
+    auto take = [&](int what, size_t bytes) {
+        if (ext) { ext->off[what] = off; ext->bytes[what] = bytes; }
+        char *q = p + off;
+        off = align256(off + bytes);
+        return q;
+    };
     WorkspaceT<CT> w;
-    w.idx = reinterpret_cast<CT *>(take((size_t)Bc * N * sizeof(CT)));
-    w.idxB = reinterpret_cast<CT *>(take((size_t)Bc * N * sizeof(CT)));
-    w.idxC = reinterpret_cast<CT *>(take((size_t)Bc * N * sizeof(CT)));
-    w.final_idx = reinterpret_cast<CT *>(take((size_t)Bc * N * sizeof(CT)));
-    for (int i = 0; i < 2; ++i) w.map[i] = reinterpret_cast<int *>(take((size_t)Bc * 4));
-    w.cnt = reinterpret_cast<int *>(take(64 * 4));
-    w.E = reinterpret_cast<float *>(take((size_t)Bc * 4));
-    w.R = reinterpret_cast<float *>(take((size_t)Bc * N * 4));
-    w.xx = reinterpret_cast<float *>(take((size_t)Bc * 4));
-    w.gterms = reinterpret_cast<float *>(take((size_t)Bc * N * N * 4));
-    w.XC = reinterpret_cast<float *>(take((size_t)Bc * N * K * 4));
-    w.xf = reinterpret_cast<int8_t *>(take(fix_plane_bytes(Bc, D)));
-    w.xe = reinterpret_cast<int *>(take((size_t)fix_round_rows(Bc) * 4));
+    w.idx = reinterpret_cast<CT *>(take(CV_IDX, (size_t)Bc * N * sizeof(CT)));
+    w.idxB = reinterpret_cast<CT *>(take(CV_IDXB, (size_t)Bc * N * sizeof(CT)));
+    w.idxC = reinterpret_cast<CT *>(take(CV_IDXC, (size_t)Bc * N * sizeof(CT)));
+    w.final_idx = reinterpret_cast<CT *>(take(CV_FINAL_IDX, (size_t)Bc * N * sizeof(CT)));
+    for (int i = 0; i < 2; ++i) w.map[i] = reinterpret_cast<int *>(take(CV_MAP0 + i, (size_t)Bc * 4));
+    w.cnt = reinterpret_cast<int *>(take(CV_CNT, 64 * 4));
+    w.E = reinterpret_cast<float *>(take(CV_E, (size_t)Bc * 4));
+    w.R = reinterpret_cast<float *>(take(CV_R, (size_t)Bc * N * 4));
+    w.xx = reinterpret_cast<float *>(take(CV_XX, (size_t)Bc * 4));
+    w.gterms = reinterpret_cast<float *>(take(CV_GTERMS, (size_t)Bc * N * N * 4));
+    w.XC = reinterpret_cast<float *>(take(CV_XC, (size_t)Bc * N * K * 4));
+    w.xf = reinterpret_cast<int8_t *>(take(CV_XF, fix_plane_bytes(Bc, D)));
+    w.xe = reinterpret_cast<int *>(take(CV_XE, (size_t)fix_round_rows(Bc) * 4));
     const int nlev = tf_levels(N);
     w.tf.ent = nullptr;
     w.tf.out_i64 = nullptr;
@@ -166,12 +181,13 @@ WorkspaceT<CT> carve(void *ws, long Bc, int N, int K, int D) {
         w.tf.S[v] = nullptr;
         if (v >= nlev) continue;                       // no list of that level
         const int kc = w.tf.kc[v];
-        if (v == 0) w.tf.ent = reinterpret_cast<uint8_t *>(take((size_t)Bc * N * kc * sizeof(CT)));
-        else w.tf.pos[v] = reinterpret_cast<uint8_t *>(take((size_t)Bc * (N >> v) * kc * 2));
-        w.tf.S[v] = reinterpret_cast<float *>(take((size_t)Bc * (N >> v) * kc * 4));
+        if (v == 0) w.tf.ent = reinterpret_cast<uint8_t *>(take(CV_ENT, (size_t)Bc * N * kc * sizeof(CT)));
+        else w.tf.pos[v] = reinterpret_cast<uint8_t *>(take(CV_POS1 + v - 1, (size_t)Bc * (N >> v) * kc * 2));
+        w.tf.S[v] = reinterpret_cast<float *>(take(CV_S0 + v, (size_t)Bc * (N >> v) * kc * 4));
     }
     const size_t tf = tf_tab_floats(N, K);
-    for (int i = 0; i < 2; ++i) w.tabs[i] = tf ? reinterpret_cast<float *>(take((size_t)Bc * tf * 4)) : nullptr;
+    for (int i = 0; i < 2; ++i) w.tabs[i] = tf ? reinterpret_cast<float *>(take(CV_TABS0 + i, (size_t)Bc * tf * 4)) : nullptr;
+    if (ext) ext->total = off;
     return w;
 }
 
@@ -762,13 +778,48 @@ struct PassState {
     }
 };
 
+// One refinement pass of a chunk: E / R of the slots (unless the pass before formed them in its emitting wave), stage 0, the
+// combines.  run_passes below calls it pass by pass; mcq_test_pass of include/mcq_probe.h calls it once.  emit_er: the emitting
+// wave of this pass forms E / R of the next one (er_ready then leaves as true); last_pass: the winners also go to `out`
+template <typename CT>
+int run_one_pass(const EncodeCall &c, const WorkspaceT<CT> &w, long Bc, const PassState<CT> &s, bool last_pass, bool emit_er,
+                 bool capped, bool &er_ready, const ChunkOut &out) {
+    const int N = c.N, K = c.K;
+    const Prepared &P = c.P;
+    if (!er_ready) {
+        Timed t(c.prof, CAT_ER);
+        if (const int rc = launch_tf_er<CT>(N, P.G, w.XC, s.idx_cur, w.xx, Bc, K, s.E_cur, s.R_cur, w.gterms, Bc, s.nact, s.map_cur, c.st))
+            return rc;
+    }
+    er_ready = false;
+    {
+        Timed t(c.prof, CAT_STAGE0);
+        if (const int rc = launch_tf_stage0(K, N, P.G, w.XC, s.idx_cur, s.R_cur, P.Q, Bc, (N == 1) ? 1 : w.tf.kc[0],
+                                            reinterpret_cast<CT *>(w.tf.ent), w.tf.S[0], (N == 1) ? s.idx_new : static_cast<CT *>(nullptr),
+                                            s.nact, s.map_cur, c.st, capped))
+            return rc;
+    }
+    if (N >= 2) {
+        TfLists L = w.tf;
+        L.map = s.map_cur;
+        if (emit_er && !last_pass) {
+            L.erG = P.G; L.erXC = w.XC; L.erxx = w.xx; L.erE = s.E_cur; L.erR = s.R_cur; L.erK = K;
+            er_ready = true;
+        }
+        if (last_pass) { L.out_i64 = out.i64; L.out_u8 = out.bytes(); L.out_pack = out.bytes_pack(); }
+        WorkspaceT<CT> wc = w;
+        wc.E = s.E_cur; wc.R = s.R_cur;
+        if (const int rc = run_tf_combines<CT>(P.G, s.idx_cur, s.idx_new, wc, L, Bc, N, K, s.nact, c.st, c.prof, capped)) return rc;
+    }
+    return 0;
+}
+
 // The refinement passes of a chunk as separate launches.  With two codebooks or more the last pass's winners go straight to
 // the caller's arrays (tf_emit; under skipping to row map[slot]); a single codebook's stay in w.idx for k_finalize.  skip: after
 // every pass but an emitting one k_compact retires the vectors the pass left unchanged (to the caller's arrays) and packs the rest
 template <typename CT>
 int run_passes(const EncodeCall &c, const WorkspaceT<CT> &w, long Bc, bool skip, const ChunkOut &out) {
-    const int N = c.N, K = c.K;
-    const Prepared &P = c.P;
+    const int N = c.N;
     PassState<CT> s(w, Bc, skip);
     if (skip) {     // (a kernel, not hipMemsetAsync: replays of a captured encode have to clear them too, LAB_NOTEBOOK.md)
         hipLaunchKernelGGL(k_zero_counts, dim3(1), dim3(64), 0, c.st, w.cnt, 64);
@@ -787,32 +838,8 @@ int run_passes(const EncodeCall &c, const WorkspaceT<CT> &w, long Bc, bool skip,
         // capped grids over the active vectors from the fourth pass on (passes 1-3 hold nearly every vector of an
         // untrained batch, and the strided kernels cost the dense passes a few per cent: DESIGN.md section 4)
         const bool capped = skip && it >= 3;
-        if (!er_ready) {
-            Timed t(c.prof, CAT_ER);
-            if (const int rc = launch_tf_er<CT>(N, P.G, w.XC, s.idx_cur, w.xx, Bc, K, s.E_cur, s.R_cur, w.gterms, Bc, s.nact, s.map_cur, c.st))
-                return rc;
-        }
-        er_ready = false;
-        {
-            Timed t(c.prof, CAT_STAGE0);
-            if (const int rc = launch_tf_stage0(K, N, P.G, w.XC, s.idx_cur, s.R_cur, P.Q, Bc, (N == 1) ? 1 : w.tf.kc[0],
-                                                reinterpret_cast<CT *>(w.tf.ent), w.tf.S[0], (N == 1) ? s.idx_new : static_cast<CT *>(nullptr),
-                                                s.nact, s.map_cur, c.st, capped))
-                return rc;
-        }
+        if (const int rc = run_one_pass<CT>(c, w, Bc, s, last_pass, er_in_emit, capped, er_ready, out)) return rc;
         const bool emits = N >= 2 && last_pass;
-        if (N >= 2) {
-            TfLists L = w.tf;
-            L.map = s.map_cur;
-            if (er_in_emit && !last_pass) {
-                L.erG = P.G; L.erXC = w.XC; L.erxx = w.xx; L.erE = s.E_cur; L.erR = s.R_cur; L.erK = K;
-                er_ready = true;
-            }
-            if (emits) { L.out_i64 = out.i64; L.out_u8 = out.bytes(); L.out_pack = out.bytes_pack(); }
-            WorkspaceT<CT> wc = w;
-            wc.E = s.E_cur; wc.R = s.R_cur;
-            if (const int rc = run_tf_combines<CT>(P.G, s.idx_cur, s.idx_new, wc, L, Bc, N, K, s.nact, c.st, c.prof, capped)) return rc;
-        }
         if (skip && !emits) {
             {
                 Timed t(c.prof, CAT_TAIL);
@@ -895,6 +922,20 @@ int run_encode(const float *x, long B, const void *prepared, float lscale, int N
                                       init_idx, flags, logits_out, codes_also);
     return run_encode_t<uint8_t>(x, B, prepared, lscale, N, K, D, iters, out_u8, out_i64, workspace, workspace_bytes, st, prof,
                                  init_idx, flags, logits_out, codes_also);
+}
+
+// mcq_test_pass of include/mcq_probe.h: one pass of B vectors as ONE chunk from imported codes -- the chunk start, then
+// run_one_pass as the last pass of a call without skipping, on the slots / rows the caller names
+template <typename CT>
+int test_pass(const EncodeCall &c, const float *x, long B, const int64_t *idx_in, int64_t *idx_out, const int *nact, const int *map,
+              bool capped, void *workspace) {
+    const WorkspaceT<CT> w = carve<CT>(workspace, B, c.N, c.K, c.D);
+    if (const int rc = launch_chunk_start<CT>(c, w, x, B, idx_in, nullptr)) return rc;
+    PassState<CT> s(w, B, false);
+    s.nact = nact;
+    s.map_cur = const_cast<int *>(map);       // (read only: nothing rotates without k_compact)
+    bool er_ready = false;
+    return run_one_pass<CT>(c, w, B, s, true, false, capped, er_ready, ChunkOut{nullptr, idx_out, nullptr, 1});
 }
 
 // floats per lane of k_decode_backward when every row involved is 16-byte aligned.  Codebooks of 64 entries and more: 4 (a
@@ -1657,6 +1698,41 @@ int mcq_test_xc_xx(const float *x, long B, const void *prepared, int N, int K, i
                    size_t workspace_bytes, void *stream, unsigned flags) {
     if (B > 0 && !xx_out) return MCQ_EINVAL;
     return test_xc(x, B, prepared, N, K, D, xc_out, xx_out, workspace, workspace_bytes, stream, flags);
+}
+
+// include/mcq_probe.h: where carve() puts every array of one chunk of B vectors
+int mcq_test_pass_layout(long B, int N, int K, int D, size_t *out, int cap) {
+    if (!domain_ok(N, K, D)) return domain_err(N, K, D);
+    if (B < 1 || !out || cap < 0) return MCQ_EINVAL;
+    CarveExtents e;
+    const TfLists tf = K > 256 ? carve<uint16_t>(nullptr, B, N, K, D, &e).tf : carve<uint8_t>(nullptr, B, N, K, D, &e).tf;
+    constexpr int n = 2 * CV_COUNT + kTfLevels + 2;
+    static_assert(n == MCQ_TEST_PASS_LAYOUT_VALUES, "include/mcq_probe.h");
+    size_t v[n];
+    for (int i = 0; i < CV_COUNT; ++i) { v[2 * i] = e.off[i]; v[2 * i + 1] = e.bytes[i]; }
+    for (int i = 0; i < kTfLevels; ++i) v[2 * CV_COUNT + i] = (size_t)tf.kc[i];
+    v[n - 2] = code_bytes_of(K);
+    v[n - 1] = e.total;
+    for (int i = 0; i < n && i < cap; ++i) out[i] = v[i];
+    return n;
+}
+
+// include/mcq_probe.h: one refinement pass of B vectors as one chunk (test_pass, beside run_encode)
+int mcq_test_pass(const float *x, long B, const void *prepared, int N, int K, int D, const int64_t *idx_in, int64_t *idx_out,
+                  const int *nact, const int *map, unsigned flags, void *workspace, size_t workspace_bytes, void *stream) {
+    g_last_launches = 0;
+    if (!domain_ok(N, K, D)) return domain_err(N, K, D);
+    if (N < 2) return MCQ_EUNSUPPORTED;
+    if (B < 0 || (flags & ~MCQ_TEST_PASS_CAPPED)) return MCQ_EINVAL;
+    if (B == 0) return 0;
+    if (!x || !prepared || !idx_in || !idx_out || !workspace) return MCQ_EINVAL;
+    if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return MCQ_EINVAL;
+    const size_t per = workspace_per_vector(N, K, D), slack = workspace_slack(D);
+    if (workspace_bytes < slack + per || (long)((workspace_bytes - slack) / per) < B) return MCQ_EWORKSPACE;     // the encode's chunk rule
+    const EncodeCall c{prepared_view(prepared, N, K, D), 1.0f, N, K, D, 1, 0u, static_cast<hipStream_t>(stream), nullptr};
+    const bool capped = (flags & MCQ_TEST_PASS_CAPPED) != 0;
+    if (K > 256) return test_pass<uint16_t>(c, x, B, idx_in, idx_out, nact, map, capped, workspace);
+    return test_pass<uint8_t>(c, x, B, idx_in, idx_out, nact, map, capped, workspace);
 }
 
 // ------------------------------------------------------------------ trainer pieces
