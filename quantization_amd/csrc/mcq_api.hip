@@ -530,8 +530,8 @@ const char *const kCatNames[CAT_COUNT] = {
     "stage0_tables",              // k_tf_stage0 / k_tf_stage0_k16
     "xc_product",                 // k_fgemm<FG_STORE>
     "combine_level0",             // k_tf_pair0
-    "combine_level1",             // k_tf_pair1 (4 codebooks: the last combine)
-    "tables_level1",              // k_tf_table1 (more than 16 codebooks)
+    "combine_level1",             // k_tf_pair1 (4 codebooks: the last combine; 8 and 16 codebooks in chunks of lazy_tables_min() and more)
+    "tables_level1",              // k_tf_table1 after k_tf_pair1: the masked cousin tables of level 2 (8 codebooks; 16: tables_upper_levels)
     "combine_level2",             // k_tf_comb at level 2 (8 codebooks: the last combine, which also forms E / R of the next pass)
     "tables_upper_levels",        // k_tf_table1 / k_tf_up above level 2
     "combine_upper_levels",       // k_tf_comb / k_tf_comb3 above level 2
@@ -568,6 +568,18 @@ inline long er_dense_min() {
     const char *v = getenv("MCQ_ER_DENSE_MIN");
     return v ? atol(v) : kErDenseMin;
 }
+// chunks of at least this many vectors of 8 or 16 codebooks of 32 entries or more (one-byte entries) build their cousin tables
+// AFTER the level-1 combines and only where the level-2 lists look (tf_table1, USED2): k_tf_pair1, then the masked k_tf_table1,
+// instead of the one k_tf_level1 launch.  MCQ_LAZY_TABLES_MIN=<n> moves the threshold (read per call; 0: any chunk, a huge value:
+// none).  Above 4,096, so that the launches tests/test_gpu_launch_census.py pins at 256 vectors stay what they are
+// (unprofiled bench pairs, 8 x 256, dim 512, three each, this sequence against the one launch: 4,096 vectors 0.463-0.465 against
+// 0.449-0.454 ms -- the extra boundary loses --, 8,192 0.766-0.767 against 0.764-0.769, overlap, 16,384 1.314-1.324 against
+// 1.335-1.341 and 32,768 2.399-2.406 against 2.464-2.469, ranges apart: profiles/r26_ab_lazy_tables.txt)
+constexpr long kLazyTablesMin = 16384;
+inline long lazy_tables_min() {
+    const char *v = getenv("MCQ_LAZY_TABLES_MIN");
+    return v ? atol(v) : kLazyTablesMin;
+}
 
 // the combines of one refinement pass
 template <typename CT>
@@ -601,12 +613,36 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
     }
     // the level-1 combines and the cousin tables of level 2 share a launch (k_tf_level1): same workgroup-to-XCD mapping as the two
     // launches, one boundary and one tail less (5.95 -> 5.86 ms per encode of 65,536 vectors, 0.55 -> 0.51 ms at 4,096)
-    const bool fuse_l1 = (N >= 8);
+    // -- except in chunks of lazy_tables_min() vectors or more (8 / 16 codebooks of 32 entries or more, one-byte entries): the level-1
+    // combines as k_tf_pair1, then ONE k_tf_table1 launch that builds the cousin tables of level 2 -- with 16 codebooks those of
+    // level 3 as well, into tabs[1] -- on the candidates the level-2 lists name.  A launch more with 8 codebooks, none with 16
+    const bool lazy = sizeof(CT) == 1 && !small && (N == 8 || N == 16) && B >= lazy_tables_min();
+    const bool fuse_l1 = (N >= 8) && !lazy;
     // 16 codebooks: the 16 cousin tables of level 3 ride along (into tabs[1]).  With 256-entry codebooks at 65,536 vectors
     // that launch is 0.93 ms long and the merge bought nothing (23.99 / 23.92 against 23.90 / 24.0 ms per encode); a trainer
     // step of the first phase (16 x 16 codebooks, 4,096 vectors) saves a 29 us launch per pass
     const bool fuse_l3 = fuse_l1 && N == 16 && small;
-    if (fuse_l1) {
+    if (lazy) {
+        if constexpr (sizeof(CT) == 1) {
+            const int ntab1 = (N >> 3) * 4, ntab3 = (N == 16) ? 16 : 1, per3 = (N == 16) ? 4 : 1;
+            const unsigned pair_blocks = (unsigned)(B * (N / 4)), tab_blocks = (unsigned)(B * ntab1);
+            const unsigned vgrid = tab_blocks + (N == 16 ? (unsigned)(B * ntab3) : 0u);
+            const int rc = pick_bool(capped, [&](auto strided) {
+                constexpr bool STRIDED = strided;
+                {
+                    Timed t(prof, CAT_LEVEL1);
+                    hipLaunchKernelGGL((k_tf_pair1<16, 16, CT, STRIDED>), dim3(pass_grid(pair_blocks, capped, kCapWave)), wave, 0, st, G, idx_cur,
+                                       w.E, L, B, N, K, L.kc[2], static_cast<CT *>(nullptr), nact);
+                    if (const int rc1 = counted_launch_rc()) return rc1;
+                }
+                Timed t(prof, N == 16 ? CAT_TABLES_UP : CAT_TABLES);      // (16 codebooks: the category of their level-3 launch)
+                hipLaunchKernelGGL((k_tf_table1<16, 16, CT, true, STRIDED>), dim3(pass_grid(vgrid, capped, kCapWave)), wave, 0, st, G, idx_cur,
+                                   L, B, N, K, ntab1, 2, w.tabs[0], nact, tab_blocks, ntab3, per3, w.tabs[1], vgrid);
+                return counted_launch_rc();
+            });
+            if (rc) return rc;
+        }
+    } else if (fuse_l1) {
         const int keep = L.kc[2];
         const int groups2 = N >> 3, per1 = 2, ntab1 = groups2 * per1 * per1;
         const unsigned pair_blocks = (unsigned)(B * (N / 4)), tab_blocks = (unsigned)(B * ntab1);
@@ -640,19 +676,24 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
         CT *fin = last ? idx_new : nullptr;
         const int per1 = 1 << (v - 1), ntab1 = groups * per1 * per1;
         const int cat_tab = (v == 2) ? CAT_TABLES : CAT_TABLES_UP, cat_comb = (v == 2) ? CAT_COMBINE : CAT_COMBINE_UP;
-        if (!(fuse_l1 && v == 2) && !(fuse_l3 && v == 3)) {     // (these tables came with the level-1 combines)
+        if (!(fuse_l1 && v == 2) && !(fuse_l3 && v == 3) && !lazy) {     // (these tables came with the level-1 combines, or right after them)
             Timed t(prof, cat_tab);
             const int rc = pick_leaf_lists<CT>(K, [&](auto kc0) {
                 constexpr int KC = kc0;
-                hipLaunchKernelGGL((k_tf_table1<KC, KC, CT>), dim3((unsigned)(B * ntab1)), wave, 0, st, G, idx_cur, L, B, N, K, ntab1, per1,
-                                   w.tabs[0], nact);
+                // (every launch here is of level 3 or above and follows the level-1 combines: lists of 16 one-byte entries take the
+                // mask of the level-2 lists at no boundary -- 16 codebooks below lazy_tables_min(), 32 and 64 codebooks: 16 x 256,
+                // dim 1024, 256 / 1,024 / 4,096 vectors 0.449 / 0.652 / 1.577 against 0.453 / 0.665 / 1.637 ms, 32 x 256 at 4,096 /
+                // 32,768 vectors 10.12 / 79.2 against 11.24 / 88.3 ms, ranges apart everywhere: profiles/r26_ab_lazy_tables.txt)
+                constexpr bool USED2 = sizeof(CT) == 1 && KC == 16;
+                hipLaunchKernelGGL((k_tf_table1<KC, KC, CT, USED2>), dim3((unsigned)(B * ntab1)), wave, 0, st, G, idx_cur, L, B, N, K, ntab1, per1,
+                                   w.tabs[0], nact, (unsigned)(B * ntab1), 1, 1, static_cast<float *>(nullptr), (unsigned)(B * ntab1));
                 return counted_launch_rc();
             });
             if (rc) return rc;
         }
         if (N == 16 && v == 3) {       // two groups of eight: levels 2 and 3 in one kernel, tables in LDS
             Timed t(prof, cat_comb);
-            const float *t3 = fuse_l3 ? w.tabs[1] : w.tabs[0];
+            const float *t3 = (fuse_l3 || lazy) ? w.tabs[1] : w.tabs[0];
             const int rc = pick_leaf_lists<CT>(K, [&](auto kc0) {
                 constexpr int KC = kc0;
                 hipLaunchKernelGGL((k_tf_comb3<KC, 2 * KC, 2 * KC, CT>), dim3((unsigned)B), dim3(256), 0, st, idx_cur, w.E, L, B, N, t3, idx_new, nact);

@@ -774,10 +774,20 @@ k_tf_pair0s(const float *__restrict__ G, const uint8_t *__restrict__ idx, const 
 // plus the border).  The sets come from a 16-lane OR-reduction of position bits, the compact rank of a position is
 // a popcount, and the four compact leaf tables live in LDS.  Every entry is computed by the same formula as in the
 // full table, so the results are identical.
-template <int KCH, int KC, typename CT = uint8_t>
+//
+// USED2 (cousin tables, lists of 16, one-byte entries; the level-2 lists of X's and Y's parents are written): only what a LATER
+// READER can reach is built.  k_tf_comb, k_tf_up and k_tf_comb3 all index T_1[X][Y] with i0 = px[2 i], jj0 = py[2 j] of the
+// level-2 lists, and the 32 candidates of such a list name 10 to 13 of the 16 candidates of a half (tools/exp_lazy_tables.py).
+// The names are OR-reduced into usedX / usedY; a candidate outside them contributes no position bit, so the sets A, B, the
+// border lanes and the core iterations shrink by themselves (52-64 -> 29-41 core gathers per leaf table), and in the sum phase
+// a lane forms the entries of used rows and columns only.  *stmask: bit v set = t[v] is such an entry (the others are 0); the
+// caller stores a lane's four entries only if one of them is, so the rows no list names and the four-column groups without a
+// named column are NOT written -- no reader looks at them.  Every entry that is formed is formed as without the flag.
+template <int KCH, int KC, typename CT = uint8_t, bool USED2 = false>
 __device__ __forceinline__ void tf_table1(const float *__restrict__ G, const CT *__restrict__ idx, const TfLists &L,
                                           long b, int N, int K, int X, int Y, float *leaf /* LDS [4][KCH*KCH + 64] */,
-                                          float (&t)[KC * KC / 64], Stamps &stp) {
+                                          float (&t)[KC * KC / 64], Stamps &stp, uint32_t *stmask = nullptr) {
+    static_assert(!USED2 || (KCH == 16 && KC == 16 && sizeof(CT) == 1), "the mask exists for lists of 16 one-byte entries");
     constexpr int VPLH = KCH * KCH / 64, VPL = KC * KC / 64, MH = KCH * KCH;
     const int lane = lane_id();
     const CT *id = idx + b * N;
@@ -803,12 +813,30 @@ __device__ __forceinline__ void tf_table1(const float *__restrict__ G, const CT 
         int mypos = (w < 2 ? px : py)[2 * c + (w & 1)];
         int myent = ent[(b * N + cb) * KCH + c];                    // entry at level-0 position c of that codebook
         int oldv = id[cb];                                          // current entry of this quarter's codebook
+        int myu2 = 0;
+        if constexpr (USED2) {
+            // the level-2 lists (32 candidates each) of the parents: lanes 0-31 the half that is X, lanes 32-63 the half that is Y
+            const int Z = lane < 32 ? X : Y;
+            myu2 = L.pos[2][((b * (N >> 2) + (Z >> 1)) * (2 * KC) + (lane & 31)) * 2 + (Z & 1)];
+            asm volatile("" : "+v"(myu2));
+        }
         asm volatile("" : "+v"(mypos), "+v"(myent), "+v"(oldv));
         stp.at(1);                                                  // list bytes in
         int oldq[4];                                                // current entries of codebooks 2X, 2X+1, 2Y, 2Y+1
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) oldq[qq] = __builtin_amdgcn_readlane(oldv, 16 * qq);
         uint32_t m = 1u << mypos;
+        uint32_t usedX = 0xFFFFu, usedY = 0xFFFFu;     // the candidates of X / Y a level-2 list names (wave-uniform)
+        if constexpr (USED2) {
+            uint32_t u = 1u << myu2;
+            u |= (uint32_t)dpp_i<0x121>((int)u);
+            u |= (uint32_t)dpp_i<0x122>((int)u);
+            u |= (uint32_t)dpp_i<0x124>((int)u);
+            u |= (uint32_t)dpp_i<0x128>((int)u);
+            usedX = (uint32_t)__builtin_amdgcn_readlane((int)u, 0) | (uint32_t)__builtin_amdgcn_readlane((int)u, 16);
+            usedY = (uint32_t)__builtin_amdgcn_readlane((int)u, 32) | (uint32_t)__builtin_amdgcn_readlane((int)u, 48);
+            if (!(((w < 2 ? usedX : usedY) >> c) & 1u)) m = 0;      // candidate c of this quarter's list: never read
+        }
         m |= (uint32_t)dpp_i<0x121>((int)m);     // row_ror 1, 2, 4, 8: OR over the 16 lanes of the quarter
         m |= (uint32_t)dpp_i<0x122>((int)m);
         m |= (uint32_t)dpp_i<0x124>((int)m);
@@ -882,6 +910,25 @@ __device__ __forceinline__ void tf_table1(const float *__restrict__ G, const CT 
         }
         wave_lds_fence();
         const int i = lane >> 2, j0 = 4 * (lane & 3);
+        if constexpr (USED2) {
+            // row i and columns j0 .. j0 + 3 of this lane: the used ones only (the ranks of the others were never set)
+            const uint32_t sm = ((usedX >> i) & 1u) ? (usedY >> j0) & 0xFu : 0u;
+            *stmask = sm;
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) t[v] = 0.f;
+            if (sm) {
+                const int ri0 = crank[i], ri1 = crank[16 + i];
+#pragma unroll
+                for (int v = 0; v < VPL; ++v)
+                    if ((sm >> v) & 1u) {
+                        const int rj0 = crank[32 + j0 + v], rj1 = crank[48 + j0 + v];
+                        t[v] = ((leaf[ri0 * RS + rj0] + leaf[LS + ri0 * RS + rj1]) + leaf[2 * LS + ri1 * RS + rj0]) +
+                               leaf[3 * LS + ri1 * RS + rj1];
+                    }
+            }
+            stp.at(3);
+            return;
+        }
         const int ri0 = crank[i], ri1 = crank[16 + i];
 #pragma unroll
         for (int v = 0; v < VPL; ++v) {
@@ -1007,18 +1054,27 @@ __device__ __forceinline__ void tf_pair1_body(unsigned bid, float *leaf, const f
     stp.flush(2, bid, 64);
 }
 
-template <int KCH, int KC, typename CT = uint8_t>
+template <int KCH, int KC, typename CT = uint8_t, bool STRIDED = false>
 __global__ void __launch_bounds__(64)
 k_tf_pair1(const float *__restrict__ G, const CT *__restrict__ idx, const float *__restrict__ E, TfLists L, long B,
            int N, int K, int keep, CT *__restrict__ idx_final, const int *__restrict__ nact) {
     __shared__ __attribute__((aligned(16))) float leaf[tf_leaf_lds_floats(KCH, sizeof(CT))];
-    tf_pair1_body<KCH, KC, CT>(blockIdx.x, leaf, G, idx, E, L, B, N, K, keep, idx_final, nact);
+    if constexpr (!STRIDED) {
+        tf_pair1_body<KCH, KC, CT>(blockIdx.x, leaf, G, idx, E, L, B, N, K, keep, idx_final, nact);
+        return;
+    }
+    // (capped grid: see k_tf_stage0; the grid is a multiple of 8, so a workgroup stays on its XCD)
+    const unsigned need = nact ? (unsigned)*nact * (unsigned)(N >> 2) : gridDim.x;
+    for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
+        tf_pair1_body<KCH, KC, CT>(c, leaf, G, idx, E, L, B, N, K, keep, idx_final, nact);
+        wave_lds_fence();
+    }
 }
 
 // T_1 of COUSIN pairs under the siblings of a higher level -> tabs[b][t][KC*KC].  One wave per (b, t); workgroup id
 // mod ntab = t, so an XCD reads the leaf blocks of its own tables only.  Under sibling pair g each side has `per`
 // level-1 groups: t = (g * per + a) * per + c  ->  X = 2 g per + a,  Y = (2 g + 1) per + c.
-template <int KCH, int KC, typename CT = uint8_t>
+template <int KCH, int KC, typename CT = uint8_t, bool USED2 = false>
 __device__ __forceinline__ void tf_table1_body(unsigned bid, float *leaf, const float *__restrict__ G, const CT *__restrict__ idx,
                                                const TfLists &L, long B, int N, int K, int ntab, int per, float *__restrict__ tabs,
                                                const int *__restrict__ nact) {
@@ -1033,9 +1089,16 @@ __device__ __forceinline__ void tf_table1_body(unsigned bid, float *leaf, const 
     const int c = t & (per - 1), a = (t >> psh) & (per - 1), g = t >> (2 * psh);
     const int X = 2 * g * per + a, Y = (2 * g + 1) * per + c;
     float tv[VPL];
-    tf_table1<KCH, KC, CT>(G, idx, L, b, N, K, X, Y, leaf, tv, stp);
+    uint32_t sm = 0;
+    tf_table1<KCH, KC, CT, USED2>(G, idx, L, b, N, K, X, Y, leaf, tv, stp, &sm);
     float *dst = tabs + ((size_t)(b * ntab + t) * (KC * KC) + VPL * lane);
-    if constexpr (VPL == 4) {
+    if constexpr (USED2) {
+        // a lane with a named entry among its four stores all four as ONE 16-byte store, the others as zeros; the lanes of rows
+        // and of four-column groups without one store nothing.  (Entry by entry -- up to four masked dword stores per lane -- the
+        // launch was SLOWER than the unmasked one: 204 against 170 us at 65,536 vectors, profiles/r26_ab_lazy_tables.txt)
+        static_assert(VPL == 4, "");
+        if (sm) __builtin_nontemporal_store((f32x4){tv[0], tv[1], tv[2], tv[3]}, reinterpret_cast<f32x4 *>(dst));
+    } else if constexpr (VPL == 4) {
         __builtin_nontemporal_store((f32x4){tv[0], tv[1], tv[2], tv[3]}, reinterpret_cast<f32x4 *>(dst));
     } else {
 #pragma unroll
@@ -1045,12 +1108,32 @@ __device__ __forceinline__ void tf_table1_body(unsigned bid, float *leaf, const 
     stp.flush(3, bid, 64);
 }
 
-template <int KCH, int KC, typename CT = uint8_t>
+// A second range of tables (ntab2, per2 -> tabs2: the workgroups from tab_blocks on; 16 codebooks, the cousins of level 3 beside
+// those of level 2) and the capped grid (STRIDED, vgrid = the full grid) as in k_tf_level1 below.  USED2: see tf_table1 -- the
+// launch then FOLLOWS the level-1 combines, whose level-2 lists it reads.
+template <int KCH, int KC, typename CT = uint8_t, bool USED2 = false, bool STRIDED = false>
 __global__ void __launch_bounds__(64)
 k_tf_table1(const float *__restrict__ G, const CT *__restrict__ idx, TfLists L, long B, int N, int K, int ntab,
-            int per, float *__restrict__ tabs, const int *__restrict__ nact) {
+            int per, float *__restrict__ tabs, const int *__restrict__ nact, unsigned tab_blocks, int ntab2, int per2,
+            float *__restrict__ tabs2, unsigned vgrid) {
     __shared__ __attribute__((aligned(16))) float leaf[tf_leaf_lds_floats(KCH, sizeof(CT))];
-    tf_table1_body<KCH, KC, CT>(blockIdx.x, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
+    if constexpr (!STRIDED) {
+        if (blockIdx.x < tab_blocks) tf_table1_body<KCH, KC, CT, USED2>(blockIdx.x, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
+        else tf_table1_body<KCH, KC, CT, USED2>(blockIdx.x - tab_blocks, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);
+        return;
+    }
+    // (the active ids of the first range rounded up to a multiple of 8, so that an id of the second keeps its XCD)
+    unsigned r1 = tab_blocks, r2 = vgrid - tab_blocks;
+    if (nact) {
+        const unsigned na = (unsigned)*nact;
+        r1 = (na * (unsigned)ntab + 7u) & ~7u;
+        r2 = r2 ? na * (unsigned)ntab2 : 0u;
+    }
+    for (unsigned c = blockIdx.x; c < r1 + r2; c += gridDim.x) {
+        if (c < r1) tf_table1_body<KCH, KC, CT, USED2>(c, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
+        else tf_table1_body<KCH, KC, CT, USED2>(c - r1, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);
+        wave_lds_fence();
+    }
 }
 
 // The sibling combines of level 1 and the cousin tables the level-2 combine needs, in ONE launch: both read the level-1 lists
