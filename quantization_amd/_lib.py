@@ -1,4 +1,4 @@
-"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h and include/mcq_probe.h).
+"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h, include/mcq_probe.h and include/mcq_wide.h).
 
 The library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950).  There
 is no CPU fallback: a missing library or a non-HIP tensor is an error.
@@ -114,6 +114,16 @@ PROBE_SIGNATURES = {
 }
 PROBE_SYMBOLS = tuple(PROBE_SIGNATURES)
 
+# include/mcq_wide.h, the companion header of the top-k search past 64 neighbours, in the same form and in its order
+# (tests/test_search_wide_host.py parses that header and compares)
+WIDE_SIGNATURES = {
+    "mcq_search_wide_workspace_bytes": _sig("z", "lliii"),
+    "mcq_search_wide": _sig("i", "plppliiiippppzp"),
+    "mcq_search_wide_lists_workspace_bytes": _sig("z", "liiii"),
+    "mcq_search_wide_lists": _sig("i", "plppliiiipplpippppzp"),
+}
+WIDE_SYMBOLS = tuple(WIDE_SIGNATURES)
+
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
 MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
@@ -133,7 +143,7 @@ def lib():
         raise McqError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950); quantization_amd has no CPU fallback")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES, **PROBE_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES, **PROBE_SIGNATURES, **WIDE_SIGNATURES}.items():
         # an older build loaded through the A/B hook above may lack a symbol: it stays unbound, and calling it raises.
         # Without the hook a missing symbol fails here, at load
         if _ALT and not hasattr(L, name):

@@ -4,6 +4,7 @@
 #include "../../include/mcq.h"
 #include "../../include/mcq_residual.h"
 #include "../../include/mcq_probe.h"
+#include "../../include/mcq_wide.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
 #include "mcq_loss_kernels.h"
@@ -12,6 +13,7 @@
 #include "mcq_train_kernels.h"
 #include "mcq_search_kernels.h"
 #include "mcq_range_kernels.h"
+#include "mcq_wide_kernels.h"
 
 #include <cstdlib>
 #include <iterator>
@@ -1223,6 +1225,76 @@ int search_topk(const float *tables, long Q, const uint8_t *codes, const float *
     return launch_rc();
 }
 
+// ---- the search past 64 neighbours (mcq_wide_kernels.h; rules 24-27 of include/mcq_wide.h; mirrored by wide_plan of
+// tests/search_wide_grid.py): the parts of lists_plan, capped so that the merge of a query streams at most kWideMergeEntries
+// entries per entry of its sorted half -- 64 parts up to k = 512 and 32 beyond, where lists_parts alone would hand the merge
+// of a single query 256 lists.  A function of the call's shape alone.  P is 1 for a call over the whole store.
+struct WidePlan {
+    int parts;
+    size_t lds, ws_half;
+};
+
+WidePlan wide_plan(long Q, int P, int N, int K, int k) {
+    const int cap = kWideMergeEntries / wide_half(k);
+    int parts = lists_parts(Q);
+    parts = parts > cap ? cap : parts;
+    return {parts, (size_t)wide_lds_bytes(N * K, P, k), align256((size_t)Q * parts * k * 4)};   // scores, then positions
+}
+
+// search_check with the cap of this feature: k in 65 .. 1,024 passes where search_check tests k > 64, a larger one fails there
+int wide_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
+               const uint64_t *mask, const ListsIn *li, bool outs_ok, const void *workspace, bool *empty) {
+    const int as = k > kWideMaxK ? 65 : (k > 64 ? 64 : k);
+    return search_check(tables, Q, codes, w, B, N, K, as, metric, mask, li, outs_ok, workspace, empty);
+}
+
+// li.probes == NULL: the whole store as one list; a bias is a null test inside the kernel, not a flag
+int launch_wide(const WidePlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
+                int N, int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
+    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
+            return pick_bool(mask != nullptr, [&](auto masked) {
+                constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
+                constexpr bool MASKED = masked;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_wide<NN, M, MASKED>),
+                                                     wide_lds_bytes(64 * 256, kListMaxProbes, kWideMaxK)))
+                    return rc;
+                hipLaunchKernelGGL((k_search_wide<NN, M, MASKED>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kWideWaves),
+                                   p.lds, st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, li.list_offsets, li.L,
+                                   li.probes, li.P, ws_s, ws_i, reinterpret_cast<const u64 *>(mask), li.bias);
+                return launch_rc();
+            });
+        });
+    });
+}
+
+// both wide entry points: over the whole store (li == NULL), or list by list
+int search_wide(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
+                const uint64_t *mask, const ListsIn *li, float *out_score, int64_t *out_index, void *workspace,
+                size_t workspace_bytes, void *stream) {
+    bool empty;
+    if (const int rc = wide_check(tables, Q, codes, w, B, N, K, k, metric, mask, li, Q == 0 || (out_score && out_index), workspace, &empty))
+        return rc;
+    if (Q == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws_s = nullptr;
+    int *ws_i = nullptr;
+    int S = 0;                                                            // lists per query; 0 (no candidate anywhere): the fill of rule 4
+    if (!empty) {
+        const ListsIn whole{nullptr, 0, nullptr, 1};
+        const ListsIn &in = li ? *li : whole;
+        const WidePlan p = wide_plan(Q, in.P, N, K, k);
+        if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
+        ws_s = static_cast<float *>(workspace);                            // the workspace: scores, then positions
+        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
+        if (const int rc = launch_wide(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, in, ws_s, ws_i)) return rc;
+        S = p.parts;
+    }
+    hipLaunchKernelGGL(k_search_wide_merge, dim3((unsigned)Q), dim3(64 * kWideWaves), 0, st, ws_s, ws_i, S, k, out_score, out_index);
+    return launch_rc();
+}
+
 }  // namespace
 
 
@@ -2183,6 +2255,32 @@ int mcq_code_norms_based(const uint8_t *codes, long B, const void *prepared, int
 int mcq_code_rnorms_based(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, const float *base, long L,
                           const int32_t *assign, float *rnorms_out, void *stream) {
     return code_norms<true, true>(codes, B, prepared, N, K, D, rnorms_out, stream, base, L, assign);
+}
+
+// ---- rules 24-27 (include/mcq_wide.h): the search past 64 neighbours, 1 <= k <= 1,024
+size_t mcq_search_wide_workspace_bytes(long Q, long B, int N, int K, int k) {
+    if (Q <= 0 || B <= 0 || k < 1 || k > kWideMaxK || B > 0x7fffffffL || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
+    return 2 * wide_plan(Q, 1, N, K, k).ws_half;
+}
+
+int mcq_search_wide(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
+                    const uint64_t *mask, float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes,
+                    void *stream) {
+    return search_wide(tables, Q, codes, w, B, N, K, k, metric, mask, nullptr, out_score, out_index, workspace, workspace_bytes,
+                       stream);
+}
+
+size_t mcq_search_wide_lists_workspace_bytes(long Q, int P, int N, int K, int k) {
+    if (Q <= 0 || P <= 0 || P > kListMaxProbes || k < 1 || k > kWideMaxK || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
+    return 2 * wide_plan(Q, P, N, K, k).ws_half;
+}
+
+int mcq_search_wide_lists(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
+                          int metric, const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes, int P,
+                          const float *probe_bias, float *out_score, int64_t *out_index, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+    const ListsIn li{list_offsets, L, probes, P, probe_bias};
+    return search_wide(tables, Q, codes, w, B, N, K, k, metric, mask, &li, out_score, out_index, workspace, workspace_bytes, stream);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

@@ -22,6 +22,11 @@ cell.  The centroid's share of a score comes back as one value per (query, probe
     lims, dist, idx = quantizer.range_search_lists(queries, codes, list_offsets, probes, radius, norms=norms,
                                                    probe_bias=probe_bias(queries, centroids, probes))
 
+A shortlist for an exact re-ranker (recall@100, recall@1000): search_lists stops at k = 64, search_lists_wide goes to 1,024.
+
+    _, short = quantizer.search_lists_wide(queries, codes, list_offsets, probes, 1000, norms=norms)     # (Q, 1000), -1 = none
+    best = ((vectors[order][short.clamp(min=0)] - queries[:, None]) ** 2).sum(2).masked_fill(short < 0, float("inf")).topk(10, largest=False)
+
 Where the coarse centroids come from (k-means over a sample, a trained layer) is the caller's business."""
 import torch
 from torch import Tensor

@@ -1,5 +1,5 @@
 """The search over stored codes (not in the reference): top-k and range search, under a mask, list by list; include/mcq.h
-rules 1-20 and include/mcq_residual.h rules 21-23.  `SearchMixin` holds the methods `Quantizer` offers for it.  It has no state of its own: it uses num_codebooks,
+rules 1-20, include/mcq_residual.h rules 21-23 and include/mcq_wide.h rules 24-27 (top-k past 64 neighbours).  `SearchMixin` holds the methods `Quantizer` offers for it.  It has no state of its own: it uses num_codebooks,
 codebook_size, dim, _prepared and _check_domain of the class it is mixed into.
 
 Each rule of the layer is written once here: the device check (_on_device), the metric check (check_metric), the choice of
@@ -28,6 +28,12 @@ _ENTRIES = (
      "mcq_search_range_count", "mcq_search_range_fill", "mcq_search_range_workspace_bytes"),
 )
 _TABLES, _PACK_MASK = "mcq_search_tables", "mcq_search_pack_mask"
+# the top-k search past 64 neighbours (include/mcq_wide.h): (scan, its workspace query) over the whole store and list by list.
+# Either takes every optional operand, as a pointer that may be NULL.
+_WIDE = {False: ("mcq_search_wide", "mcq_search_wide_workspace_bytes"),
+         True: ("mcq_search_wide_lists", "mcq_search_wide_lists_workspace_bytes")}
+WIDE_MAX_K = 1024               # search_wide and search_lists_wide: the largest k
+NARROW_MAX_K = 64               # search and search_lists: the largest k
 
 
 def _entry(name: str):
@@ -276,9 +282,10 @@ class SearchMixin:
         return tables, flat, w, (q2d * q2d).sum(dim=1, keepdim=True), lists
 
     def _run(self, tables: Tensor, codes: Tensor, w: Tensor, metric: str, mask, lists, k: int = None, thr: Tensor = None,
-             max_results: int = None):
-        """The one call path into the library, behind _search_scan (k given) and _search_range (thr given), whose docstrings
-        say what comes back.  metric, mask and lists have passed _checked, and `lists` is what it returned."""
+             max_results: int = None, wide: bool = False):
+        """The one call path into the library, behind _search_scan (k given), _search_range (thr given) and
+        _search_wide_scan (k given, wide), whose docstrings say what comes back.  metric, mask and lists have passed
+        _checked, and `lists` is what it returned."""
         N, K = self.num_codebooks, self.codebook_size
         if metric == "ip":
             w = None
@@ -297,6 +304,8 @@ class SearchMixin:
         has = {"bias": lists is not None and len(lists) == 3, "lists": lists is not None, "mask": mask is not None,
                "metric": metric != "l2", None: True}
         first, scan, scan_bytes, count, fill, range_bytes = next(row for row in _ENTRIES if has[row[0]])
+        if wide:                                                  # (k given) the wide pair takes what the call has and NULL for the rest
+            first, (scan, scan_bytes) = "wide", _WIDE[has["lists"]]
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             # every tensor made here stays alive until the last launch of the call has been enqueued
@@ -312,8 +321,10 @@ class SearchMixin:
                          probes.data_ptr(), probes.shape[1])
                 if first == "bias":
                     args += (lists[2].data_ptr(),)
-            elif mask is not None:
-                args += (words.data_ptr(),)
+                elif wide:
+                    args += (lists[2].data_ptr() if has["bias"] else None,)
+            elif mask is not None or wide:
+                args += (None if words is None else words.data_ptr(),)
             size = (Q, B if lists is None else probes.shape[1], N, K) + (() if k is None else (k,))
             ws = torch.empty(_entry(range_bytes if k is None else scan_bytes)(*size), dtype=torch.uint8, device=dev)
             if k is not None:
@@ -387,11 +398,39 @@ class SearchMixin:
         distances and similarities to centroid + decode(code).  The value of an entry that names no list is not read."""
         return self._topk(queries, codes, k, norms, metric, rnorms, mask, (list_offsets, probes), probe_bias)
 
-    def _topk(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask, lists=None, bias=None):
-        """search() and search_lists(): `lists` is None or (list_offsets, probes), `bias` the probe_bias beside them"""
+    def _search_wide_scan(self, tables: Tensor, codes: Tensor, w: Tensor, k: int, metric: str = "l2", mask: Tensor = None,
+                          lists=None, bias: Tensor = None):
+        """_search_scan through the wide kernels (mcq_search_wide, and mcq_search_wide_lists with `lists`), 1 <= k <= 1,024:
+        the same arguments, the same result and, at k <= 64, the same bits.  It ALWAYS runs the wide kernels, at small k
+        too (the public calls hand k <= 64 to the older entries)."""
+        return self._run(tables, codes, w, metric, mask,
+                         _checked(metric, mask, codes.shape[0], lists, tables.shape[0], bias=bias), k=k, wide=True)
+
+    def search_wide(self, queries: Tensor, codes: Tensor, k: int, norms: Tensor = None, metric: str = "l2",
+                    rnorms: Tensor = None, mask: Tensor = None):
+        """search() for 1 <= k <= 1,024: a shortlist for an exact re-ranker, recall@100 or recall@1000 of an index.
+        Arguments, checks, returned values, clamping, the order among equal scores and the tail of a short store are
+        search()'s; the first 64 columns of a result are search(k=64)'s, bit for bit.  k <= 64 IS search(): the call is
+        forwarded; a larger k runs the wide kernels (mcq_search_wide), whose result list lives in LDS, not in a wave's
+        registers.  k > 1,024: McqError."""
+        return self._topk(queries, codes, k, norms, metric, rnorms, mask, wide=k > NARROW_MAX_K)
+
+    def search_lists_wide(self, queries: Tensor, codes: Tensor, list_offsets: Tensor, probes: Tensor, k: int,
+                          norms: Tensor = None, metric: str = "l2", rnorms: Tensor = None, mask: Tensor = None,
+                          probe_bias: Tensor = None):
+        """search_lists() for 1 <= k <= 1,024 (mcq_search_wide_lists): everything is search_lists()'s -- list_offsets, probes,
+        the mask, probe_bias for a store of residual codes, the returned values and the tail of a query with fewer than k
+        candidates.  k <= 64 IS search_lists(): the call is forwarded; a larger k runs the wide kernels.  k > 1,024: McqError."""
+        return self._topk(queries, codes, k, norms, metric, rnorms, mask, (list_offsets, probes), probe_bias,
+                          wide=k > NARROW_MAX_K)
+
+    def _topk(self, queries: Tensor, codes: Tensor, k: int, norms, metric: str, rnorms, mask, lists=None, bias=None,
+              wide: bool = False):
+        """search(), search_lists() and their wide twins: `lists` is None or (list_offsets, probes), `bias` the probe_bias
+        beside them, `wide` the entries of include/mcq_wide.h"""
         with torch.no_grad():
             tables, flat, w, qq, lists = self._operands(queries, codes, metric, norms, rnorms, mask, lists, bias=bias)
-            scores, indexes = self._run(tables, flat, w, metric, mask, lists, k=k)
+            scores, indexes = self._run(tables, flat, w, metric, mask, lists, k=k, wide=wide)
             values = _reported(scores, metric, qq)
         lead = queries.shape[:-1]
         return values.reshape(*lead, k), indexes.reshape(*lead, k)
