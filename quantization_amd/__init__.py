@@ -9,5 +9,6 @@ from .trainer import QuantizerTrainer  # noqa: F401
 from .prediction import JointCodebookLoss  # noqa: F401   (the consumer of the codes, quantization/__init__.py:4)
 from .hdf5_data import read_hdf5_data  # noqa: F401      (the data helper, quantization/__init__.py:3)
 from .ivf import build_lists, probe_lists, probe_bias, list_assign  # noqa: F401   (an inverted file over a store of codes: Quantizer.search_lists, range_search_lists)
+from .rerank import rerank  # noqa: F401   (the exact re-ranking of a shortlist: the step after search_wide / search_lists_wide)
 
-__all__ = ["Quantizer", "QuantizerTrainer", "JointCodebookLoss", "read_hdf5_data", "build_lists", "probe_lists", "probe_bias", "list_assign"]
+__all__ = ["Quantizer", "QuantizerTrainer", "JointCodebookLoss", "read_hdf5_data", "build_lists", "probe_lists", "probe_bias", "list_assign", "rerank"]

@@ -5,6 +5,7 @@
 #include "../../include/mcq_residual.h"
 #include "../../include/mcq_probe.h"
 #include "../../include/mcq_wide.h"
+#include "../../include/mcq_rerank.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
 #include "mcq_loss_kernels.h"
@@ -14,6 +15,7 @@
 #include "mcq_search_kernels.h"
 #include "mcq_range_kernels.h"
 #include "mcq_wide_kernels.h"
+#include "mcq_rerank_kernels.h"
 
 #include <cstdlib>
 #include <iterator>
@@ -1295,6 +1297,87 @@ int search_wide(const float *tables, long Q, const uint8_t *codes, const float *
     return launch_rc();
 }
 
+// ---- the exact re-ranking of a shortlist (mcq_rerank_kernels.h; rules 28-31 of include/mcq_rerank.h; mirrored by rerank_plan
+// of tests/rerank_grid.py): one query per workgroup and `parts` parts of its shortlist row, cut by count of its steps of
+// kRerankGroup entries -- as many as fill the chip once at small Q, no more than the row has steps, capped as wide_plan caps
+// them for the merge.  A function of the call's shape alone.
+struct RerankPlan {
+    int parts;
+    size_t lds, ws_half;
+};
+
+RerankPlan rerank_plan(long Q, long S, int D, int k) {
+    const long steps = (S + kRerankGroup - 1) / kRerankGroup;
+    const long cap = kWideMergeEntries / wide_half(k);
+    long parts = kRerankTargetBlocks / (Q > 0 ? Q : 1);
+    parts = parts > cap ? cap : parts;
+    parts = parts > steps ? steps : parts;
+    parts = parts < 1 ? 1 : parts;
+    return {(int)parts, (size_t)rerank_lds_bytes(D, k), align256((size_t)Q * parts * k * 4)};   // scores, then positions
+}
+
+// rule 28's limits, in its order; 0 inside the domain
+int rerank_domain(long Q, long S, long B, long Bs, int D, int k, int metric) {
+    constexpr long kLimit = 0x7fffffffL;                                   // sizes stay below 2^31 - 1
+    if (D > kRerankMaxD || k > kWideMaxK) return MCQ_EUNSUPPORTED;
+    if (D < 1 || k < 1 || Q < 0 || S < 0 || B < 0 || Bs < 0) return MCQ_EINVAL;
+    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
+    if (Q >= kLimit || S >= kLimit || B >= kLimit || Bs >= kLimit) return MCQ_EUNSUPPORTED;
+    return 0;
+}
+
+int launch_rerank(const RerankPlan &p, hipStream_t st, const void *queries, bool qhalf, int Q, const void *vectors, bool xhalf,
+                  long B, int D, const int64_t *shortlist, int S, const int64_t *row_of, long Bs, int k, int metric, int vec,
+                  float *ws_s, int *ws_i) {
+    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        return pick_bool(qhalf, [&](auto qh) {
+            return pick_bool(xhalf, [&](auto xh) {
+                constexpr int M = decltype(m)::value;
+                constexpr bool QH = qh, XH = xh;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_rerank<QH, XH, M>),
+                                                     rerank_lds_bytes(kRerankMaxD, kWideMaxK)))
+                    return rc;
+                hipLaunchKernelGGL((k_rerank<QH, XH, M>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kRerankWaves), p.lds, st,
+                                   queries, vectors, B, D, shortlist, S, row_of, Bs, k, p.parts, vec, ws_s, ws_i);
+                return launch_rc();
+            });
+        });
+    });
+}
+
+int rerank(const void *queries, bool qhalf, long Q, const void *vectors, bool xhalf, long B, int D, const int64_t *shortlist,
+           long S, const int64_t *row_of, long Bs, int k, int metric, float *out_score, int64_t *out_index, void *workspace,
+           size_t workspace_bytes, void *stream) {
+    if (!row_of) Bs = B;                                                   // (positions are rows)
+    if (const int rc = rerank_domain(Q, S, B, Bs, D, k, metric)) return rc;
+    if (Q > 0 && (!out_score || !out_index)) return MCQ_EINVAL;
+    if (Q == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws_s = nullptr;
+    int *ws_i = nullptr;
+    int parts = 0;                                                        // lists per query; 0 (no candidate anywhere): the fill
+    if (S > 0 && B > 0 && Bs > 0) {
+        if (!queries || !vectors || !shortlist || !workspace) return MCQ_EINVAL;
+        const size_t qel = qhalf ? 2 : 4, xel = xhalf ? 2 : 4;
+        if (reinterpret_cast<uintptr_t>(queries) % qel != 0 || reinterpret_cast<uintptr_t>(vectors) % xel != 0) return MCQ_EINVAL;
+        if (reinterpret_cast<uintptr_t>(shortlist) % 8 != 0 || reinterpret_cast<uintptr_t>(row_of) % 8 != 0) return MCQ_EINVAL;
+        const RerankPlan p = rerank_plan(Q, S, D, k);
+        if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
+        ws_s = static_cast<float *>(workspace);                            // the workspace: scores, then positions
+        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
+        // one vector load per lane and trip where every row starts on its boundary: 16 bytes of fp32, 8 of fp16
+        const int vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(vectors) % (4 * xel) == 0;
+        if (const int rc = launch_rerank(p, st, queries, qhalf, (int)Q, vectors, xhalf, B, D, shortlist, (int)S, row_of, Bs, k,
+                                         metric, vec, ws_s, ws_i))
+            return rc;
+        parts = p.parts;
+    }
+    hipLaunchKernelGGL(k_search_wide_merge, dim3((unsigned)Q), dim3(64 * kWideWaves), 0, st, ws_s, ws_i, parts, k, out_score,
+                       out_index);
+    return launch_rc();
+}
+
 }  // namespace
 
 
@@ -2281,6 +2364,19 @@ int mcq_search_wide_lists(const float *tables, long Q, const uint8_t *codes, con
                           size_t workspace_bytes, void *stream) {
     const ListsIn li{list_offsets, L, probes, P, probe_bias};
     return search_wide(tables, Q, codes, w, B, N, K, k, metric, mask, &li, out_score, out_index, workspace, workspace_bytes, stream);
+}
+
+// ---- rules 28-31 (include/mcq_rerank.h): the exact re-ranking of a shortlist
+size_t mcq_rerank_workspace_bytes(long Q, long S, int D, int k) {
+    if (Q <= 0 || S <= 0 || rerank_domain(Q, S, 0, 0, D, k, MCQ_SEARCH_L2) != 0) return 256;
+    return 2 * rerank_plan(Q, S, D, k).ws_half;
+}
+
+int mcq_rerank(const void *queries, int queries_half, long Q, const void *vectors, int vectors_half, long B, int D,
+               const int64_t *shortlist, long S, const int64_t *row_of, long Bs, int k, int metric, float *out_score,
+               int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
+    return rerank(queries, queries_half != 0, Q, vectors, vectors_half != 0, B, D, shortlist, S, row_of, Bs, k, metric, out_score,
+                  out_index, workspace, workspace_bytes, stream);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

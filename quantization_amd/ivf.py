@@ -25,7 +25,11 @@ cell.  The centroid's share of a score comes back as one value per (query, probe
 A shortlist for an exact re-ranker (recall@100, recall@1000): search_lists stops at k = 64, search_lists_wide goes to 1,024.
 
     _, short = quantizer.search_lists_wide(queries, codes, list_offsets, probes, 1000, norms=norms)     # (Q, 1000), -1 = none
-    best = ((vectors[order][short.clamp(min=0)] - queries[:, None]) ** 2).sum(2).masked_fill(short < 0, float("inf")).topk(10, largest=False)
+    dist, idx = quantization_amd.rerank(queries, vectors, short, 10, row_of=order)      # exact |q - x|^2 of the raw vectors
+    original = torch.where(idx >= 0, order[idx.clamp(min=0)], idx)
+
+rerank (quantization_amd/rerank.py, mcq_rerank) reads every candidate's raw row once; `vectors` stays in its original order,
+row_of = order maps a position of the store in list order to its row, and the -1 padding is skipped, not clamped.
 
 Where the coarse centroids come from (k-means over a sample, a trained layer) is the caller's business."""
 import torch
