@@ -300,7 +300,7 @@ int mcq_decode_backward_u8(const float *grad_out, const uint8_t *codes, long B, 
  * one table of N*K floats per query, one float per stored vector (formed once per store), N additions per (query, candidate).
  * One-byte codes only: K <= 256 (MCQ_EUNSUPPORTED past that, as at the trainer's entry points), 1 <= k <= 64 (k > 64:
  * MCQ_EUNSUPPORTED), B <= 2^31 - 1.  `prepared` of either flavour (the decode-only state is enough).
- * The contract (the tests restate rules 3 and 4 in numpy and compare bit for bit):
+ * The contract (the tests restate rules 1, 2, 3, 4 and 6 in numpy and compare bit for bit):
  *   1. tables[q][n*K + k] = -2 * sum_d q[d] * C[n][k][d]: one fp32 chain over d ascending (each product rounded, then added);
  *      fp16 queries widen to fp32 first.
  *   2. norms[b] = sum_d (sum_n C[n][code[b][n]][d])^2 in fp32: rows added n ascending, then 64 per-lane chains and the xor

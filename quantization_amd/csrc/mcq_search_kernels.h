@@ -2,7 +2,7 @@
 // answered from the codes themselves (no decode).  The quantizer is additive, x^_b = sum_n C[n][code[b][n]], so
 //     |q - x^_b|^2 = |q|^2 + sum_n T_q[n][code[b][n]] + t_b,     T_q[n][k] = -2 <q, C[n][k]>,     t_b = |x^_b|^2.
 //
-// Arithmetic contract (include/mcq.h, "search over stored codes"; the tests restate rules 3 and 4 in numpy):
+// Arithmetic contract (include/mcq.h, "search over stored codes"; the tests restate rules 1, 2, 3, 4 and 6 in numpy):
 //   1. k_search_tables: T[q][n*K + k] = -2 * (one fp32 chain over d ascending, accumulator starting at +0, each product rounded,
 //      then added: -ffp-contract=off).  Chain length = the padded dim (the pad columns of `prepared` are zero).
 //   2. k_code_norms: per lane l and float4 group g = l, l + 64, ...: v = ((C[0][c_0] + C[1][c_1]) + ...) per component (N - 1

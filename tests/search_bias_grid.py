@@ -21,6 +21,7 @@ import numpy as np
 import search_lists_grid as lg
 import search_metric_grid as mg
 import search_selection_grid as sel
+import search_tables_grid as tg
 
 ME = "tests/search_bias_grid.py"
 METRICS = lg.METRICS
@@ -116,32 +117,18 @@ def rows_with_two_lists(list_offsets, probes):
 # ------------------------------------------------------------------ rule 22 in numpy
 def restate_norms_based(C, codes, base, assign, D):
     """C (N, K, Dp) float32 -- the PADDED rows of `prepared` --, codes (B, N), base (L, D) float32, assign (B,) integer ->
-    float32 (B,).  base None: rule 2 itself."""
-    N, K, Dp = C.shape
+    float32 (B,).  base None: rule 2 itself, restate_norms of tests/search_tables_grid.py, whose row sums and lane chains these
+    are: the base row goes in between them."""
+    if base is None:
+        return tg.restate_norms(C, codes)
     B = codes.shape[0]
-    v = C[0][codes[:, 0].astype(np.int64) & (K - 1)].astype(np.float32)
-    for n in range(1, N):
-        v = (v + C[n][codes[:, n].astype(np.int64) & (K - 1)]).astype(np.float32)
-    if base is not None:
-        ok = (assign >= 0) & (assign < len(base))
-        add = np.zeros((B, D), dtype=np.float32)
-        add[ok] = base[assign[ok]]
-        head = (v[:, :D] + add).astype(np.float32)
-        v[:, :D] = np.where(ok[:, None], head, v[:, :D])             # (no row: nothing is added, not even a zero)
-    sq = (v * v).astype(np.float32)
-    groups = Dp // 4
-    part = np.zeros((B, 64), dtype=np.float32)
-    lanes = np.arange(64)
-    for g0 in range(0, groups, 64):                                  # lane l: the float4 groups l, l + 64, ... in turn
-        g = g0 + lanes
-        live = g < groups
-        for c in range(4):
-            term = np.zeros((B, 64), dtype=np.float32)
-            term[:, live] = sq[:, 4 * g[live] + c]
-            part = (part + term).astype(np.float32)
-    for m in (32, 16, 8, 4, 2, 1):                                   # the xor butterfly: every lane ends with the same sum
-        part = (part + part[:, lanes ^ m]).astype(np.float32)
-    return part[:, 0].copy()
+    v = tg.row_sums(C, codes)
+    ok = (assign >= 0) & (assign < len(base))
+    add = np.zeros((B, D), dtype=np.float32)
+    add[ok] = base[assign[ok]]
+    head = (v[:, :D] + add).astype(np.float32)
+    v[:, :D] = np.where(ok[:, None], head, v[:, :D])                 # (no row: nothing is added, not even a zero)
+    return tg.lane_sums(v)
 
 
 # ------------------------------------------------------------------ the launchers' cells with a bias

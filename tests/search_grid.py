@@ -182,4 +182,7 @@ CASES = [
          partial=True),
     Case("stored_queries_clamp", 8, 16, 24, 17, 1000, 10, queries="stored", packed=True, tiles=True, sliced=True, partial=True),
     Case("n8_k256_q1_k1", 8, 256, 512, 1, 100_003, 1, sliced=True, partial=True),
+    # dims whose padded dim is no multiple of kTabChunk (40 -> 48, 1000 -> 1008): the last chunk of k_search_tables is half a one
+    Case("n8_k256_d40", 8, 256, 40, 17, 4099, 10, state="decode_only", codes="random", tiles=True, sliced=True, partial=True),
+    Case("n2_k64_d1000", 2, 64, 1000, 5, 300, 10, partial=True),
 ]

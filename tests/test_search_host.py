@@ -139,6 +139,7 @@ def test_gpu_cases_reach_what_they_claim():
     # ties decide whole lists both where arrival order is position order and where it is not
     assert {cs.strided for cs in sg.CASES if cs.codes == "dup16" and cs.k == 64} == {False, True}
     assert {cs.N for cs in sg.CASES} >= {1, 2, 8, 16, 64} and {cs.K for cs in sg.CASES} == {16, 64, 256}
-    assert {cs.D for cs in sg.CASES} == {24, 512} and {cs.Q for cs in sg.CASES} == {1, 17, 200}
+    assert {cs.D for cs in sg.CASES} == {24, 40, 512, 1000} and {cs.Q for cs in sg.CASES} == {1, 5, 17, 200}
+    assert {sg.padded(cs.D) % c["kTabChunk"] for cs in sg.CASES} == {0, 16}      # whole chunks, and half a last one
     assert {cs.k for cs in sg.CASES} == {1, 10, 64}
     assert {cs.B for cs in sg.CASES} >= {1, 63, 64, 65, 9, 100_003, 1_048_576 + 17}
