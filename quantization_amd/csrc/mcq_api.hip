@@ -255,6 +255,18 @@ inline int launch_rc() {
 }
 inline int counted_launch_rc() { MCQ_LAUNCH_CHECK(); return 0; }
 
+// A kernel that spends `threads_per_row` threads on a row is launched over B rows in pieces of at most kPieceRows * 64 /
+// threads_per_row rows, 2^31 threads each: launch(first row, rows) -> rc.  A grid of 2^32 threads or more is not refused by
+// the runtime here; it returns hipSuccess and runs the thread count modulo 2^32, so the rows past it keep what the output held
+// ("Stores past 2^26 rows").  B within one piece is exactly one launch with the geometry it always had.
+template <typename F>
+int launch_in_pieces(long B, int threads_per_row, F &&launch) {
+    const long piece = (long)kPieceRows * 64 / (threads_per_row > 64 ? threads_per_row : 64);
+    for (long at = 0; at < B; at += piece)
+        if (const int rc = launch(at, B - at < piece ? B - at : piece)) return rc;
+    return 0;
+}
+
 // Kernel selection: a runtime value becomes a template argument ("Kernel selection").  pick<Vs...>(v, f) calls
 // f(std::integral_constant<int, V>{}) for the V that equals v and returns what f returns; no V equals v: MCQ_EUNSUPPORTED.  The
 // list IS the set of instantiations: f is stamped for every V, so a case belongs in it only if the host can reach it.
@@ -1083,9 +1095,12 @@ int code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K,
     if (BASED && (!base || !assign)) return MCQ_EINVAL;
     if (BASED && (reinterpret_cast<uintptr_t>(base) % 4 != 0 || reinterpret_cast<uintptr_t>(assign) % 4 != 0)) return MCQ_EINVAL;
     const Prepared P = prepared_view(prepared, N, K, D);
-    hipLaunchKernelGGL((k_code_norms<RNORM, BASED>), dim3((unsigned)((B + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
-                       static_cast<hipStream_t>(stream), codes, B, P.C, N, K, round_up16(D), out, base, L, D, assign);
-    return launch_rc();
+    return launch_in_pieces(B, 64, [&](long at, long rows) {     // one wave per stored vector
+        hipLaunchKernelGGL((k_code_norms<RNORM, BASED>), dim3((unsigned)((rows + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
+                           static_cast<hipStream_t>(stream), codes + at * N, rows, P.C, N, K, round_up16(D), out + at, base, L, D,
+                           BASED ? assign + at : assign);
+        return launch_rc();
+    });
 }
 
 // the launch arithmetic of the scan and of the sweeps (mirrored by tile_plan of tests/search_grid.py): a tile of qt queries per
@@ -1601,16 +1616,28 @@ int decode_sliced_lpv(int Dp) {
 bool decode_sliced_applies(const DecodeArgs &a) {
     return a.sliced_ok && a.rep == 1 && a.B >= 4096 && a.K >= 32 && decode_sliced_lpv(a.Dp) <= 64;
 }
+// rows [at, at + rows) of a call as a call of their own: the per-vector kernels go through launch_in_pieces
+inline DecodeArgs decode_piece(const DecodeArgs &a, long at, long rows) {
+    DecodeArgs p = a;
+    p.codes = static_cast<const char *>(a.codes) + at * a.codes_per_row * a.code_bytes;
+    p.out = a.out + at * a.D;
+    p.B = rows;
+    return p;
+}
+
 template <typename T>
-int launch_decode_sliced(const DecodeArgs &a) {
-    const int lpv = decode_sliced_lpv(a.Dp), vpw = 64 / lpv;
-    const dim3 g((unsigned)(((a.B + 4 * vpw - 1) / (4 * vpw)) * 8));
-    return pick<4, 8, 16>(a.N <= 4 ? 4 : (a.N <= 8 ? 8 : 16), [&](auto ch) {      // codes of a vector per load
-        return pick<4, 8, 16, 32, 64>(lpv, [&](auto ll) {
-            constexpr int CHH = decltype(ch)::value, LL = decltype(ll)::value;
-            hipLaunchKernelGGL((k_decode_sliced<T, CHH, LL>), g, dim3(256), 0, a.st, static_cast<const T *>(a.codes), a.B, a.C, a.N, a.K, a.D,
-                               a.Dp, a.out);
-            return launch_rc();
+int launch_decode_sliced(const DecodeArgs &whole) {
+    const int lpv = decode_sliced_lpv(whole.Dp), vpw = 64 / lpv;
+    return launch_in_pieces(whole.B, 8 * lpv, [&](long at, long rows) {           // 8 slices x lpv lanes per vector
+        const DecodeArgs a = decode_piece(whole, at, rows);
+        const dim3 g((unsigned)(((a.B + 4 * vpw - 1) / (4 * vpw)) * 8));
+        return pick<4, 8, 16>(a.N <= 4 ? 4 : (a.N <= 8 ? 8 : 16), [&](auto ch) {      // codes of a vector per load
+            return pick<4, 8, 16, 32, 64>(lpv, [&](auto ll) {
+                constexpr int CHH = decltype(ch)::value, LL = decltype(ll)::value;
+                hipLaunchKernelGGL((k_decode_sliced<T, CHH, LL>), g, dim3(256), 0, a.st, static_cast<const T *>(a.codes), a.B, a.C, a.N, a.K,
+                                   a.D, a.Dp, a.out);
+                return launch_rc();
+            });
         });
     });
 }
@@ -1621,20 +1648,26 @@ inline int decode_reg_j(const DecodeArgs &a) { return (a.Dp / 4 + 63) / 64; }
 bool decode_reg_applies(const DecodeArgs &a) {
     return a.code_bytes == 1 && a.rep == 1 && in_pairs(kDecRegShapes, a.N, decode_reg_j(a));
 }
-int launch_decode_reg(const DecodeArgs &a) {
-    return pick_pair<kDecRegShapes>(a.N, decode_reg_j(a), [&](auto nn, auto jj) {
+int launch_decode_reg(const DecodeArgs &whole) {
+    return pick_pair<kDecRegShapes>(whole.N, decode_reg_j(whole), [&](auto nn, auto jj) {
         constexpr int NN = nn, JJ = jj;
-        hipLaunchKernelGGL((k_decode_reg<NN, JJ>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, a.st,
-                           static_cast<const uint8_t *>(a.codes), a.B, a.C, a.K, a.D, a.Dp, a.out);
-        return launch_rc();
+        return launch_in_pieces(whole.B, 64, [&](long at, long rows) {            // one wave per vector
+            const DecodeArgs a = decode_piece(whole, at, rows);
+            hipLaunchKernelGGL((k_decode_reg<NN, JJ>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, a.st,
+                               static_cast<const uint8_t *>(a.codes), a.B, a.C, a.K, a.D, a.Dp, a.out);
+            return launch_rc();
+        });
     });
 }
 
 template <typename T>
-int launch_decode_generic(const DecodeArgs &a) {
-    hipLaunchKernelGGL((k_decode<T>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, a.st, static_cast<const T *>(a.codes),
-                       a.codes_per_row, a.B, a.C, a.N, a.K, a.D, a.Dp, a.out);
-    return launch_rc();
+int launch_decode_generic(const DecodeArgs &whole) {
+    return launch_in_pieces(whole.B, 64, [&](long at, long rows) {                // one wave per vector
+        const DecodeArgs a = decode_piece(whole, at, rows);
+        hipLaunchKernelGGL((k_decode<T>), dim3((unsigned)((a.B + 3) / 4)), dim3(256), 0, a.st, static_cast<const T *>(a.codes),
+                           a.codes_per_row, a.B, a.C, a.N, a.K, a.D, a.Dp, a.out);
+        return launch_rc();
+    });
 }
 }  // namespace
 

@@ -40,6 +40,11 @@ constexpr int kTabRows = 64;              // k_search_tables: table rows (n*K + 
 constexpr int kTabQueries = 16;           //                  queries per workgroup
 constexpr int kTabChunk = 32;             //                  features staged per step
 constexpr int kNormWaves = 4;             // k_code_norms: stored vectors per workgroup, one wave each
+constexpr int kPieceRows = 32 * 1024 * 1024;   // rows per launch of the kernels that spend a wave (64 threads) or more on a row
+                                          // (k_code_norms, the per-vector decodes): 2^31 threads.  A launch of 2^32 threads or
+                                          // more is not rejected by the runtime on gfx950: it returns 0 and runs the thread
+                                          // count modulo 2^32 (launch_in_pieces of mcq_api.hip; DESIGN.md section 4,
+                                          // "Stores past 2^26 rows")
 constexpr int kScanWaves = 8;             // k_search_scan: waves per workgroup (512 threads)
 constexpr int kScanQTMax = 16;            //                queries per tile at most
 constexpr int kScanTableLds = 128 * 1024; //                bytes of LDS the tables of a tile may take (160 KiB per CU)

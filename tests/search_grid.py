@@ -15,7 +15,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "quantization_amd", "csrc", "mcq_search_kernels.h")
 
-NAMES = ("kTabRows", "kTabQueries", "kTabChunk", "kNormWaves", "kScanWaves", "kScanQTMax", "kScanTableLds",
+NAMES = ("kTabRows", "kTabQueries", "kTabChunk", "kNormWaves", "kPieceRows", "kScanWaves", "kScanQTMax", "kScanTableLds",
          "kScanTargetBlocks", "kScanMaxSlices", "kNoIndex")
 
 
