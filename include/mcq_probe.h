@@ -62,8 +62,8 @@ int mcq_test_pass_layout(long B, int N, int K, int D, size_t *out, int cap);
 
 /* ONE refinement pass of B vectors as ONE chunk, from caller-supplied codes, through the launchers of the encode's own pass loop
  * (the chunk start with imported codes: frames to limb planes, k_import_indexes, the x.C product; then E / R, stage 0 and the
- * combines as separate launches -- never the LDS-resident pass of 8 x 16 and 16 x 16, no fixed-point skipping of its own, E / R
- * of a next pass not formed).  What the pass leaves in `workspace` is read by mcq_test_pass_layout(B, ...).
+ * combines as separate launches -- never the LDS-resident pass of 8 x 16 and 16 x 16, which mcq_test_pass16 below runs; no
+ * fixed-point skipping of its own, E / R of a next pass not formed).  What the pass leaves in `workspace` is read by mcq_test_pass_layout(B, ...).
  *   x            fp32 [B][D], the frames (row r)
  *   idx_in       int64 [B][N], the current codes of the SLOTS, every one in [0, K)
  *   idx_out      int64 [B][N]: the new codes of slot b go to row b, or to row map[b]; they are also left in the workspace's idx,
@@ -82,6 +82,46 @@ int mcq_test_pass_layout(long B, int N, int K, int D, size_t *out, int cap);
 int mcq_test_pass(const float *x, long B, const void *prepared, int N, int K, int D, const int64_t *idx_in, int64_t *idx_out,
                   const int *nact /* may be NULL */, const int *map /* may be NULL */, unsigned flags, void *workspace,
                   size_t workspace_bytes, void *stream);
+
+
+/* One record of the LDS-resident pass of 8 x 16 and 16 x 16 codebooks (k_tf_pass16<N>, which mcq_test_pass never takes; its probe
+ * instantiation k_tf_pass16_probe<N> is the same body with the records added).  After the winner's walk of pass p of vector b, and
+ * before the wave leaves a vector at its fixed point, the wave writes record b * iters + p.  A record is the list part of the
+ * wave's LDS scratch as it lies, then what the pass held in registers (host only; the constants the kernel itself uses).  out[i],
+ * i < min(cap, 25), receive
+ *   out[2 a], out[2 a + 1]   byte offset in the record and byte size of array a; an array N codebooks do not have reports 0, 0
+ *      a = 0 ent  uint8[N][8]            the level-0 lists: codebook entries
+ *          1 pos1 uint8[N/2][8][2]   2 pos2 uint8[N/4][16][2]   3 pos3 uint8[2][16][2] (N = 16 only)   positions in the halves' lists
+ *          4 S0 float[N][8]   5 S1 float[N/2][8]   6 S2 float[N/4][16]   7 S3 float[2][16] (N = 16 only)   the candidates' scores
+ *          8 E  float         9 R  float[N]      E and R[n] of the pass
+ *          10 idx uint8[N]    the codes the pass leaves
+ *          11 mark uint32     0x36315021: the record was written
+ *   out[24]                  the bytes of one record (the same for both N; a multiple of 4)
+ * The bytes of a record outside these arrays hold whatever the scratch held (with N = 8, scratch the kernel never writes) or are
+ * not written.  Returns 25 (MCQ_TEST_PASS16_LAYOUT_VALUES).  N other than 8 or 16: MCQ_EUNSUPPORTED; out == NULL or cap < 0:
+ * MCQ_EINVAL.                                                                                                                   */
+#define MCQ_TEST_PASS16_LAYOUT_VALUES 25
+#define MCQ_TEST_PASS16_WRITTEN 0x36315021u
+int mcq_test_pass16_layout(int N, size_t *out, int cap);
+
+/* `iters` refinement passes of B vectors of N x 16 codebooks, N = 8 or 16, as ONE chunk, from caller-supplied codes, through the
+ * LDS-resident pass: the encode's own chunk start with imported codes (as mcq_test_pass), then the launcher the encode calls
+ * for these shapes -- one launch for all passes, a wave leaves a vector after the first pass that returns its input.
+ *   x, idx_in    as mcq_test_pass
+ *   idx_out      int64 [B][N]: the codes after the last pass a vector ran; they are also left in the workspace's idx
+ *   dump         NULL: the instantiation the encode itself launches (k_tf_pass16<N>).  Else 4-byte aligned device memory of at
+ *                least B * iters records: the probe instantiation, which writes record b * iters + p for every pass p vector
+ *                b runs and nothing of the records of later passes
+ *   max_workgroups  0: the launcher's own grid; positive: at most that many workgroups of eight waves (the kernel strides by
+ *                its grid, so with 1 every wave carries B / 8 vectors one after the other through the same scratch)
+ *   workspace    as mcq_test_pass
+ * mcq_last_encode_launches() counts the launches of the call.  Checks in this order: the domain of (N, 16, D); N other than 8 or
+ * 16: MCQ_EUNSUPPORTED; B < 0, iters outside 1 .. 60 or max_workgroups < 0: MCQ_EINVAL; B == 0 returns 0 and looks at nothing;
+ * NULL x / prepared / idx_in / idx_out / workspace or a misaligned workspace or dump: MCQ_EINVAL; a workspace that does not hold
+ * B as one chunk, then a dump of fewer than B * iters records: MCQ_EWORKSPACE.                                                  */
+int mcq_test_pass16(const float *x, long B, const void *prepared, int N, int D, int iters, const int64_t *idx_in, int64_t *idx_out,
+                    void *dump /* may be NULL */, size_t dump_bytes, int max_workgroups, void *workspace, size_t workspace_bytes,
+                    void *stream);
 
 #ifdef __cplusplus
 }

@@ -104,13 +104,15 @@ RESIDUAL_SIGNATURES = {
 RESIDUAL_SYMBOLS = tuple(RESIDUAL_SIGNATURES)
 
 # include/mcq_probe.h, the companion header of the probes the tests run single steps of the encode through, in the same form
-# (tests/test_er_probe_host.py and tests/test_pass_lists_host.py parse that header and compare)
+# (tests/test_er_probe_host.py, tests/test_pass_lists_host.py and tests/test_pass16_lists_host.py parse that header and compare)
 PROBE_SIGNATURES = {
     "mcq_test_er_workspace_bytes": _sig("z", "li"),
     "mcq_test_er": _sig("i", "piiippplppipppzp"),
     "mcq_test_xc_xx": _sig("i", "plpiiipppzpu"),
     "mcq_test_pass_layout": _sig("i", "liiipi"),
     "mcq_test_pass": _sig("i", "plpiiippppupzp"),
+    "mcq_test_pass16_layout": _sig("i", "ipi"),
+    "mcq_test_pass16": _sig("i", "plpiiipppzipzp"),
 }
 PROBE_SYMBOLS = tuple(PROBE_SIGNATURES)
 

@@ -790,11 +790,19 @@ int launch_chunk_start(const EncodeCall &c, const WorkspaceT<CT> &w, const float
 // persistent workgroups that hold the Gram matrix in LDS (mcq_pass16_kernels.h); a wave leaves a vector at its fixed point
 // by itself, without compaction.  Not under the profiler, whose categories are the separate launches.  The kernel writes the
 // caller's arrays itself where codes are not packed (out.pack == 1); packed nibbles leave through k_finalize, from w.idx
-int launch_pass16(const EncodeCall &c, const WorkspaceT<uint8_t> &w, long Bc, const ChunkOut &out) {
+// (mcq_test_pass16 of include/mcq_probe.h only: dump -- the probe instantiation, which also leaves a record per vector and pass
+// there; max_wgs > 0 -- fewer workgroups than the launcher's own cap, the kernel strides by its grid)
+int launch_pass16(const EncodeCall &c, const WorkspaceT<uint8_t> &w, long Bc, const ChunkOut &out, uint8_t *dump = nullptr,
+                  int max_wgs = 0) {
     // the first pass16 call on a device opts BOTH shapes in: the other shape's first call may come inside a captured stream
     static bool allowed16[64] = {}, allowed8[64] = {};
     int rc = allow_dynamic_lds(allowed16, reinterpret_cast<const void *>(&k_tf_pass16<16>), p16_lds_bytes<16>());
     if (rc == 0) rc = allow_dynamic_lds(allowed8, reinterpret_cast<const void *>(&k_tf_pass16<8>), p16_lds_bytes<8>());
+    if (rc == 0 && dump) {
+        static bool probe16[64] = {}, probe8[64] = {};
+        rc = allow_dynamic_lds(probe16, reinterpret_cast<const void *>(&k_tf_pass16_probe<16>), p16_lds_bytes<16>());
+        if (rc == 0) rc = allow_dynamic_lds(probe8, reinterpret_cast<const void *>(&k_tf_pass16_probe<8>), p16_lds_bytes<8>());
+    }
     if (rc) return rc;
     Pass16Args a;
     a.G = c.P.G; a.XC = w.XC; a.xx = w.xx; a.Q = c.P.Q; a.idx = w.idx; a.B = Bc; a.iters = c.iters;
@@ -803,7 +811,10 @@ int launch_pass16(const EncodeCall &c, const WorkspaceT<uint8_t> &w, long Bc, co
     const long wgs = (Bc + kP16Waves - 1) / kP16Waves;
     return pick<16, 8>(c.N, [&](auto nn) {   // one workgroup per CU (157,696 B of LDS), two with eight codebooks (62,464 B)
         constexpr int NN = nn, cap = NN == 16 ? 256 : 512;
-        hipLaunchKernelGGL(k_tf_pass16<NN>, dim3((unsigned)(wgs < cap ? wgs : cap)), dim3(64 * kP16Waves), p16_lds_bytes<NN>(), c.st, a);
+        const long lim = (max_wgs > 0 && max_wgs < cap) ? max_wgs : cap;
+        const dim3 grid((unsigned)(wgs < lim ? wgs : lim)), block(64 * kP16Waves);
+        if (dump) hipLaunchKernelGGL(k_tf_pass16_probe<NN>, grid, block, p16_lds_bytes<NN>(), c.st, a, dump);
+        else hipLaunchKernelGGL(k_tf_pass16<NN>, grid, block, p16_lds_bytes<NN>(), c.st, a);
         return counted_launch_rc();
     });
 }
@@ -1962,6 +1973,44 @@ int mcq_test_pass(const float *x, long B, const void *prepared, int N, int K, in
     const bool capped = (flags & MCQ_TEST_PASS_CAPPED) != 0;
     if (K > 256) return test_pass<uint16_t>(c, x, B, idx_in, idx_out, nact, map, capped, workspace);
     return test_pass<uint8_t>(c, x, B, idx_in, idx_out, nact, map, capped, workspace);
+}
+
+// include/mcq_probe.h: where the arrays of one record of k_tf_pass16_probe lie (the constants of mcq_pass16_kernels.h)
+int mcq_test_pass16_layout(int N, size_t *out, int cap) {
+    if (N != 8 && N != 16) return MCQ_EUNSUPPORTED;
+    if (!out || cap < 0) return MCQ_EINVAL;
+    constexpr int n = 2 * kP16RecArrays + 1;
+    static_assert(n == MCQ_TEST_PASS16_LAYOUT_VALUES && kP16RecWritten == MCQ_TEST_PASS16_WRITTEN, "include/mcq_probe.h");
+    size_t v[n];
+    for (int i = 0; i < kP16RecArrays; ++i) {
+        const size_t bytes = (size_t)p16_rec_bytes(N, i);
+        v[2 * i] = bytes ? (size_t)kP16RecOff[i] : 0;
+        v[2 * i + 1] = bytes;
+    }
+    v[n - 1] = kP16Rec;
+    for (int i = 0; i < n && i < cap; ++i) out[i] = v[i];
+    return n;
+}
+
+// include/mcq_probe.h: every pass of B vectors of 8 x 16 or 16 x 16 as one chunk from imported codes -- the chunk start, then
+// launch_pass16 as the encode calls it, with the record dump and the grid cap the caller asks for
+int mcq_test_pass16(const float *x, long B, const void *prepared, int N, int D, int iters, const int64_t *idx_in, int64_t *idx_out,
+                    void *dump, size_t dump_bytes, int max_workgroups, void *workspace, size_t workspace_bytes, void *stream) {
+    constexpr int K = 16;
+    g_last_launches = 0;
+    if (!domain_ok(N, K, D)) return domain_err(N, K, D);
+    if (N != 8 && N != 16) return MCQ_EUNSUPPORTED;
+    if (B < 0 || iters < 1 || iters > 60 || max_workgroups < 0) return MCQ_EINVAL;
+    if (B == 0) return 0;
+    if (!x || !prepared || !idx_in || !idx_out || !workspace) return MCQ_EINVAL;
+    if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0 || reinterpret_cast<uintptr_t>(dump) % 4 != 0) return MCQ_EINVAL;
+    const size_t per = workspace_per_vector(N, K, D), slack = workspace_slack(D);
+    if (workspace_bytes < slack + per || (long)((workspace_bytes - slack) / per) < B) return MCQ_EWORKSPACE;     // the encode's chunk rule
+    if (dump && dump_bytes / kP16Rec / (size_t)iters < (size_t)B) return MCQ_EWORKSPACE;
+    const EncodeCall c{prepared_view(prepared, N, K, D), 1.0f, N, K, D, iters, 0u, static_cast<hipStream_t>(stream), nullptr};
+    const WorkspaceT<uint8_t> w = carve<uint8_t>(workspace, B, N, K, D);
+    if (const int rc = launch_chunk_start<uint8_t>(c, w, x, B, idx_in, nullptr)) return rc;
+    return launch_pass16(c, w, B, ChunkOut{nullptr, idx_out, nullptr, 1}, static_cast<uint8_t *>(dump), max_workgroups);
 }
 
 // ------------------------------------------------------------------ trainer pieces

@@ -11,7 +11,8 @@ import pytest
 import search_selection_grid as sel
 
 NEW = ("mcq_test_er_workspace_bytes", "mcq_test_er", "mcq_test_xc_xx",
-       "mcq_test_pass_layout", "mcq_test_pass")      # (the last two: tests/test_pass_lists_host.py checks their arguments)
+       "mcq_test_pass_layout", "mcq_test_pass",      # (these two: tests/test_pass_lists_host.py checks their arguments,
+       "mcq_test_pass16_layout", "mcq_test_pass16")  # these two: tests/test_pass16_lists_host.py)
 PROBE_HDR = sel.API.replace("quantization_amd/csrc/mcq_api.hip", "include/mcq_probe.h")
 
 

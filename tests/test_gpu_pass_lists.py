@@ -118,14 +118,14 @@ def arrays_of(raw, lay, B, N):
     return out
 
 
-def assert_nothing_else_written(raw, lay, what):
+def assert_nothing_else_written(raw, lay, what, unused=UNUSED):
     end = 0
     for name in pl.CARVE_ORDER:
         off, nbytes = lay["at"][name]
         if nbytes == 0:
             continue
         assert (raw[end:off] == FILL).all(), (what, "before", name)
-        if name in UNUSED:
+        if name in unused:
             assert (raw[off:off + nbytes] == FILL).all(), (what, name)
         end = off + nbytes
     assert end <= lay["total"] <= raw.size and (raw[end:] == FILL).all(), (what, "past the last array")
