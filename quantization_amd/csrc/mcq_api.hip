@@ -6,6 +6,7 @@
 #include "../../include/mcq_probe.h"
 #include "../../include/mcq_wide.h"
 #include "../../include/mcq_rerank.h"
+#include "../../include/mcq_code16.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
 #include "mcq_loss_kernels.h"
@@ -1051,6 +1052,11 @@ int search_domain(int N, int K, int D) {
     return K > 256 ? MCQ_EUNSUPPORTED : 0;
 }
 
+// two-byte codes (include/mcq_code16.h rule 33): every codebook size of the library; N * K <= kMaxRows is the 64 KiB of table
+// the list kernels carry beside the probe ranges
+int code16_domain(int N, int K, int D) { return domain_ok(N, K, D) ? 0 : domain_err(N, K, D); }
+static_assert(wide_lds_bytes(kMaxRows, kListMaxProbes, kWideMaxK) <= 160 * 1024, "the table of a two-byte call fits the CU");
+
 // the probe set of a call that goes list by list (rules 13-20); a call over the whole store has none and passes NULL
 struct ListsIn {
     const int64_t *list_offsets;
@@ -1066,11 +1072,12 @@ struct ListsIn {
 // knows which of them an empty call still writes).  *empty: the call has no candidate anywhere (Q or B is 0; with lists, L or
 // P) -- it reads no input, so none is looked at.  mask: NULL where the call has none (rule 12); one that is there is read as
 // 8-byte words.  li: the limits of rule 16 come between B's and the outputs, its pointers and alignments with the others
-// (a bias, rule 23, is optional: only its alignment is looked at, last).
-int search_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
-                 const uint64_t *mask, const ListsIn *li, bool outs_ok, const void *workspace, bool *empty) {
+// (a bias, rule 23, is optional: only its alignment is looked at, last).  code_bytes: 1, or 2 for the entries of
+// include/mcq_code16.h, which differ in the domain and in the alignment of the codes (rules 33 and 34) and in nothing else.
+int search_check(const float *tables, long Q, const void *codes, const float *w, long B, int N, int K, int k, int metric,
+                 const uint64_t *mask, const ListsIn *li, bool outs_ok, const void *workspace, bool *empty, int code_bytes = 1) {
     *empty = false;
-    if (const int rc = search_domain(N, K, 1)) return rc;
+    if (const int rc = code_bytes == 2 ? code16_domain(N, K, 1) : search_domain(N, K, 1)) return rc;
     if (k > 64) return MCQ_EUNSUPPORTED;
     if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
     if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
@@ -1084,7 +1091,7 @@ int search_check(const float *tables, long Q, const uint8_t *codes, const float 
     }
     if (!tables || !codes || !workspace || (li && (!li->list_offsets || !li->probes))) return MCQ_EINVAL;
     if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;                  // (the inner product never reads w)
-    const int need = N >= 16 ? 16 : N;                                    // a candidate's codes are loaded as one vector
+    const int need = N * code_bytes >= 16 ? 16 : N * code_bytes;          // a candidate's codes are loaded as one vector
     if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
     if (reinterpret_cast<uintptr_t>(mask) % 8 != 0) return MCQ_EINVAL;
     if (li && (reinterpret_cast<uintptr_t>(li->list_offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(li->probes) % 4 != 0)) return MCQ_EINVAL;
@@ -1093,11 +1100,11 @@ int search_check(const float *tables, long Q, const uint8_t *codes, const float 
 }
 
 // mcq_code_norms (t[b]) and mcq_code_rnorms (RNORM: r[b]); BASED: mcq_code_norms_based and mcq_code_rnorms_based, rule 22, the
-// norms of base[assign[b]] + decode(codes[b]) -- its checks of L, base and assign run only then
-template <bool RNORM, bool BASED = false>
-int code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *out, void *stream,
+// norms of base[assign[b]] + decode(codes[b]) -- its checks of L, base and assign run only then.  T = uint16_t: mcq_code_norms_u16
+template <bool RNORM, bool BASED = false, typename T = uint8_t>
+int code_norms(const T *codes, long B, const void *prepared, int N, int K, int D, float *out, void *stream,
                const float *base = nullptr, long L = 0, const int32_t *assign = nullptr) {
-    if (const int rc = search_domain(N, K, D)) return rc;
+    if (const int rc = sizeof(T) == 2 ? code16_domain(N, K, D) : search_domain(N, K, D)) return rc;
     if (B < 0) return MCQ_EINVAL;
     if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
     if (BASED && L < 0) return MCQ_EINVAL;
@@ -1105,9 +1112,10 @@ int code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K,
     if (!codes || !prepared || !out) return MCQ_EINVAL;
     if (BASED && (!base || !assign)) return MCQ_EINVAL;
     if (BASED && (reinterpret_cast<uintptr_t>(base) % 4 != 0 || reinterpret_cast<uintptr_t>(assign) % 4 != 0)) return MCQ_EINVAL;
+    if (reinterpret_cast<uintptr_t>(codes) % sizeof(T) != 0) return MCQ_EINVAL;
     const Prepared P = prepared_view(prepared, N, K, D);
     return launch_in_pieces(B, 64, [&](long at, long rows) {     // one wave per stored vector
-        hipLaunchKernelGGL((k_code_norms<RNORM, BASED>), dim3((unsigned)((rows + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
+        hipLaunchKernelGGL((k_code_norms<RNORM, BASED, T>), dim3((unsigned)((rows + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), 0,
                            static_cast<hipStream_t>(stream), codes + at * N, rows, P.C, N, K, round_up16(D), out + at, base, L, D,
                            BASED ? assign + at : assign);
         return launch_rc();
@@ -1270,10 +1278,10 @@ WidePlan wide_plan(long Q, int P, int N, int K, int k) {
 }
 
 // search_check with the cap of this feature: k in 65 .. 1,024 passes where search_check tests k > 64, a larger one fails there
-int wide_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
-               const uint64_t *mask, const ListsIn *li, bool outs_ok, const void *workspace, bool *empty) {
+int wide_check(const float *tables, long Q, const void *codes, const float *w, long B, int N, int K, int k, int metric,
+               const uint64_t *mask, const ListsIn *li, bool outs_ok, const void *workspace, bool *empty, int code_bytes = 1) {
     const int as = k > kWideMaxK ? 65 : (k > 64 ? 64 : k);
-    return search_check(tables, Q, codes, w, B, N, K, as, metric, mask, li, outs_ok, workspace, empty);
+    return search_check(tables, Q, codes, w, B, N, K, as, metric, mask, li, outs_ok, workspace, empty, code_bytes);
 }
 
 // li.probes == NULL: the whole store as one list; a bias is a null test inside the kernel, not a flag
@@ -1297,12 +1305,36 @@ int launch_wide(const WidePlan &p, hipStream_t st, const float *tables, int Q, c
     });
 }
 
-// both wide entry points: over the whole store (li == NULL), or list by list
-int search_wide(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
+// launch_wide over two-byte codes (mcq_search_topk_u16): the same plan, the uint16_t instantiations.  N = 64 is reachable at
+// K <= 256 only (rule 33), and then with the largest table the one-byte kernels carry.
+int launch_wide16(const WidePlan &p, hipStream_t st, const float *tables, int Q, const uint16_t *codes, const float *w, long B,
+                  int N, int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
+    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
+            return pick_bool(mask != nullptr, [&](auto masked) {
+                constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
+                constexpr bool MASKED = masked;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_wide<NN, M, MASKED, uint16_t>),
+                                                     wide_lds_bytes(kMaxRows, kListMaxProbes, kWideMaxK)))
+                    return rc;
+                hipLaunchKernelGGL((k_search_wide<NN, M, MASKED, uint16_t>), dim3((unsigned)Q * (unsigned)p.parts),
+                                   dim3(64 * kWideWaves), p.lds, st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts,
+                                   li.list_offsets, li.L, li.probes, li.P, ws_s, ws_i, reinterpret_cast<const u64 *>(mask), li.bias);
+                return launch_rc();
+            });
+        });
+    });
+}
+
+// both wide entry points: over the whole store (li == NULL), or list by list.  T = uint16_t: mcq_search_topk_u16
+template <typename T>
+int search_wide(const float *tables, long Q, const T *codes, const float *w, long B, int N, int K, int k, int metric,
                 const uint64_t *mask, const ListsIn *li, float *out_score, int64_t *out_index, void *workspace,
                 size_t workspace_bytes, void *stream) {
     bool empty;
-    if (const int rc = wide_check(tables, Q, codes, w, B, N, K, k, metric, mask, li, Q == 0 || (out_score && out_index), workspace, &empty))
+    if (const int rc = wide_check(tables, Q, codes, w, B, N, K, k, metric, mask, li, Q == 0 || (out_score && out_index), workspace, &empty,
+                                  sizeof(T)))
         return rc;
     if (Q == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1316,7 +1348,11 @@ int search_wide(const float *tables, long Q, const uint8_t *codes, const float *
         if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
         ws_s = static_cast<float *>(workspace);                            // the workspace: scores, then positions
         ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
-        if (const int rc = launch_wide(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, in, ws_s, ws_i)) return rc;
+        if constexpr (sizeof(T) == 2) {
+            if (const int rc = launch_wide16(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, in, ws_s, ws_i)) return rc;
+        } else {
+            if (const int rc = launch_wide(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, in, ws_s, ws_i)) return rc;
+        }
         S = p.parts;
     }
     hipLaunchKernelGGL(k_search_wide_merge, dim3((unsigned)Q), dim3(64 * kWideWaves), 0, st, ws_s, ws_i, S, k, out_score, out_index);
@@ -1422,10 +1458,11 @@ RangePlan range_plan(long Q, long B, int N, int K) {
     return p;
 }
 
-struct RangeArgs {
+template <typename T>
+struct RangeArgsT {
     const float *tables;
     int Q;
-    const uint8_t *codes;
+    const T *codes;
     const float *w;
     long B;
     int N, K, metric;
@@ -1437,6 +1474,8 @@ struct RangeArgs {
     long capacity;
     const uint64_t *mask;                                                 // NULL: none (rule 12)
 };
+using RangeArgs = RangeArgsT<uint8_t>;
+using RangeArgs16 = RangeArgsT<uint16_t>;                                 // two-byte codes (include/mcq_code16.h)
 
 // a sweep: FILL == false counts, FILL == true stores; a candidate's digits arrive in chunks of CH = min(N, 8)
 template <bool FILL>
@@ -1493,15 +1532,41 @@ int launch_range_lists(const RangeListsPlan &p, hipStream_t st, const RangeArgs 
     });
 }
 
+// launch_range_lists over two-byte codes (mcq_search_range_u16_count / _fill): the same plan, the uint16_t instantiations.
+// li.probes == NULL: the whole store as one list.
+template <bool FILL>
+int launch_range_lists16(const RangeListsPlan &p, hipStream_t st, const RangeArgs16 &a, const ListsIn &li) {
+    return pick<1, 2, 4, 8>(a.N < 8 ? a.N : 8, [&](auto ch) {
+        return pick_bool(a.mask != nullptr, [&](auto masked) {
+            return pick_bool(li.bias != nullptr, [&](auto biased) {
+                constexpr int CH = decltype(ch)::value;
+                constexpr bool MASKED = masked, BIAS = biased;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_lists<CH, FILL, MASKED, BIAS, uint16_t>),
+                                                     lists_lds_bytes(kMaxRows, kListMaxProbes)))
+                    return rc;
+                hipLaunchKernelGGL((k_range_lists<CH, FILL, MASKED, BIAS, uint16_t>), dim3((unsigned)a.Q * (unsigned)p.parts),
+                                   dim3(64 * kRangeListWaves), p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts,
+                                   li.list_offsets, li.L, li.probes, li.P, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity,
+                                   reinterpret_cast<const u64 *>(a.mask), li.bias);
+                return launch_rc();
+            });
+        });
+    });
+}
+
 // rules 9 and 19: what every range entry point rejects -- search_check without k (lims is written even by an empty call),
 // then thr and the size of the workspace; nothing touches the device
-int range_check(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+// code_bytes == 2: a call over the whole store is one list too (launch_range_any), and sized so
+int range_check(const float *tables, long Q, const void *codes, const float *w, long B, int N, int K, int metric,
                 const uint64_t *mask, const ListsIn *li, const float *thr, const int64_t *lims, const void *workspace,
-                size_t workspace_bytes, bool *empty) {
-    if (const int rc = search_check(tables, Q, codes, w, B, N, K, 1, metric, mask, li, lims != nullptr, workspace, empty)) return rc;
+                size_t workspace_bytes, bool *empty, int code_bytes = 1) {
+    if (const int rc = search_check(tables, Q, codes, w, B, N, K, 1, metric, mask, li, lims != nullptr, workspace, empty, code_bytes))
+        return rc;
     if (*empty) return 0;
     if (!thr) return MCQ_EINVAL;                     // (after w and the alignment: all three are MCQ_EINVAL, no code moved)
-    if (workspace_bytes < (li ? range_lists_plan(Q, li->P, N, K).ws_bytes : range_plan(Q, B, N, K).ws_bytes)) return MCQ_EWORKSPACE;
+    const size_t need = (li || code_bytes == 2) ? range_lists_plan(Q, li ? li->P : 1, N, K).ws_bytes : range_plan(Q, B, N, K).ws_bytes;
+    if (workspace_bytes < need) return MCQ_EWORKSPACE;
     return 0;
 }
 
@@ -1518,18 +1583,29 @@ int launch_range_any(hipStream_t st, const RangeArgs &a, const ListsIn *li, int 
     return launch_range<FILL>(p, st, a);
 }
 
+// two-byte codes: always list by list, the whole store as the one list of k_range_lists' probes == NULL
+template <bool FILL>
+int launch_range_any(hipStream_t st, const RangeArgs16 &a, const ListsIn *li, int *per = nullptr) {
+    const ListsIn whole{nullptr, 0, nullptr, 1};
+    const ListsIn &in = li ? *li : whole;
+    const RangeListsPlan p = range_lists_plan(a.Q, in.P, a.N, a.K);
+    if (per) *per = p.parts * kRangeListWaves;
+    return launch_range_lists16<FILL>(p, st, a, in);
+}
+
 // every count entry point: the COUNT sweep, the counts -> offsets per query, the totals -> lims
-int range_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+template <typename T>
+int range_count(const float *tables, long Q, const T *codes, const float *w, long B, int N, int K, int metric,
                 const uint64_t *mask, const ListsIn *li, const float *thr, int64_t *lims, void *workspace, size_t workspace_bytes,
                 void *stream) {
     bool empty;
-    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, li, thr, lims, workspace, workspace_bytes, &empty))
+    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, li, thr, lims, workspace, workspace_bytes, &empty, sizeof(T)))
         return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!empty) {
         int64_t *ws = static_cast<int64_t *>(workspace);
-        const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr, ws, nullptr,
-                          nullptr, nullptr, 0, mask};
+        const RangeArgsT<T> a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr, ws, nullptr,
+                              nullptr, nullptr, 0, mask};
         int per = 0;
         if (const int rc = launch_range_any<false>(st, a, li, &per)) return rc;
         hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)Q), dim3(64), 0, st, ws, per, lims);
@@ -1540,17 +1616,18 @@ int range_count(const float *tables, long Q, const uint8_t *codes, const float *
 }
 
 // every fill entry point: the FILL sweep into out_score / out_index, `capacity` entries each
-int range_fill(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
+template <typename T>
+int range_fill(const float *tables, long Q, const T *codes, const float *w, long B, int N, int K, int metric,
                const uint64_t *mask, const ListsIn *li, const float *thr, const int64_t *lims, float *out_score, int64_t *out_index,
                long capacity, void *workspace, size_t workspace_bytes, void *stream) {
     bool empty;
-    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, li, thr, lims, workspace, workspace_bytes, &empty))
+    if (const int rc = range_check(tables, Q, codes, w, B, N, K, metric, mask, li, thr, lims, workspace, workspace_bytes, &empty, sizeof(T)))
         return rc;
     if (capacity < 0) return MCQ_EINVAL;
     if (empty || capacity == 0) return 0;                                  // nothing can be stored
     if (!out_score || !out_index) return MCQ_EINVAL;
-    const RangeArgs a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
-                      static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity, mask};
+    const RangeArgsT<T> a{tables, (int)Q, codes, metric == MCQ_SEARCH_IP ? nullptr : w, B, N, K, metric, thr,
+                          static_cast<int64_t *>(workspace), lims, out_score, out_index, capacity, mask};
     return launch_range_any<true>(static_cast<hipStream_t>(stream), a, li);
 }
 
@@ -2261,9 +2338,9 @@ int mcq_grad_tail(const float *part_c, long n_c, const float *sa, const float *s
 }
 
 // ---- search over stored codes: mcq_search_kernels.h (the launch arithmetic is above, ahead of the C linkage block)
-int mcq_search_tables(const void *q, int q_is_fp16, long Q, const void *prepared, int N, int K, int D, float *tables_out,
-                      void *stream) {
-    if (const int rc = search_domain(N, K, D)) return rc;
+static int search_tables(int domain_rc, const void *q, int q_is_fp16, long Q, const void *prepared, int N, int K, int D,
+                         float *tables_out, void *stream) {
+    if (domain_rc) return domain_rc;
     if (Q < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
     if (Q == 0) return 0;
     if (!q || !prepared || !tables_out) return MCQ_EINVAL;
@@ -2273,6 +2350,11 @@ int mcq_search_tables(const void *q, int q_is_fp16, long Q, const void *prepared
                        dim3(256), 0, static_cast<hipStream_t>(stream), q, q_is_fp16 ? 1 : 0, (int)Q, P.C, NK, D, round_up16(D),
                        tables_out);
     return launch_rc();
+}
+
+int mcq_search_tables(const void *q, int q_is_fp16, long Q, const void *prepared, int N, int K, int D, float *tables_out,
+                      void *stream) {
+    return search_tables(search_domain(N, K, D), q, q_is_fp16, Q, prepared, N, K, D, tables_out, stream);
 }
 
 int mcq_code_norms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *norms_out, void *stream) {
@@ -2459,6 +2541,58 @@ int mcq_rerank(const void *queries, int queries_half, long Q, const void *vector
                int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
     return rerank(queries, queries_half != 0, Q, vectors, vectors_half != 0, B, D, shortlist, S, row_of, Bs, k, metric, out_score,
                   out_index, workspace, workspace_bytes, stream);
+}
+
+// ---- rules 32-35 (include/mcq_code16.h): stores of two-byte codes.  probes == NULL: the whole store
+int mcq_search_tables_u16(const void *q, int q_is_fp16, long Q, const void *prepared, int N, int K, int D, float *tables_out,
+                          void *stream) {
+    return search_tables(code16_domain(N, K, D), q, q_is_fp16, Q, prepared, N, K, D, tables_out, stream);
+}
+
+int mcq_code_norms_u16(const uint16_t *codes, long B, const void *prepared, int N, int K, int D, int rnorm, const float *base,
+                       long L, const int32_t *assign, float *out, void *stream) {
+    if (!base && !assign)
+        return rnorm ? code_norms<true, false>(codes, B, prepared, N, K, D, out, stream)
+                     : code_norms<false, false>(codes, B, prepared, N, K, D, out, stream);
+    return rnorm ? code_norms<true, true>(codes, B, prepared, N, K, D, out, stream, base, L, assign)
+                 : code_norms<false, true>(codes, B, prepared, N, K, D, out, stream, base, L, assign);
+}
+
+size_t mcq_search_topk_u16_workspace_bytes(long Q, int P, int N, int K, int k) {
+    if (Q <= 0 || P <= 0 || P > kListMaxProbes || k < 1 || k > kWideMaxK || Q > 0x7fffffffL || code16_domain(N, K, 1) != 0) return 256;
+    return 2 * wide_plan(Q, P, N, K, k).ws_half;
+}
+
+int mcq_search_topk_u16(const float *tables, long Q, const uint16_t *codes, const float *w, long B, int N, int K, int k, int metric,
+                        const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes, int P,
+                        const float *probe_bias, float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes,
+                        void *stream) {
+    const ListsIn li{list_offsets, L, probes, P, probe_bias};
+    return search_wide(tables, Q, codes, w, B, N, K, k, metric, mask, probes ? &li : nullptr, out_score, out_index, workspace,
+                       workspace_bytes, stream);
+}
+
+size_t mcq_search_range_u16_workspace_bytes(long Q, int P, int N, int K) {
+    if (Q <= 0 || P <= 0 || P > kListMaxProbes || Q > 0x7fffffffL || code16_domain(N, K, 1) != 0) return 256;
+    return range_lists_plan(Q, P, N, K).ws_bytes;
+}
+
+int mcq_search_range_u16_count(const float *tables, long Q, const uint16_t *codes, const float *w, long B, int N, int K, int metric,
+                               const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes, int P,
+                               const float *probe_bias, const float *thr, int64_t *lims, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+    const ListsIn li{list_offsets, L, probes, P, probe_bias};
+    return range_count(tables, Q, codes, w, B, N, K, metric, mask, probes ? &li : nullptr, thr, lims, workspace, workspace_bytes,
+                       stream);
+}
+
+int mcq_search_range_u16_fill(const float *tables, long Q, const uint16_t *codes, const float *w, long B, int N, int K, int metric,
+                              const uint64_t *mask, const int64_t *list_offsets, long L, const int32_t *probes, int P,
+                              const float *probe_bias, const float *thr, const int64_t *lims, float *out_score, int64_t *out_index,
+                              long capacity, void *workspace, size_t workspace_bytes, void *stream) {
+    const ListsIn li{list_offsets, L, probes, P, probe_bias};
+    return range_fill(tables, Q, codes, w, B, N, K, metric, mask, probes ? &li : nullptr, thr, lims, out_score, out_index, capacity,
+                      workspace, workspace_bytes, stream);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

@@ -153,15 +153,19 @@ k_range_sweep(const float *__restrict__ tables, int Q, const uint8_t *__restrict
 //     finish the count unchanged.  No atomics of any kind.
 //   * with a bias (BIAS; rules 21-23): s = score_finish(S + the bias of the step's slot, w), the bias travelling with the
 //     cursor as in k_search_lists; the same step space, runs, counts and slots.
+//   * T: the digit type of the store (CodeChunk).  With uint16_t (include/mcq_code16.h) probes == NULL is the whole store as
+//     ONE implicit list [0, B) (P is 1, list_offsets and L are not read), as in k_search_wide: parts and runs ascend with
+//     the position, so the hits of a query leave in ascending position and two-byte codes need no sweep of their own.  The
+//     one-byte instantiations have k_range_sweep for that and do not test the pointer: they are the code they were.
 // LDS: lists_lds_bytes of mcq_search_kernels.h.
 constexpr int kRangeListWaves = 4;        // k_range_lists: waves per workgroup (256 threads), as kListWaves: a table is N*K
                                           // floats (8 KiB at 8 x 256), so several workgroups share a CU and 4 waves each keep
                                           // 4 per SIMD at 4 workgroups per CU (not measured against 8 or 16)
 
 // ws: int64 [Q][S][kRangeListWaves] -- counts out (COUNT), start offsets relative to lims[q] in (FILL).
-template <int CH, bool FILL, bool MASKED, bool BIAS>
+template <int CH, bool FILL, bool MASKED, bool BIAS, typename T = uint8_t>
 __global__ void __launch_bounds__(64 * kRangeListWaves)
-k_range_lists(const float *__restrict__ tables, const uint8_t *__restrict__ codes, const float *__restrict__ w, long B,
+k_range_lists(const float *__restrict__ tables, const T *__restrict__ codes, const float *__restrict__ w, long B,
               int N, int K, int metric, int S, const int64_t *__restrict__ list_offsets, long L, const int *__restrict__ probes,
               int P, const float *__restrict__ thr, int64_t *__restrict__ ws, const int64_t *__restrict__ lims,
               float *__restrict__ out_s, int64_t *__restrict__ out_i, long capacity, const u64 *__restrict__ mask,
@@ -172,8 +176,13 @@ k_range_lists(const float *__restrict__ tables, const uint8_t *__restrict__ code
     const int q = blockIdx.x / S, part = blockIdx.x % S;
     const int NK = N * K;
     ListWalk walk;
-    const long long T = walk.build<THREADS>(range_smem, NK, list_offsets, L, probes + (long)q * P, P, B, tid);
-    const long long lo = T * part / S, hi = T * (part + 1) / S;           // (T <= 2^37, S <= 256)
+    long long steps;
+    if (sizeof(T) > 1 && !probes) {
+        steps = walk.whole(range_smem, NK, B, tid);
+    } else {
+        steps = walk.build<THREADS>(range_smem, NK, list_offsets, L, probes + (long)q * P, P, B, tid);
+    }
+    const long long lo = steps * part / S, hi = steps * (part + 1) / S;   // (steps <= 2^37, S <= 256)
     int64_t *mine = ws + ((long)q * S + part) * kRangeListWaves;           // this part's kRangeListWaves entries
     if (lo >= hi) {                                          // no step: zeros (COUNT), and nothing is staged
         if (!FILL && tid < kRangeListWaves) mine[tid] = 0;
@@ -192,7 +201,7 @@ k_range_lists(const float *__restrict__ tables, const uint8_t *__restrict__ code
     if constexpr (FILL) base = lims[q] + mine[wave];
     long cnt = 0;                                            // (uniform) this wave's hits so far (a list named twice counts twice)
 
-    CodeChunk<CH> cur;
+    CodeChunk<CH, T> cur;
     float t = 0.f;
     ListCursor<MASKED, BIAS> pos;
     pos.start(walk, step, stop, cur, t, codes, w, metric, N, mask, brow, lane);

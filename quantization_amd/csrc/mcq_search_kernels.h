@@ -141,9 +141,11 @@ __device__ __forceinline__ float rnorm_of(float t) { return t == 0.f ? 0.f : 1.0
 // Dp; a row need not be 16-byte aligned, so it is read element by element), features d >= D get no base (the pad columns of
 // C are zero: they contribute zero).  assign[b] outside [0, L) adds no base row.  Without BASED the four last arguments are
 // never read.
-template <bool RNORM, bool BASED>
+// T: the type of a stored digit, uint8_t or uint16_t (two-byte codes, include/mcq_code16.h rule 32): lane n reads digit n as
+// one element of T.
+template <bool RNORM, bool BASED, typename T = uint8_t>
 __global__ void __launch_bounds__(64 * kNormWaves)
-k_code_norms(const uint8_t *__restrict__ codes, long B, const float *__restrict__ C, int N, int K, int Dp,
+k_code_norms(const T *__restrict__ codes, long B, const float *__restrict__ C, int N, int K, int Dp,
              float *__restrict__ norms, const float *__restrict__ base, long L, int D, const int *__restrict__ assign) {
     const long b = (long)blockIdx.x * kNormWaves + (threadIdx.x >> 6);
     if (b >= B) return;
@@ -193,25 +195,44 @@ k_rnorms_from_norms(const float *__restrict__ norms, long B, float *__restrict__
 // (one vector load) and reuses them for every query of the tile.  Every wave keeps one sorted list per query in registers, one
 // entry per lane; the waves' lists are merged per query through LDS (the tables are dead by then) and the workgroup leaves one
 // list of k entries per (query, slice) in the workspace.
-// Up to 8 codebooks' digits of one candidate: one vector load.
-template <int CH>
+// Up to 8 codebooks' digits of one candidate: one vector load.  T is the type of a stored digit: uint8_t (the default: every
+// kernel written before two-byte codes existed is the instantiation it was), four digits to a word, or uint16_t
+// (include/mcq_code16.h rule 32), two digits to a word and a load of 2, 4, 8 or 16 bytes.  Either way a digit is masked with
+// K - 1 by the caller's kmask, so whatever bits a stored element holds the LDS read stays inside the table.
+template <int CH, typename T = uint8_t>
 struct CodeChunk {
-    uint32_t w[(CH + 3) / 4];
-    __device__ __forceinline__ void load(const uint8_t *__restrict__ p) {
-        if constexpr (CH == 1) {
+    static_assert(sizeof(T) == 1 || sizeof(T) == 2, "one-byte or two-byte digits");
+    static constexpr int PER = 4 / (int)sizeof(T);           // digits per 32-bit word
+    static constexpr int WORDS = (CH + PER - 1) / PER;
+    uint32_t w[WORDS];
+    __device__ __forceinline__ void load(const T *__restrict__ p) {
+        static_assert(CH == 1 || CH == 2 || CH == 4 || CH == 8, "chunks of 1, 2, 4 or 8 codebooks");
+        if constexpr (CH * sizeof(T) <= 1) {
             w[0] = p[0];
-        } else if constexpr (CH == 2) {
+        } else if constexpr (CH * sizeof(T) == 2) {
             w[0] = *reinterpret_cast<const uint16_t *>(p);
-        } else if constexpr (CH == 4) {
+        } else if constexpr (CH * sizeof(T) == 4) {
             w[0] = *reinterpret_cast<const uint32_t *>(p);
-        } else {
-            static_assert(CH == 8, "chunks of 1, 2, 4 or 8 codebooks");
+        } else if constexpr (CH * sizeof(T) == 8) {
             const uint2 v = *reinterpret_cast<const uint2 *>(p);
             w[0] = v.x;
             w[1] = v.y;
+        } else {
+            const uint4 v = *reinterpret_cast<const uint4 *>(p);
+            w[0] = v.x;
+            w[1] = v.y;
+            w[2] = v.z;
+            w[3] = v.w;
         }
     }
-    __device__ __forceinline__ int digit(int n, int kmask) const { return (int)(w[n >> 2] >> (8 * (n & 3))) & kmask; }
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int i = 0; i < WORDS; ++i) w[i] = 0;
+    }
+    __device__ __forceinline__ int digit(int n, int kmask) const {
+        if constexpr (sizeof(T) == 1) return (int)(w[n >> 2] >> (8 * (n & 3))) & kmask;
+        return (int)(w[n >> 1] >> (16 * (n & 1))) & kmask;
+    }
 };
 
 // ---- the tile scorer: everything k_search_scan and k_range_sweep (mcq_range_kernels.h) share -- the staging of the tables,
@@ -255,16 +276,15 @@ __device__ __forceinline__ long step_at(const Slice &sl, long step, int lane) {
 // What a step needs from HBM travels one step ahead, in two plain locals of the kernel: `cur`, its first CH digits, and its
 // w (t[b] under L2, r[b] under the cosine, never read under kMetricIP).  tile_first loads those of a wave's first step (none
 // when it has no step: first >= stop).  `metric` and N may be compile-time values of the caller here and in tile_step.
-template <int CH>
-__device__ __forceinline__ void tile_first(CodeChunk<CH> &cur, float &t, const uint8_t *__restrict__ codes,
+template <int CH, typename T>
+__device__ __forceinline__ void tile_first(CodeChunk<CH, T> &cur, float &t, const T *__restrict__ codes,
                                            const float *__restrict__ w, int metric, int N, const Slice &sl, long first, long stop,
                                            int lane) {
     if (first < stop) {
         cur.load(codes + step_at(sl, first, lane) * N);
         if (metric != kMetricIP) t = w[step_at(sl, first, lane)];
     } else {
-        cur.w[0] = 0;
-        if constexpr (CH == 8) cur.w[1] = 0;
+        cur.clear();
     }
 }
 
@@ -322,17 +342,18 @@ k_pack_mask(const uint8_t *__restrict__ flags, long B, u64 *__restrict__ mask) {
 // NCONST: N where the caller has it as a template parameter (the scan), 0 where N is a runtime value (the sweep).  The chunk
 // count has to be a constant BEFORE inlining: without it the scans of two chunks (N = 16) under kMetricIP compile to a branch
 // where the loop had a select, and take up to 13 VGPRs more.
-template <int QT, int CH, int NCONST = 0>
-__device__ __forceinline__ void tile_step(float (&acc)[QT], CodeChunk<CH> &cur, float &tn, const float *Tl,
-                                          const uint8_t *__restrict__ codes, const float *__restrict__ w, int metric, int N, int K,
+// T: the digit type, deduced from `cur` and `codes`; the chunks of a row sit CH elements of T apart.
+template <int QT, int CH, int NCONST = 0, typename T>
+__device__ __forceinline__ void tile_step(float (&acc)[QT], CodeChunk<CH, T> &cur, float &tn, const float *Tl,
+                                          const T *__restrict__ codes, const float *__restrict__ w, int metric, int N, int K,
                                           long b, long bnext) {
     const int kmask = K - 1, nch = NCONST ? NCONST / CH : N / CH;
-    const uint8_t *p = codes + b * N;
+    const T *p = codes + b * N;
 #pragma unroll
     for (int q = 0; q < QT; ++q) acc[q] = -0.f;              // (-0) + x == x for every x, signed zeros included
 #pragma unroll 1
     for (int c = 0; c < nch; ++c) {
-        CodeChunk<CH> nxt;                                   // the next step's digits travel while this one gathers
+        CodeChunk<CH, T> nxt;                                // the next step's digits travel while this one gathers
         if (c + 1 < nch) {
             nxt.load(p + (c + 1) * CH);
         } else {
@@ -573,6 +594,24 @@ struct ListWalk {
         __syncthreads();
         return pre[P];
     }
+    // (every thread of the workgroup; k_range_lists over two-byte codes) the whole store as ONE implicit list [0, B), laid
+    // out as build() lays out a row of one probe -> its steps
+    __device__ __forceinline__ long long whole(char *smem, int NK, long B, int tid) {
+        pre = reinterpret_cast<long long *>(smem + lists_lds_head(NK));
+        lbeg = reinterpret_cast<int *>(pre + 2);
+        lend = lbeg + 1;
+        P = 1;
+        p = 0;
+        const long long T = (B + 63) / 64;
+        if (tid == 0) {
+            pre[0] = 0;
+            pre[1] = T;
+            lbeg[0] = 0;
+            lend[0] = (int)B;
+        }
+        __syncthreads();
+        return T;
+    }
     __device__ __forceinline__ Slice seek(long long step, long &j) {
         int a = 0, z = P;                                    // pre[a] <= step < pre[z]
         while (z - a > 1) {
@@ -603,9 +642,9 @@ struct ListCursor {
     float bias, bias_next;
 
     // the wave's first step: its digits and w go to cur and t (tile_first: one step, or none when step >= stop)
-    template <int CH>
-    __device__ __forceinline__ void start(ListWalk &walk, long long step, long long stop, CodeChunk<CH> &cur, float &t,
-                                          const uint8_t *__restrict__ codes, const float *__restrict__ w, int metric, int N,
+    template <int CH, typename T>
+    __device__ __forceinline__ void start(ListWalk &walk, long long step, long long stop, CodeChunk<CH, T> &cur, float &t,
+                                          const T *__restrict__ codes, const float *__restrict__ w, int metric, int N,
                                           const u64 *__restrict__ mask, const float *__restrict__ brow, int lane) {
         Slice sl{0, 1, 0};
         long j = 0;

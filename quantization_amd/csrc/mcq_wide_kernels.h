@@ -141,9 +141,11 @@ struct WideList {
 // probe_bias == NULL: no bias.  The bias is no template parameter here: a call without one adds -0.0, and (S + -0.0) has the
 // bits of S for every S.  It travels one step ahead as ListCursor's does: read at walk.p once peek() has moved that on.
 // The part leaves as k entries, ascending, at list (q, part) of the workspace; an entry without a candidate is (+inf, kNoIndex).
-template <int N, int M, bool MASKED>
+// T: the digit type of the store (CodeChunk).  With uint16_t (include/mcq_code16.h) this kernel serves every k from 1: the
+// narrow kernels have no two-byte twin.
+template <int N, int M, bool MASKED, typename T = uint8_t>
 __global__ void __launch_bounds__(64 * kWideWaves)
-k_search_wide(const float *__restrict__ tables, int Q, const uint8_t *__restrict__ codes, const float *__restrict__ w,
+k_search_wide(const float *__restrict__ tables, int Q, const T *__restrict__ codes, const float *__restrict__ w,
               long B, int K, int k, int S, const int64_t *__restrict__ list_offsets, long L, const int *__restrict__ probes,
               int P, float *__restrict__ ws_s, int *__restrict__ ws_i, const u64 *__restrict__ mask,
               const float *__restrict__ probe_bias) {
@@ -153,25 +155,13 @@ k_search_wide(const float *__restrict__ tables, int Q, const uint8_t *__restrict
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x / S, part = blockIdx.x % S;
     ListWalk walk;
-    long long T;
+    long long steps;
     if (probes) {
-        T = walk.build<THREADS>(search_smem, N * K, list_offsets, L, probes + (long)q * P, P, B, tid);
-    } else {                                                 // the one list [0, B), laid out as build() lays a row out
-        walk.pre = reinterpret_cast<long long *>(search_smem + lists_lds_head(N * K));
-        walk.lbeg = reinterpret_cast<int *>(walk.pre + 2);
-        walk.lend = walk.lbeg + 1;
-        walk.P = 1;
-        walk.p = 0;
-        T = (B + 63) / 64;
-        if (tid == 0) {
-            walk.pre[0] = 0;
-            walk.pre[1] = T;
-            walk.lbeg[0] = 0;
-            walk.lend[0] = (int)B;
-        }
-        __syncthreads();
+        steps = walk.build<THREADS>(search_smem, N * K, list_offsets, L, probes + (long)q * P, P, B, tid);
+    } else {                                                 // the one list [0, B)
+        steps = walk.whole(search_smem, N * K, B, tid);
     }
-    const long long lo = T * part / S, hi = T * (part + 1) / S;           // (T <= 2^37, S <= 256)
+    const long long lo = steps * part / S, hi = steps * (part + 1) / S;           // (T <= 2^37, S <= 256)
     const long out = ((long)q * S + part) * k;
     if (lo >= hi) {                                          // no step: the empty list, and nothing is staged
         for (int e = tid; e < k; e += THREADS) {
@@ -186,7 +176,7 @@ k_search_wide(const float *__restrict__ tables, int Q, const uint8_t *__restrict
     WideList<THREADS> list;
     list.init(search_smem + wide_lds_list(N * K, P), k, tid);
 
-    CodeChunk<CH> cur;
+    CodeChunk<CH, T> cur;
     float t = 0.f;
     ListCursor<MASKED, false> pos;
     long long step = lo + wave;

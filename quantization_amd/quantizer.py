@@ -433,7 +433,8 @@ class Quantizer(SearchMixin, nn.Module):
 
     def decode(self, indexes: Tensor) -> Tensor:
         """codes (*, num_codebooks) or packed (*, num_codebooks / r), any integer dtype ->
-        fp32 (*, dim) sum of the chosen scaled centers.  quantization.py:117-148.
+        fp32 (*, dim) sum of the chosen scaled centers.  quantization.py:117-148.  The int16 store pack_codes makes for
+        codebook_size > 256 is one such dtype: it is widened in torch to the int64 digits the kernel takes.
         Differentiable w.r.t. centers / centers_scale when autograd is recording."""
         lead = indexes.shape[:-1]
         per_row = indexes.shape[-1]

@@ -1,5 +1,6 @@
 """The search over stored codes (not in the reference): top-k and range search, under a mask, list by list; include/mcq.h
-rules 1-20, include/mcq_residual.h rules 21-23 and include/mcq_wide.h rules 24-27 (top-k past 64 neighbours).  `SearchMixin` holds the methods `Quantizer` offers for it.  It has no state of its own: it uses num_codebooks,
+rules 1-20, include/mcq_residual.h rules 21-23, include/mcq_wide.h rules 24-27 (top-k past 64 neighbours) and
+include/mcq_code16.h rules 32-35 (stores of two-byte codes, codebook_size 512 and 1,024).  `SearchMixin` holds the methods `Quantizer` offers for it.  It has no state of its own: it uses num_codebooks,
 codebook_size, dim, _prepared and _check_domain of the class it is mixed into.
 
 Each rule of the layer is written once here: the device check (_on_device), the metric check (check_metric), the choice of
@@ -32,6 +33,12 @@ _TABLES, _PACK_MASK = "mcq_search_tables", "mcq_search_pack_mask"
 # Either takes every optional operand, as a pointer that may be NULL.
 _WIDE = {False: ("mcq_search_wide", "mcq_search_wide_workspace_bytes"),
          True: ("mcq_search_wide_lists", "mcq_search_wide_lists_workspace_bytes")}
+# stores of two-byte codes (include/mcq_code16.h; codebook_size > 256): ONE top-k entry for every k up to 1,024 and one pair
+# of range entries, each taking every optional operand as a pointer that may be NULL -- no probes is the whole store
+_TABLES16, _NORMS16 = "mcq_search_tables_u16", "mcq_code_norms_u16"
+_TOPK16 = ("mcq_search_topk_u16", "mcq_search_topk_u16_workspace_bytes")
+_RANGE16 = ("mcq_search_range_u16_count", "mcq_search_range_u16_fill", "mcq_search_range_u16_workspace_bytes")
+CODE16_MAX_ROWS = 16384         # num_codebooks * codebook_size at most: the 64 KiB of table a search kernel carries
 WIDE_MAX_K = 1024               # search_wide and search_lists_wide: the largest k
 NARROW_MAX_K = 64               # search and search_lists: the largest k
 
@@ -149,18 +156,50 @@ class SearchMixin:
 
     def _search_state(self, dev):
         """(blob, stream) for the search entry points: any flavour of derived state will do (they read the scaled centers)."""
+        self._two_byte()
         self._check_domain()
-        if self.codebook_size > 256:
-            raise _lib.McqError("quantization_amd: the search over stored codes takes one-byte codes (codebook_size <= 256)")
         with torch.no_grad():
             blob = self._prepared(any_flavour=True)
         return blob, torch.cuda.current_stream(dev).cuda_stream
 
+    def _two_byte(self) -> bool:
+        """whether the stores of this quantizer hold two-byte codes (codebook_size > 256: pack_codes, include/mcq_code16.h);
+        their tables must fit the search kernels"""
+        N, K = self.num_codebooks, self.codebook_size
+        if K > 256 and N * K > CODE16_MAX_ROWS:
+            raise _lib.McqError(f"quantization_amd: the search over two-byte codes takes num_codebooks * codebook_size <= "
+                                f"{CODE16_MAX_ROWS:,} (a query's table is that many floats in LDS), not {N} x {K}")
+        return K > 256
+
+    def pack_codes(self, indexes: Tensor) -> Tensor:
+        """integer digits (*, num_codebooks) as encode(..., as_bytes=False) returned them -> the store the searches take:
+        torch.int16 (*, num_codebooks) for codebook_size > 256 (2 bytes per digit where int64 spends 8), torch.uint8
+        (*, num_codebooks), one digit per byte, otherwise.  A digit outside [0, codebook_size) is a ValueError (one host
+        synchronisation).  decode() takes either store."""
+        N, K = self.num_codebooks, self.codebook_size
+        if not isinstance(indexes, Tensor) or indexes.dtype.is_floating_point or indexes.dtype.is_complex or \
+                indexes.dtype == torch.bool or indexes.ndim < 1 or indexes.shape[-1] != N:
+            raise ValueError(f"pack_codes: an integer (*, {N}) tensor of digits, not {getattr(indexes, 'dtype', type(indexes))} "
+                             f"{tuple(getattr(indexes, 'shape', ()))}")
+        if indexes.numel() and (int(indexes.min()) < 0 or int(indexes.max()) >= K):
+            raise ValueError(f"pack_codes: digits outside [0, {K})")
+        return indexes.detach().to(torch.int16 if K > 256 else torch.uint8).contiguous()
+
     def _unpacked_codes(self, codes: Tensor) -> Tensor:
-        """codes as encode(..., as_bytes=True) returned them -> uint8 (B, num_codebooks), one digit per byte, on the device."""
-        _on_device(codes)
+        """codes as encode(..., as_bytes=True) returned them -> uint8 (B, num_codebooks), one digit per byte, on the device.
+        codebook_size > 256: the int16 store of pack_codes (int64 digits are narrowed, per call) -> int16 (B, num_codebooks)."""
         N, K = self.num_codebooks, self.codebook_size
         flat = codes.reshape(-1, codes.shape[-1])
+        if self._two_byte():                                       # (shape and dtype first: they need no device)
+            if flat.dtype not in (torch.int16, torch.int64):
+                raise _lib.McqError(f"quantization_amd: with codebook_size {K} the search takes the int16 store that "
+                                    f"pack_codes makes of encode(..., as_bytes=False), not {flat.dtype} codes")
+            if flat.shape[1] != N:
+                raise _lib.McqError(f"codes of {flat.shape[1]} digits per vector do not belong to {N} codebooks of {K}")
+            _on_device(codes)
+            flat = flat.to(torch.int16).contiguous()
+            return flat.clone() if flat.data_ptr() % 16 else flat
+        _on_device(codes)
         if flat.dtype != torch.uint8:
             raise _lib.McqError("quantization_amd: the search takes uint8 codes (encode(..., as_bytes=True))")
         if flat.shape[1] != N:
@@ -173,7 +212,9 @@ class SearchMixin:
         return flat
 
     def search_tables(self, queries: Tensor) -> Tensor:
-        """queries (*, dim) fp32 or fp16 -> fp32 (Q, num_codebooks, codebook_size): T[q][n][k] = -2 <q, C[n][k]> (mcq_search_tables)."""
+        """queries (*, dim) fp32 or fp16 -> fp32 (Q, num_codebooks, codebook_size): T[q][n][k] = -2 <q, C[n][k]> (mcq_search_tables;
+        mcq_search_tables_u16 with codebook_size > 256)."""
+        self._two_byte()
         _on_device(queries)
         N, K, D = self.num_codebooks, self.codebook_size, self.dim
         q2d = queries.detach().reshape(-1, D)
@@ -182,11 +223,12 @@ class SearchMixin:
         with torch.no_grad(), torch.cuda.device(dev):
             blob, st = self._search_state(dev)
             out = torch.empty((Q, N, K), dtype=torch.float32, device=dev)
-            _call(_TABLES, q2d.data_ptr(), int(q2d.dtype == torch.float16), Q, blob.data_ptr(), N, K, D, out.data_ptr(), st)
+            _call(_TABLES16 if K > 256 else _TABLES, q2d.data_ptr(), int(q2d.dtype == torch.float16), Q, blob.data_ptr(), N, K, D, out.data_ptr(), st)
         return out
 
-    def _code_norms(self, codes: Tensor, entry: str, base=None, assign=None) -> Tensor:
-        """code_norms and code_rnorms: `entry` names the library call; with base and assign its _based twin (rule 22)"""
+    def _code_norms(self, codes: Tensor, rnorm: bool, base=None, assign=None) -> Tensor:
+        """code_norms and code_rnorms (rnorm): mcq_code_norms / mcq_code_rnorms, with base and assign their _based twins
+        (rule 22); over two-byte codes the one entry mcq_code_norms_u16"""
         N, K, D = self.num_codebooks, self.codebook_size, self.dim
         if (base is None) != (assign is None):
             raise ValueError("code_norms: base and assign come together (base[assign[b]] is added to the decode of codes[b])")
@@ -204,9 +246,8 @@ class SearchMixin:
         with torch.no_grad(), torch.cuda.device(dev):
             blob, st = self._search_state(dev)
             out = torch.empty((B,), dtype=torch.float32, device=dev)
-            if base is None:
-                _call(entry, flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
-            else:
+            L, a = 0, None
+            if base is not None:
                 _on_device(base, assign)
                 base = base.detach().to(torch.float32).contiguous()
                 L = base.shape[0]
@@ -214,23 +255,31 @@ class SearchMixin:
                 if a.dtype != torch.int32:                         # (a value that names no row stays one after narrowing)
                     a = torch.where((a >= 0) & (a < L), a, torch.full_like(a, -1)).to(torch.int32)
                 a = a.contiguous()
+            entry = "mcq_code_rnorms" if rnorm else "mcq_code_norms"
+            if flat.dtype == torch.int16:
+                _call(_NORMS16, flat.data_ptr(), B, blob.data_ptr(), N, K, D, int(rnorm), None if base is None else base.data_ptr(),
+                      L, None if a is None else a.data_ptr(), out.data_ptr(), st)
+            elif base is None:
+                _call(entry, flat.data_ptr(), B, blob.data_ptr(), N, K, D, out.data_ptr(), st)
+            else:
                 _call(entry + "_based", flat.data_ptr(), B, blob.data_ptr(), N, K, D, base.data_ptr(), L, a.data_ptr(),
                       out.data_ptr(), st)
         return out
 
     def code_norms(self, codes: Tensor, base: Tensor = None, assign: Tensor = None) -> Tensor:
-        """codes (*, num_codebooks) uint8 (or packed, codebook_size 16) -> fp32 (B,): |decode(codes[b])|^2 (mcq_code_norms).
+        """codes (*, num_codebooks) uint8 (or packed, codebook_size 16; the int16 store of pack_codes with codebook_size >
+        256, as every method here takes it) -> fp32 (B,): |decode(codes[b])|^2 (mcq_code_norms).
         Formed once per store of codes and handed to search(norms=...).
         base (L, dim) and assign integer (B,), both or neither: |base[assign[b]] + decode(codes[b])|^2
         (mcq_code_norms_based) -- the norms of a store of RESIDUAL codes, base the coarse centroids and assign[b] the list of
         position b (quantization_amd.ivf.list_assign); an assign[b] outside [0, L) adds no row."""
-        return self._code_norms(codes, "mcq_code_norms", base, assign)
+        return self._code_norms(codes, False, base, assign)
 
     def code_rnorms(self, codes: Tensor, base: Tensor = None, assign: Tensor = None) -> Tensor:
         """codes as for code_norms -> fp32 (B,): 1 / sqrt(code_norms(codes)), 0 for an all-zero reconstruction (mcq_code_rnorms).
         What the cosine search multiplies by: formed once per store and handed to search(metric="cosine", rnorms=...).
         base and assign as code_norms takes them (mcq_code_rnorms_based): the same bits as rnorms_from_norms of its result."""
-        return self._code_norms(codes, "mcq_code_rnorms", base, assign)
+        return self._code_norms(codes, True, base, assign)
 
     def rnorms_from_norms(self, norms: Tensor) -> Tensor:
         """norms fp32 (B,) as code_norms returned them -> fp32 (B,): the same values code_rnorms gives, without a gather
@@ -299,13 +348,19 @@ class SearchMixin:
         if codes.data_ptr() % 16:
             codes = codes.clone()
         Q, B, dev = tables.shape[0], codes.shape[0], tables.device
-        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and codes.dtype == torch.uint8
+        # a store of two-byte codes (include/mcq_code16.h): the public calls make one iff codebook_size > 256 (_unpacked_codes);
+        # here the dtype decides, so that _search_scan and _search_range can hold the two kinds against each other at K <= 256
+        two = codes.dtype == torch.int16
+        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N)
+        assert two or (codes.dtype == torch.uint8 and K <= 256)
         assert w is None or tuple(w.shape) == (B,)
         has = {"bias": lists is not None and len(lists) == 3, "lists": lists is not None, "mask": mask is not None,
                "metric": metric != "l2", None: True}
         first, scan, scan_bytes, count, fill, range_bytes = next(row for row in _ENTRIES if has[row[0]])
         if wide:                                                  # (k given) the wide pair takes what the call has and NULL for the rest
             first, (scan, scan_bytes) = "wide", _WIDE[has["lists"]]
+        if two:                                                   # one entry for every k, narrow or wide; one pair for the range
+            first, (scan, scan_bytes), (count, fill, range_bytes) = "code16", _TOPK16, _RANGE16
         with torch.no_grad(), torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             # every tensor made here stays alive until the last launch of the call has been enqueued
@@ -315,7 +370,12 @@ class SearchMixin:
             if k is None or first is not None:                    # (the oldest scan is L2 only and takes no metric)
                 args += (METRICS[metric],)
             words = None if mask is None else mask.detach().contiguous() if mask.dtype == torch.int64 else self.pack_mask(mask)
-            if lists is not None:
+            if two:
+                offsets, probes = (None, None) if lists is None else lists[:2]
+                args += (None if words is None else words.data_ptr(), None if lists is None else offsets.data_ptr(),
+                         0 if lists is None else offsets.numel() - 1, None if lists is None else probes.data_ptr(),
+                         1 if lists is None else probes.shape[1], lists[2].data_ptr() if has["bias"] else None)
+            elif lists is not None:
                 offsets, probes = lists[:2]
                 args += (None if words is None else words.data_ptr(), offsets.data_ptr(), offsets.numel() - 1,
                          probes.data_ptr(), probes.shape[1])
@@ -325,7 +385,7 @@ class SearchMixin:
                     args += (lists[2].data_ptr() if has["bias"] else None,)
             elif mask is not None or wide:
                 args += (None if words is None else words.data_ptr(),)
-            size = (Q, B if lists is None else probes.shape[1], N, K) + (() if k is None else (k,))
+            size = (Q, (1 if two else B) if lists is None else probes.shape[1], N, K) + (() if k is None else (k,))
             ws = torch.empty(_entry(range_bytes if k is None else scan_bytes)(*size), dtype=torch.uint8, device=dev)
             if k is not None:
                 scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
@@ -364,7 +424,10 @@ class SearchMixin:
                rnorms: Tensor = None, mask: Tensor = None):
         """The k stored vectors nearest to each query, from the codes alone (nothing is decoded).
         queries (*, dim) fp32 or fp16; codes (B, num_codebooks) uint8 as encode(..., as_bytes=True) returned them (packed
-        16-entry codes are unpacked first); norms = code_norms(codes) when not given (pass them in when searching repeatedly).
+        16-entry codes are unpacked first).  With codebook_size > 256 -- here and in every other method of the search --
+        codes is the int16 (B, num_codebooks) store pack_codes makes of encode(..., as_bytes=False); int64 digits are
+        accepted and narrowed on every call, so keep the store packed; uint8 is refused; num_codebooks * codebook_size is
+        at most 16,384; and k may be anything up to 1,024 (one kernel serves every k: mcq_search_topk_u16); norms = code_norms(codes) when not given (pass them in when searching repeatedly).
         -> (distances fp32 (*, k), indexes int64 (*, k)): |q - decode(codes[b])|^2 clamped at 0, nearest first, the lower
         position first among equal scores; with fewer than k stored vectors the tail is (+inf, -1).  Not differentiable.
         metric="ip": -> (similarities, indexes), <q, decode(codes[b])>, largest first; norms are neither needed nor formed.
