@@ -1,4 +1,4 @@
-"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h, include/mcq_probe.h, include/mcq_wide.h, include/mcq_rerank.h and include/mcq_code16.h).
+"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h, include/mcq_probe.h, include/mcq_wide.h, include/mcq_rerank.h, include/mcq_code16.h and include/mcq_shortlist.h).
 
 The library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950).  There
 is no CPU fallback: a missing library or a non-HIP tensor is an error.
@@ -147,6 +147,15 @@ CODE16_SIGNATURES = {
 }
 CODE16_SYMBOLS = tuple(CODE16_SIGNATURES)
 
+# include/mcq_shortlist.h, the companion header of the search over a shortlist, in the same form and in its order
+# (tests/test_search_shortlist_host.py parses that header and compares)
+SHORTLIST_SIGNATURES = {
+    "mcq_search_shortlist_workspace_bytes": _sig("z", "lliii"),
+    "mcq_search_shortlist": _sig("i", "plppliiiiplplppppzp"),
+    "mcq_search_shortlist_u16": _sig("i", "plppliiiiplplppppzp"),
+}
+SHORTLIST_SYMBOLS = tuple(SHORTLIST_SIGNATURES)
+
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
 MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
@@ -167,7 +176,7 @@ def lib():
                        "(hipcc --offload-arch=gfx950); quantization_amd has no CPU fallback")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES, **PROBE_SIGNATURES, **WIDE_SIGNATURES,
-                                      **RERANK_SIGNATURES, **CODE16_SIGNATURES}.items():
+                                      **RERANK_SIGNATURES, **CODE16_SIGNATURES, **SHORTLIST_SIGNATURES}.items():
         # an older build loaded through the A/B hook above may lack a symbol: it stays unbound, and calling it raises.
         # Without the hook a missing symbol fails here, at load
         if _ALT and not hasattr(L, name):

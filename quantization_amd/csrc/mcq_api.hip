@@ -7,6 +7,7 @@
 #include "../../include/mcq_wide.h"
 #include "../../include/mcq_rerank.h"
 #include "../../include/mcq_code16.h"
+#include "../../include/mcq_shortlist.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
 #include "mcq_loss_kernels.h"
@@ -17,6 +18,7 @@
 #include "mcq_range_kernels.h"
 #include "mcq_wide_kernels.h"
 #include "mcq_rerank_kernels.h"
+#include "mcq_shortlist_kernels.h"
 
 #include <cstdlib>
 #include <iterator>
@@ -1440,6 +1442,89 @@ int rerank(const void *queries, bool qhalf, long Q, const void *vectors, bool xh
     return launch_rc();
 }
 
+// ---- the search over a shortlist (mcq_shortlist_kernels.h; rules 36-39 of include/mcq_shortlist.h; mirrored by short_plan of
+// tests/search_shortlist_grid.py): one query per workgroup and `parts` parts of its shortlist row, cut by count of its steps
+// of kShortStep entries -- as many as fill the chip once at small Q, no more than the row has steps, capped as wide_plan caps
+// them for the merge.  A function of the call's shape alone.
+struct ShortPlan {
+    int parts;
+    size_t lds, ws_half;
+};
+
+ShortPlan short_plan(long Q, long S, int N, int K, int k) {
+    const long steps = (S + kShortStep - 1) / kShortStep;
+    const long cap = kWideMergeEntries / wide_half(k);
+    long parts = kShortTargetBlocks / (Q > 0 ? Q : 1);
+    parts = parts > cap ? cap : parts;
+    parts = parts > steps ? steps : parts;
+    parts = parts < 1 ? 1 : parts;
+    return {(int)parts, (size_t)short_lds_bytes(N * K, k), align256((size_t)Q * parts * k * 4)};   // scores, then positions
+}
+
+// rule 36's limits, in its order; 0 inside the domain.  code_bytes: 1, or 2 for mcq_search_shortlist_u16
+int short_domain(long Q, long S, long B, long Bs, int N, int K, int k, int metric, int code_bytes) {
+    constexpr long kLimit = 0x7fffffffL;                                   // sizes stay below 2^31 - 1
+    if (const int rc = code_bytes == 2 ? code16_domain(N, K, 1) : search_domain(N, K, 1)) return rc;
+    if (k > kWideMaxK) return MCQ_EUNSUPPORTED;
+    if (k < 1 || Q < 0 || S < 0 || B < 0 || Bs < 0) return MCQ_EINVAL;
+    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
+    if (Q >= kLimit || S >= kLimit || B >= kLimit || Bs >= kLimit) return MCQ_EUNSUPPORTED;
+    return 0;
+}
+
+template <typename T>
+int launch_short(const ShortPlan &p, hipStream_t st, const float *tables, int Q, const T *codes, const float *w, long B, int N,
+                 int K, int k, int metric, const int64_t *shortlist, int S, const int64_t *row_of, long Bs, const float *bias,
+                 float *ws_s, int *ws_i) {
+    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
+            constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
+            static bool allowed[64] = {};
+            if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_short<NN, M, T>),
+                                                 short_lds_bytes(kMaxRows, kWideMaxK)))
+                return rc;
+            hipLaunchKernelGGL((k_search_short<NN, M, T>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kWideWaves), p.lds, st,
+                               tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, shortlist, S, row_of, Bs, bias,
+                               ws_s, ws_i);
+            return launch_rc();
+        });
+    });
+}
+
+// both entries of include/mcq_shortlist.h.  T = uint16_t: mcq_search_shortlist_u16
+template <typename T>
+int search_shortlist(const float *tables, long Q, const T *codes, const float *w, long B, int N, int K, int k, int metric,
+                     const int64_t *shortlist, long S, const int64_t *row_of, long Bs, const float *bias, float *out_score,
+                     int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!row_of) Bs = B;                                                   // (positions are rows)
+    if (const int rc = short_domain(Q, S, B, Bs, N, K, k, metric, sizeof(T))) return rc;
+    if (Q > 0 && (!out_score || !out_index)) return MCQ_EINVAL;
+    if (Q == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ws_s = nullptr;
+    int *ws_i = nullptr;
+    int parts = 0;                                                        // lists per query; 0 (no candidate anywhere): the fill
+    if (S > 0 && B > 0 && Bs > 0) {
+        if (!tables || !codes || !shortlist || !workspace) return MCQ_EINVAL;
+        if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;              // (the inner product never reads w)
+        const int need = N * (int)sizeof(T) >= 16 ? 16 : N * (int)sizeof(T);   // a candidate's codes are loaded as one vector
+        if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
+        if (reinterpret_cast<uintptr_t>(shortlist) % 8 != 0 || reinterpret_cast<uintptr_t>(row_of) % 8 != 0) return MCQ_EINVAL;
+        if (reinterpret_cast<uintptr_t>(bias) % 4 != 0) return MCQ_EINVAL;
+        const ShortPlan p = short_plan(Q, S, N, K, k);
+        if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
+        ws_s = static_cast<float *>(workspace);                            // the workspace: scores, then positions
+        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
+        if (const int rc = launch_short<T>(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, shortlist, (int)S, row_of, Bs, bias,
+                                           ws_s, ws_i))
+            return rc;
+        parts = p.parts;
+    }
+    hipLaunchKernelGGL(k_search_wide_merge, dim3((unsigned)Q), dim3(64 * kWideWaves), 0, st, ws_s, ws_i, parts, k, out_score,
+                       out_index);
+    return launch_rc();
+}
+
 }  // namespace
 
 
@@ -2593,6 +2678,26 @@ int mcq_search_range_u16_fill(const float *tables, long Q, const uint16_t *codes
     const ListsIn li{list_offsets, L, probes, P, probe_bias};
     return range_fill(tables, Q, codes, w, B, N, K, metric, mask, probes ? &li : nullptr, thr, lims, out_score, out_index, capacity,
                       workspace, workspace_bytes, stream);
+}
+
+// ---- rules 36-39 (include/mcq_shortlist.h): the search over a shortlist
+size_t mcq_search_shortlist_workspace_bytes(long Q, long S, int N, int K, int k) {
+    if (Q <= 0 || S <= 0 || short_domain(Q, S, 0, 0, N, K, k, MCQ_SEARCH_L2, 2) != 0) return 256;
+    return 2 * short_plan(Q, S, N, K, k).ws_half;
+}
+
+int mcq_search_shortlist(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
+                         int metric, const int64_t *shortlist, long S, const int64_t *row_of, long Bs, const float *bias,
+                         float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
+    return search_shortlist(tables, Q, codes, w, B, N, K, k, metric, shortlist, S, row_of, Bs, bias, out_score, out_index, workspace,
+                            workspace_bytes, stream);
+}
+
+int mcq_search_shortlist_u16(const float *tables, long Q, const uint16_t *codes, const float *w, long B, int N, int K, int k,
+                             int metric, const int64_t *shortlist, long S, const int64_t *row_of, long Bs, const float *bias,
+                             float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
+    return search_shortlist(tables, Q, codes, w, B, N, K, k, metric, shortlist, S, row_of, Bs, bias, out_score, out_index, workspace,
+                            workspace_bytes, stream);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

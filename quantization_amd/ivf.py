@@ -31,6 +31,19 @@ A shortlist for an exact re-ranker (recall@100, recall@1000): search_lists stops
 rerank (quantization_amd/rerank.py, mcq_rerank) reads every candidate's raw row once; `vectors` stays in its original order,
 row_of = order maps a position of the store in list order to its row, and the -1 padding is skipped, not clamped.
 
+Two-stage quantisation (faiss's IndexRefine / IVFPQR): cheap codes in the inverted file find the candidates, a second, finer
+Quantizer over the SAME vectors -- 32 to 64 bytes a vector where the raw row takes 2 KB -- rescores them, and only then, if at
+all, is raw data touched.  The fine codes stay in the original order, as the raw vectors do:
+
+    fine_codes = fine.encode(x, as_bytes=True); fine_norms = fine.code_norms(fine_codes)      # once, original order
+    _, short = coarse.search_lists_wide(queries, codes, list_offsets, probes, 1000, norms=norms)        # positions in list order
+    dist, idx = fine.search_shortlist(queries, fine_codes, short, 100, norms=fine_norms, row_of=order)  # the fine codes' ADC
+    dist, idx = quantization_amd.rerank(queries, vectors, idx, 10, row_of=order)                        # optional: exact
+    original = torch.where(idx >= 0, order[idx.clamp(min=0)], idx)
+
+search_shortlist (quantization_amd/search.py, mcq_search_shortlist) reads the fine codes of the named rows and nothing else;
+its values are the bits fine.search reports for the same (query, vector), and its indexes stay positions in list order.
+
 Where the coarse centroids come from (k-means over a sample, a trained layer) is the caller's business."""
 import torch
 from torch import Tensor

@@ -1,6 +1,7 @@
 """The search over stored codes (not in the reference): top-k and range search, under a mask, list by list; include/mcq.h
 rules 1-20, include/mcq_residual.h rules 21-23, include/mcq_wide.h rules 24-27 (top-k past 64 neighbours) and
-include/mcq_code16.h rules 32-35 (stores of two-byte codes, codebook_size 512 and 1,024).  `SearchMixin` holds the methods `Quantizer` offers for it.  It has no state of its own: it uses num_codebooks,
+include/mcq_code16.h rules 32-35 (stores of two-byte codes, codebook_size 512 and 1,024) and include/mcq_shortlist.h rules
+36-39 (the search over a per-query shortlist).  `SearchMixin` holds the methods `Quantizer` offers for it.  It has no state of its own: it uses num_codebooks,
 codebook_size, dim, _prepared and _check_domain of the class it is mixed into.
 
 Each rule of the layer is written once here: the device check (_on_device), the metric check (check_metric), the choice of
@@ -38,7 +39,10 @@ _WIDE = {False: ("mcq_search_wide", "mcq_search_wide_workspace_bytes"),
 _TABLES16, _NORMS16 = "mcq_search_tables_u16", "mcq_code_norms_u16"
 _TOPK16 = ("mcq_search_topk_u16", "mcq_search_topk_u16_workspace_bytes")
 _RANGE16 = ("mcq_search_range_u16_count", "mcq_search_range_u16_fill", "mcq_search_range_u16_workspace_bytes")
-CODE16_MAX_ROWS = 16384         # num_codebooks * codebook_size at most: the 64 KiB of table a search kernel carries
+# the search over a shortlist (include/mcq_shortlist.h): the entry by "the store holds two-byte codes", and the workspace query
+_SHORT = {False: "mcq_search_shortlist", True: "mcq_search_shortlist_u16"}
+_SHORT_BYTES = "mcq_search_shortlist_workspace_bytes"
+CODE16_MAX_ROWS = 16384        # num_codebooks * codebook_size at most: the 64 KiB of table a search kernel carries
 WIDE_MAX_K = 1024               # search_wide and search_lists_wide: the largest k
 NARROW_MAX_K = 64               # search and search_lists: the largest k
 
@@ -496,6 +500,110 @@ class SearchMixin:
             scores, indexes = self._run(tables, flat, w, metric, mask, lists, k=k, wide=wide)
             values = _reported(scores, metric, qq)
         lead = queries.shape[:-1]
+        return values.reshape(*lead, k), indexes.reshape(*lead, k)
+
+    # ------------------------------------------------- the search over a shortlist
+    def _search_shortlist_scan(self, tables: Tensor, codes: Tensor, w: Tensor, shortlist: Tensor, k: int, metric: str = "l2",
+                               row_of: Tensor = None, bias: Tensor = None):
+        """tables fp32 (Q, N, K), codes uint8 or int16 (B, N) unpacked, w as _search_scan takes it under the metric,
+        shortlist int64 (Q, S), row_of None or int64 (Bs,), bias None or fp32 (Q, S) -> (scores fp32 (Q, k), positions int64
+        (Q, k)): rules 36-38 of include/mcq_shortlist.h (mcq_search_shortlist; mcq_search_shortlist_u16 over int16 codes).
+        The dtype of `codes` decides the entry, as in _run."""
+        N, K = self.num_codebooks, self.codebook_size
+        check_metric(metric)
+        if metric == "ip":
+            w = None
+        elif w is None:
+            raise ValueError(f"metric {metric!r} needs the per-candidate array")
+        _on_device(tables, codes, w, shortlist, row_of, bias)
+        tables = tables.detach().to(torch.float32).contiguous()
+        if w is not None:
+            w = w.detach().to(torch.float32).contiguous()
+        codes = codes.contiguous()
+        if codes.data_ptr() % 16:
+            codes = codes.clone()
+        shortlist = shortlist.detach().contiguous()
+        Q, B, S, dev = tables.shape[0], codes.shape[0], shortlist.shape[1], tables.device
+        two = codes.dtype == torch.int16
+        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and tuple(shortlist.shape) == (Q, S)
+        assert two or (codes.dtype == torch.uint8 and K <= 256)
+        assert shortlist.dtype == torch.int64 and (w is None or tuple(w.shape) == (B,))
+        if row_of is not None:
+            row_of = row_of.detach().contiguous()
+            assert row_of.dtype == torch.int64 and row_of.ndim == 1
+        if bias is not None:
+            bias = bias.detach().to(torch.float32).contiguous()
+            assert tuple(bias.shape) == (Q, S)
+        with torch.no_grad(), torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            ws = torch.empty(_entry(_SHORT_BYTES)(Q, S, N, K, int(k)), dtype=torch.uint8, device=dev)
+            scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+            indexes = torch.empty((Q, k), dtype=torch.int64, device=dev)
+            _call(_SHORT[two], tables.data_ptr(), Q, codes.data_ptr(), None if w is None else w.data_ptr(), B, N, K, int(k),
+                  METRICS[metric], shortlist.data_ptr(), S, None if row_of is None else row_of.data_ptr(),
+                  0 if row_of is None else row_of.numel(), None if bias is None else bias.data_ptr(), scores.data_ptr(),
+                  indexes.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        return scores, indexes
+
+    def search_shortlist(self, queries: Tensor, codes: Tensor, shortlist: Tensor, k: int, norms: Tensor = None,
+                         metric: str = "l2", rnorms: Tensor = None, row_of: Tensor = None, bias: Tensor = None):
+        """search() over the candidates a per-query shortlist names, from the codes alone: nothing is decoded, nothing of
+        size (Q, S, dim) is made, and the store is read only at the rows the shortlists name (mcq_search_shortlist).
+        The second stage of a two-stage quantisation (the codes of a finer quantizer over the same vectors rescore what
+        cheap codes found; quantization_amd.ivf has the recipe), the scorer behind a graph index or any other candidate
+        generator, and a filter given per query as a list of ids.
+        queries (*, dim) fp32 or fp16; codes, norms and rnorms exactly as search takes them (uint8, packed 16-entry codes,
+        or the int16 store of pack_codes with codebook_size > 256; norms / rnorms are made from the codes when absent: pass
+        them in when searching repeatedly).
+        shortlist (*, S) int64 or int32 with the leading dimensions of queries -- what the searches return as indexes.  An
+        entry p with 0 <= p < Bs names a candidate, every other value none (-1 is the padding; B, 2**40 and -7 likewise);
+        Bs is row_of.numel() with row_of, else B; a position named twice in a row is a candidate twice.
+        row_of: optional int64 (Bs,): candidate p is scored with codes[row_of[p]] (and norms[row_of[p]]), and an entry
+        outside [0, B) makes p no candidate.  This is build_lists' `order`: a shortlist of positions in list order against a
+        store kept in the original order.  Reported indexes stay the shortlist's positions p.
+        bias: optional floating (*, S), one value per shortlist slot, added to the table sum of that slot's candidate before
+        the metric finishes the score (probe_bias per candidate: residual codes whose lists differ within a row).
+        1 <= k <= 1,024; k may exceed S.
+        -> (values fp32 (*, k), indexes int64 (*, k)): search()'s values for the same (query, stored vector), bit for bit,
+        its order (nearest or most similar first, the lower position first among equals), its clamping, and its tail for a
+        row with fewer than k candidates: (+inf, -1) under "l2", (-inf, -1) under the other two.
+        Not differentiable; no CPU fallback (McqError); argument errors are ValueErrors raised before anything is launched."""
+        check_metric(metric)
+        if not isinstance(queries, Tensor) or queries.ndim < 1 or queries.shape[-1] != self.dim:
+            raise ValueError(f"queries: a (*, {self.dim}) tensor, not {tuple(getattr(queries, 'shape', ()))}")
+        lead = tuple(queries.shape[:-1])
+        if not isinstance(shortlist, Tensor) or shortlist.dtype not in (torch.int64, torch.int32) or shortlist.ndim < 1 or \
+                tuple(shortlist.shape[:-1]) != lead:
+            raise ValueError(f"shortlist: an int64 or int32 {lead} + (S,) tensor, not {getattr(shortlist, 'dtype', type(shortlist))} "
+                             f"{tuple(getattr(shortlist, 'shape', ()))}")
+        if row_of is not None and (not isinstance(row_of, Tensor) or row_of.dtype != torch.int64 or row_of.ndim != 1):
+            raise ValueError(f"row_of: an int64 (Bs,) tensor, not {getattr(row_of, 'dtype', type(row_of))} "
+                             f"{tuple(getattr(row_of, 'shape', ()))}")
+        if bias is not None and (not isinstance(bias, Tensor) or not bias.dtype.is_floating_point or
+                                 tuple(bias.shape) != tuple(shortlist.shape)):
+            raise ValueError(f"bias: a floating {tuple(shortlist.shape)} tensor, one value per entry of shortlist, not "
+                             f"{getattr(bias, 'dtype', type(bias))} {tuple(getattr(bias, 'shape', ()))}")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= WIDE_MAX_K:
+            raise ValueError(f"k = {k!r}: an integer, 1 <= k <= {WIDE_MAX_K}")
+        if not isinstance(codes, Tensor) or codes.ndim < 1:
+            raise ValueError("codes: a (B, num_codebooks) tensor of stored codes")
+        if self.codebook_size > 256 and codes.dtype == torch.uint8:
+            raise ValueError(f"codes: with codebook_size {self.codebook_size} the search takes the int16 store that pack_codes "
+                             f"makes of encode(..., as_bytes=False), not uint8 codes")
+        limit = (1 << 31) - 1
+        if shortlist.shape[-1] >= limit or (row_of is not None and row_of.numel() >= limit):
+            raise ValueError("shortlist and row_of: fewer than 2^31 - 1 entries")
+        S = int(shortlist.shape[-1])
+        with torch.no_grad():
+            flat = self._unpacked_codes(codes)
+            w = self._metric_array(metric, flat, norms, rnorms)
+            tables = self.search_tables(queries)
+            q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
+            qq = (q2d * q2d).sum(dim=1, keepdim=True)
+            short = shortlist.detach().reshape(-1, S).to(torch.int64)
+            b2d = None if bias is None else bias.detach().reshape(-1, S)
+            scores, indexes = self._search_shortlist_scan(tables, flat, w, short, k, metric, row_of, b2d)
+            values = _reported(scores, metric, qq)
         return values.reshape(*lead, k), indexes.reshape(*lead, k)
 
     # ------------------------------------------------- range search over stored codes
