@@ -15,8 +15,13 @@
  *    NULL = the default stream) and returns immediately: no allocation, no
  *    synchronisation, re-entrant per (device, stream).  Process-wide state is limited to
  *    read-only tuning hooks (environment variables latched on first use; DESIGN.md lists
- *    them; none changes a result) and a thread-local launch counter
- *    (mcq_last_encode_launches);
+ *    them; none changes a result), a thread-local launch counter
+ *    (mcq_last_encode_launches) and, per device, one side stream with two events: an encode of a
+ *    large batch may run its chunks on two LANES, the caller's stream and that side stream.  It forks
+ *    behind everything `stream` holds at the call and joins before it returns, so `stream` alone
+ *    orders inputs, workspace and results as if every launch were on it; concurrent callers on one
+ *    device are serialised over that section.  A capturing stream, or a device where the side stream
+ *    cannot be made, gets the one-stream sequence (include/mcq_lanes.h);
  *  - return value: 0 = ok; MCQ_E* < 0 = rejected argument; > 0 = hipError_t of a
  *    failed launch.  Nothing is thrown across the boundary.
  *  - supported domain: codebook_size K a power of two in [16, 1024], num_codebooks N
@@ -542,7 +547,9 @@ int mcq_last_encode_launches(void);
 
 /* Measurement tool (bench.py): runs the encode exactly as mcq_encode enqueues it -- the same launches, nothing switched off --
  * once per category of launch, with HIP events on `stream` round the launches of that category only (events round every launch of
- * one encode stretch it by a tenth); synchronises and allocates the output of those encodes.
+ * one encode stretch it by a tenth); synchronises and allocates the output of those encodes.  A batch that mcq_encode runs on two
+ * lanes is timed as the same chunks on the same workspace shares, one after the other on `stream`: the launches are the shipped
+ * ones, their overlap across lanes is not part of what is timed.
  * ms_out[c] / launches_out[c] (c < cap) receive the summed milliseconds and the number of timed intervals of category c,
  * mcq_profile_category_name(c) its name (NULL past the last one).  Returns the number of categories, or an error code.   */
 int mcq_profile_encode(const float *x, long B, const void *prepared, float lscale_exp, int N, int K,

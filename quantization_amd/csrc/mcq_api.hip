@@ -8,6 +8,7 @@
 #include "../../include/mcq_rerank.h"
 #include "../../include/mcq_code16.h"
 #include "../../include/mcq_shortlist.h"
+#include "../../include/mcq_lanes.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
 #include "mcq_loss_kernels.h"
@@ -19,9 +20,11 @@
 #include "mcq_wide_kernels.h"
 #include "mcq_rerank_kernels.h"
 #include "mcq_shortlist_kernels.h"
+#include "mcq_lanes.h"
 
 #include <cstdlib>
 #include <iterator>
+#include <mutex>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -127,8 +130,10 @@ size_t workspace_per_vector(int N, int K, int D) {
     return 4 * cb * (size_t)N + 8 + 8 + 4 * (size_t)N + 4 * (size_t)N * K + (size_t)tf_levels(N) * N * (16 * cb + 2 * 16 + 4 * 16) + 64 +
            2 * 4 * tf_tab_floats(N, K) + 4 * (size_t)fix_round_cols(D) + 4 + 4 * (size_t)N * N;
 }
-// alignment of the carved arrays + the rows the limb planes are padded by (to a multiple of 128)
-size_t workspace_slack(int D) { return 48 * 256 + (size_t)kFixTile * (4 * (size_t)fix_round_cols(D) + 4); }
+// what one lane's share holds besides its vectors: alignment of the carved arrays + the rows the limb planes are padded by (to a
+// multiple of 128); and what the whole workspace does (mcq_lanes.h: two such shares, a spare vector, the second share's alignment)
+size_t lane_slack(int D) { return 48 * 256 + (size_t)kFixTile * (4 * (size_t)fix_round_cols(D) + 4); }
+size_t workspace_slack(int N, int K, int D) { return plan_slack(workspace_per_vector(N, K, D), lane_slack(D)); }
 
 // default chunk: 65,536 vectors, fewer when a vector's share of the workspace is large (N >= 32), so that the workspace
 // mcq_encode_workspace_bytes asks for stays near 2 GB
@@ -243,6 +248,7 @@ struct Prof {
 };
 
 thread_local int g_last_launches = 0;
+thread_local int g_last_lanes = 0;       // streams the last encode of this thread enqueued on (mcq_last_encode_lanes)
 
 #define MCQ_LAUNCH_CHECK()                               \
     do {                                                 \
@@ -311,6 +317,44 @@ int allow_dynamic_lds(bool (&allowed)[64], const void *kernel, int bytes) {
         allowed[dev] = true;
     }
     return 0;
+}
+
+// What the encode keeps per device, made once under the record's mutex: the side stream and the fork / join events of the
+// second lane (run_encode_t), and the LDS opt-ins of the LDS-resident pass (launch_pass16).  A device the runtime does not name
+// (or one past the table) has no record: no second lane there, and the opt-ins are repeated on every call.
+struct DeviceRec {
+    std::mutex mu;                  // guards the lane fields; held over the two-lane section of an encode (fork .. join)
+    bool lanes_tried = false, lanes_ok = false;
+    hipStream_t side = nullptr;     // lane 1
+    hipEvent_t fork = nullptr, join = nullptr;
+    std::mutex lds_mu;              // guards the opt-in flags (taken inside the two-lane section: a mutex of its own)
+    bool pass16_ok = false, pass16_probe_ok = false;
+};
+DeviceRec g_device[64];
+DeviceRec *device_rec() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return (dev >= 0 && dev < 64) ? &g_device[dev] : nullptr;
+}
+
+// r.mu held.  The side stream does not synchronise with the null stream (the events order it) and the events carry no
+// timestamps.  A failure is remembered (not retried on every call) and leaves no error behind: the encode runs on one lane
+bool lanes_ready(DeviceRec &r) {
+    if (r.lanes_tried) return r.lanes_ok;
+    r.lanes_tried = true;
+    if (hipStreamCreateWithFlags(&r.side, hipStreamNonBlocking) == hipSuccess &&
+        hipEventCreateWithFlags(&r.fork, hipEventDisableTiming) == hipSuccess &&
+        hipEventCreateWithFlags(&r.join, hipEventDisableTiming) == hipSuccess) {
+        r.lanes_ok = true;
+        return true;
+    }
+    (void)hipGetLastError();
+    if (r.join) (void)hipEventDestroy(r.join);
+    if (r.fork) (void)hipEventDestroy(r.fork);
+    if (r.side) (void)hipStreamDestroy(r.side);
+    r.side = nullptr; r.fork = r.join = nullptr;
+    (void)hipGetLastError();
+    return false;
 }
 
 // The launches of its scope as one interval of category `cat` of the profiler, if there is one: `{ Timed t(prof, CAT); launch }`
@@ -599,6 +643,24 @@ inline long lazy_tables_min() {
     const char *v = getenv("MCQ_LAZY_TABLES_MIN");
     return v ? atol(v) : kLazyTablesMin;
 }
+// Batches of at least encode_lanes_min() vectors are encoded as chunks on TWO lanes (mcq_lanes.h), when encode_lanes() allows a
+// second one.  MCQ_ENCODE_LANES=1: one lane at the one-lane chunk size whatever the batch (same-library A/B), 2: a second lane;
+// MCQ_ENCODE_LANES_MIN=<n> moves the threshold (0: any batch).  Both read per call
+// (unprofiled bench pairs, 8 x 256, dim 512, three each, one lane against two: 8,192 vectors 0.763-0.766 against 0.783-0.788 ms --
+// the fork and join lose --, 16,384 1.306-1.315 against 1.300-1.310, overlap, 32,768 2.372-2.380 against 2.300-2.319, 65,536
+// 4.531-4.558 against 4.346-4.467 and 131,072 9.042-9.120 against 8.761-8.803, ranges apart: profiles/r27_ab_two_lanes.txt.  The
+// halves of 32,768 are chunks of 16,384: still at kErDenseMin and kLazyTablesMin)
+constexpr int kEncodeLanes = 2;
+constexpr long kEncodeLanesMin = 32768;
+inline int encode_lanes() {
+    const char *v = getenv("MCQ_ENCODE_LANES");
+    const int n = v ? atoi(v) : kEncodeLanes;
+    return n >= 2 ? 2 : 1;
+}
+inline long encode_lanes_min() {
+    const char *v = getenv("MCQ_ENCODE_LANES_MIN");
+    return v ? atol(v) : kEncodeLanesMin;
+}
 
 // the combines of one refinement pass
 template <typename CT>
@@ -798,15 +860,28 @@ int launch_chunk_start(const EncodeCall &c, const WorkspaceT<CT> &w, const float
 int launch_pass16(const EncodeCall &c, const WorkspaceT<uint8_t> &w, long Bc, const ChunkOut &out, uint8_t *dump = nullptr,
                   int max_wgs = 0) {
     // the first pass16 call on a device opts BOTH shapes in: the other shape's first call may come inside a captured stream
-    static bool allowed16[64] = {}, allowed8[64] = {};
-    int rc = allow_dynamic_lds(allowed16, reinterpret_cast<const void *>(&k_tf_pass16<16>), p16_lds_bytes<16>());
-    if (rc == 0) rc = allow_dynamic_lds(allowed8, reinterpret_cast<const void *>(&k_tf_pass16<8>), p16_lds_bytes<8>());
-    if (rc == 0 && dump) {
-        static bool probe16[64] = {}, probe8[64] = {};
-        rc = allow_dynamic_lds(probe16, reinterpret_cast<const void *>(&k_tf_pass16_probe<16>), p16_lds_bytes<16>());
-        if (rc == 0) rc = allow_dynamic_lds(probe8, reinterpret_cast<const void *>(&k_tf_pass16_probe<8>), p16_lds_bytes<8>());
+    // (flags of the device's record, set under its mutex: two host threads, or the two lanes' first chunks, find them consistent)
+    auto opt_in = [](const void *k16, const void *k8) {
+        const hipError_t e16 = hipFuncSetAttribute(k16, hipFuncAttributeMaxDynamicSharedMemorySize, p16_lds_bytes<16>());
+        if (e16 != hipSuccess) return (int)e16;
+        return (int)hipFuncSetAttribute(k8, hipFuncAttributeMaxDynamicSharedMemorySize, p16_lds_bytes<8>());
+    };
+    {
+        DeviceRec *const r = device_rec();
+        std::unique_lock<std::mutex> lock;
+        if (r) lock = std::unique_lock<std::mutex>(r->lds_mu);
+        if (!r || !r->pass16_ok) {
+            if (const int rc = opt_in(reinterpret_cast<const void *>(&k_tf_pass16<16>), reinterpret_cast<const void *>(&k_tf_pass16<8>)))
+                return rc;
+            if (r) r->pass16_ok = true;
+        }
+        if (dump && (!r || !r->pass16_probe_ok)) {
+            if (const int rc = opt_in(reinterpret_cast<const void *>(&k_tf_pass16_probe<16>),
+                                      reinterpret_cast<const void *>(&k_tf_pass16_probe<8>)))
+                return rc;
+            if (r) r->pass16_probe_ok = true;
+        }
     }
-    if (rc) return rc;
     Pass16Args a;
     a.G = c.P.G; a.XC = w.XC; a.xx = w.xx; a.Q = c.P.Q; a.idx = w.idx; a.B = Bc; a.iters = c.iters;
     a.out_i64 = out.pack == 1 ? out.i64 : nullptr;
@@ -937,12 +1012,35 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
     if (sizeof(CT) > 1 && (out_u8 != nullptr || codes_also != nullptr)) return MCQ_EINVAL;
     if (B == 0) return 0;
     if (!x || !prepared || !workspace) return MCQ_EINVAL;
-    const size_t per = workspace_per_vector(N, K, D), slack = workspace_slack(D);
-    if (workspace_bytes < slack + per) return MCQ_EWORKSPACE;
-    long chunk = (long)((workspace_bytes - slack) / per);
-    if (chunk > B) chunk = B;
-    if (chunk < B && chunk < 128) return MCQ_EWORKSPACE;
-    if (chunk < B) chunk &= ~127L;
+    const size_t per = workspace_per_vector(N, K, D);
+    // The plan: one lane, or two for a batch of encode_lanes_min() vectors or more -- unless the caller's stream is capturing (a
+    // fork inside a captured graph makes parallel branches), which takes the one-lane sequence as it always was
+    ChunkPlan plan;
+    bool two = encode_lanes() == 2 && B >= encode_lanes_min();
+    if (two && prof == nullptr) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); two = false; }
+        else if (cap != hipStreamCaptureStatusNone) two = false;
+    }
+    if (two) two = plan_two_lanes(B, workspace_bytes, per, lane_slack(D), &plan);
+    if (!two && !plan_one_lane(B, workspace_bytes, per, lane_slack(D), &plan)) return MCQ_EWORKSPACE;
+    // Fork: lane 1 starts behind everything the caller's stream holds now -- the frames, `prepared`, earlier users of the
+    // workspace.  The profiler keeps its one stream: the same chunks on the same shares, one after the other (include/mcq.h)
+    DeviceRec *rec = nullptr;
+    std::unique_lock<std::mutex> lanes_lock;
+    if (two && prof == nullptr && plan.chunks >= 2 && (rec = device_rec()) != nullptr) {
+        lanes_lock = std::unique_lock<std::mutex>(rec->mu);
+        if (!lanes_ready(*rec) || hipEventRecord(rec->fork, st) != hipSuccess || hipStreamWaitEvent(rec->side, rec->fork, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            lanes_lock.unlock();
+            rec = nullptr;
+        }
+    }
+    if (two && prof == nullptr && rec == nullptr && plan.chunks >= 2 &&
+        !plan_one_lane(B, workspace_bytes, per, lane_slack(D), &plan))      // no second stream: today's sequence
+        return MCQ_EWORKSPACE;
+    const hipStream_t lane_st[kMaxLanes] = {st, rec ? rec->side : st};
+    g_last_lanes = rec ? 2 : 1;
     const EncodeCall c{prepared_view(prepared, N, K, D), lscale, N, K, D, iters, flags, st, prof};
     const int pack = (out_u8 != nullptr && K == 16 && N >= 2) ? 2 : 1;
     // fixed-point skipping (the default; MCQ_ENCODE_ALL_PASSES turns it off): vectors whose indexes a pass leaves unchanged
@@ -952,36 +1050,52 @@ int run_encode_t(const float *x, long B, const void *prepared, float lscale, int
     const bool want_skip = (flags & MCQ_ENCODE_ALL_PASSES) == 0 && iters >= 3;     // (with two passes the second one holds ~every vector)
     const bool use_p16 = sizeof(CT) == 1 && K == 16 && (N == 16 || N == 8) && iters > 0 && prof == nullptr && pass16_enabled();
 
-    for (long lo = 0; lo < B; lo += chunk) {
-        const long Bc = (B - lo < chunk) ? (B - lo) : chunk;
-        const WorkspaceT<CT> w = carve<CT>(workspace, Bc, N, K, D);
+    // one chunk on its lane: `cl` is the call with the lane's stream, `ws` the lane's share
+    auto encode_chunk = [&](const EncodeCall &cl, void *ws, long lo, long Bc) -> int {
+        const WorkspaceT<CT> w = carve<CT>(ws, Bc, N, K, D);
         const ChunkOut out{out_u8 ? out_u8 + lo * (N / pack) : nullptr, out_i64 ? out_i64 + lo * N : nullptr,
                            codes_also ? codes_also + lo * N : nullptr, pack};
         const float *xc = (flags & MCQ_ENCODE_X_FP16) ? reinterpret_cast<const float *>(reinterpret_cast<const uint16_t *>(x) + lo * D)
                                                       : x + lo * D;
-        if (const int rc = launch_chunk_start<CT>(c, w, xc, Bc, init_idx ? init_idx + lo * N : nullptr,
+        if (const int rc = launch_chunk_start<CT>(cl, w, xc, Bc, init_idx ? init_idx + lo * N : nullptr,
                                                   logits_out ? logits_out + lo * N * K : nullptr))
             return rc;
         bool left = false;      // the codes are in the caller's arrays already; otherwise in w.idx, for k_finalize
         if constexpr (sizeof(CT) == 1) {
             if (use_p16) {
-                if (const int rc = launch_pass16(c, w, Bc, out)) return rc;
+                if (const int rc = launch_pass16(cl, w, Bc, out)) return rc;
                 left = out.pack == 1;
             }
         }
         if (!use_p16) {
             const bool skip = want_skip && Bc >= skip_min_batch();
-            if (const int rc = run_passes<CT>(c, w, Bc, skip, out)) return rc;
+            if (const int rc = run_passes<CT>(cl, w, Bc, skip, out)) return rc;
             left = skip || (iters > 0 && N >= 2);      // every vector left through k_compact or the last emit / the last emit
         }
-        if (left) continue;
+        if (left) return 0;
         const long outn = out.i64 ? Bc * N : Bc * (N / pack);
         Timed t(prof, CAT_TAIL);
-        hipLaunchKernelGGL(k_finalize<CT>, dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, st, w.idx, Bc, N, pack, out.u8, out.i64,
+        hipLaunchKernelGGL(k_finalize<CT>, dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, cl.st, w.idx, Bc, N, pack, out.u8, out.i64,
                            out.also);
         MCQ_LAUNCH_CHECK();
+        return 0;
+    };
+    // chunk i on lane i mod lanes; between fork and join the lanes never wait for each other
+    int rc = 0;
+    for (long i = 0; i < plan.chunks && rc == 0; ++i) {
+        const int lane = plan.lane_of(i);
+        EncodeCall cl = c;
+        cl.st = lane_st[lane];
+        rc = encode_chunk(cl, static_cast<char *>(workspace) + plan.lane_off[lane], plan.first_of(i), plan.rows_of(i, B));
     }
-    return 0;
+    // Join, also after a failed launch: from here the caller's stream alone orders the codes and the workspace.  A join that cannot
+    // be enqueued is made on the host
+    if (rec != nullptr && (hipEventRecord(rec->join, rec->side) != hipSuccess || hipStreamWaitEvent(st, rec->join, 0) != hipSuccess)) {
+        const hipError_t e = hipGetLastError();
+        (void)hipStreamSynchronize(rec->side);
+        if (rc == 0) rc = e != hipSuccess ? (int)e : MCQ_EINVAL;
+    }
+    return rc;
 }
 
 int run_encode(const float *x, long B, const void *prepared, float lscale, int N, int K, int D, int iters,
@@ -1919,7 +2033,7 @@ int mcq_prepare_params(const float *centers, const float *centers_scale, const f
 size_t mcq_encode_workspace_bytes(long B, int N, int K, int D) {
     if (B <= 0 || N <= 0 || K <= 0 || D <= 0 || !domain_ok(N, K, D)) return 48 * 256;
     const long dc = default_chunk(N, K, D), chunk = B < dc ? B : dc;
-    return workspace_slack(D) + workspace_per_vector(N, K, D) * (size_t)chunk;
+    return workspace_slack(N, K, D) + workspace_per_vector(N, K, D) * (size_t)chunk;
 }
 
 int mcq_encode(const float *x, long B, const void *prepared, float lscale_exp, int N, int K, int D, int refine_iters,
@@ -2119,6 +2233,25 @@ int mcq_test_pass_layout(long B, int N, int K, int D, size_t *out, int cap) {
     return n;
 }
 
+// include/mcq_lanes.h: the chunk plan run_encode_t takes for this batch and workspace (host only: nothing touches a device, so
+// neither a capturing stream nor a missing side stream is seen here)
+int mcq_test_chunk_plan(long B, int N, int K, int D, size_t workspace_bytes, int lanes, long *out, int cap) {
+    if (!domain_ok(N, K, D)) return domain_err(N, K, D);
+    if (B < 1 || lanes < 0 || lanes > kMaxLanes || !out || cap < 0) return MCQ_EINVAL;
+    const size_t per = workspace_per_vector(N, K, D);
+    ChunkPlan p;
+    bool two = lanes == 0 ? (encode_lanes() == 2 && B >= encode_lanes_min()) : lanes == 2;
+    if (two) two = plan_two_lanes(B, workspace_bytes, per, lane_slack(D), &p);
+    if (!two && !plan_one_lane(B, workspace_bytes, per, lane_slack(D), &p)) return MCQ_EWORKSPACE;
+    const long head[MCQ_TEST_CHUNK_PLAN_HEAD] = {p.lanes, p.chunk, p.chunks, (long)p.lane_off[0], (long)p.lane_off[1], (long)p.lane_bytes};
+    for (int i = 0; i < MCQ_TEST_CHUNK_PLAN_HEAD && i < cap; ++i) out[i] = head[i];
+    for (long i = 0; i < p.chunks && MCQ_TEST_CHUNK_PLAN_HEAD + 3 * i + 2 < cap; ++i) {
+        long *const o = out + MCQ_TEST_CHUNK_PLAN_HEAD + 3 * i;
+        o[0] = p.lane_of(i); o[1] = p.first_of(i); o[2] = p.rows_of(i, B);
+    }
+    return MCQ_TEST_CHUNK_PLAN_HEAD;
+}
+
 // include/mcq_probe.h: one refinement pass of B vectors as one chunk (test_pass, beside run_encode)
 int mcq_test_pass(const float *x, long B, const void *prepared, int N, int K, int D, const int64_t *idx_in, int64_t *idx_out,
                   const int *nact, const int *map, unsigned flags, void *workspace, size_t workspace_bytes, void *stream) {
@@ -2129,7 +2262,7 @@ int mcq_test_pass(const float *x, long B, const void *prepared, int N, int K, in
     if (B == 0) return 0;
     if (!x || !prepared || !idx_in || !idx_out || !workspace) return MCQ_EINVAL;
     if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return MCQ_EINVAL;
-    const size_t per = workspace_per_vector(N, K, D), slack = workspace_slack(D);
+    const size_t per = workspace_per_vector(N, K, D), slack = workspace_slack(N, K, D);
     if (workspace_bytes < slack + per || (long)((workspace_bytes - slack) / per) < B) return MCQ_EWORKSPACE;     // the encode's chunk rule
     const EncodeCall c{prepared_view(prepared, N, K, D), 1.0f, N, K, D, 1, 0u, static_cast<hipStream_t>(stream), nullptr};
     const bool capped = (flags & MCQ_TEST_PASS_CAPPED) != 0;
@@ -2166,7 +2299,7 @@ int mcq_test_pass16(const float *x, long B, const void *prepared, int N, int D, 
     if (B == 0) return 0;
     if (!x || !prepared || !idx_in || !idx_out || !workspace) return MCQ_EINVAL;
     if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0 || reinterpret_cast<uintptr_t>(dump) % 4 != 0) return MCQ_EINVAL;
-    const size_t per = workspace_per_vector(N, K, D), slack = workspace_slack(D);
+    const size_t per = workspace_per_vector(N, K, D), slack = workspace_slack(N, K, D);
     if (workspace_bytes < slack + per || (long)((workspace_bytes - slack) / per) < B) return MCQ_EWORKSPACE;     // the encode's chunk rule
     if (dump && dump_bytes / kP16Rec / (size_t)iters < (size_t)B) return MCQ_EWORKSPACE;
     const EncodeCall c{prepared_view(prepared, N, K, D), 1.0f, N, K, D, iters, 0u, static_cast<hipStream_t>(stream), nullptr};
@@ -2713,6 +2846,7 @@ int mcq_search_pack_mask(const uint8_t *flags, long B, uint64_t *mask_out, void 
 }
 
 int mcq_last_encode_launches(void) { return g_last_launches; }
+int mcq_last_encode_lanes(void) { return g_last_lanes; }
 
 int mcq_test_select(const float *scores, int cases, int per_lane, int cnt, float *out_v, int *out_p, void *stream) {
     if (!scores || !out_v || !out_p || cases <= 0 || cnt < 1 || cnt > 64) return MCQ_EINVAL;
