@@ -459,7 +459,20 @@ int launch_logits(const int8_t *xf, const int *xe, long B, const Prepared &P, in
 // the active vectors (capped: later passes of fixed-point skipping, where most workgroups of the full grid would find no vector
 // and still cost their dispatch, about 0.2 ns each)
 constexpr unsigned kCapStage0 = 32768, kCapWave = 65536;     // workgroups of four waves / of one wave
-inline unsigned pass_grid(unsigned full, bool capped, unsigned cap) { return (capped && full > cap) ? cap : full; }
+// MCQ_PASS_CAP_STAGE0=<n> / MCQ_PASS_CAP_WAVE=<n> move the caps (read per call, rounded down to a multiple of 8, at least 8): the
+// tests make a workgroup loop many times over a few dozen vectors with them, the A/B runs try other caps
+inline unsigned pass_cap(const char *name, unsigned dflt) {
+    const char *v = getenv(name);
+    if (!v) return dflt;
+    const long n = atol(v);
+    return n < 8 ? 8u : n > 0x7ffffff8L ? 0x7ffffff8u : (unsigned)n & ~7u;
+}
+inline unsigned cap_stage0() { return pass_cap("MCQ_PASS_CAP_STAGE0", kCapStage0); }
+inline unsigned cap_wave() { return pass_cap("MCQ_PASS_CAP_WAVE", kCapWave); }
+// The looping (STRIDED) form of a kernel only where the grid IS capped: a capped pass whose full grid fits under the cap takes the
+// dense form, whose workgroups past the active vectors return at once (full == cap used to run the loop for one iteration each)
+inline bool pass_strided(unsigned full, bool capped, unsigned cap) { return capped && full > cap; }
+inline unsigned pass_grid(unsigned full, bool capped, unsigned cap) { return pass_strided(full, capped, cap) ? cap : full; }
 
 // Stage 0 of a pass.  Four or more 16-entry codebooks: four codebooks per wave, rank-in-row selection (k_tf_stage0_k16: its lists
 // of kc[0] == 8 fit a row, so k_tf_stage0<16, N> exists for N <= 2 only).  No shape past kMaxRows rows is stamped either.
@@ -467,13 +480,14 @@ template <typename CT>
 int launch_tf_stage0(int K, int N, const float *G, const float *XC, const CT *idx, const float *R, const float *Q, long B, int keep,
                      CT *ent, float *S, CT *fin, const int *nact, const int *map, hipStream_t st, bool capped) {
     const unsigned vgrid = (unsigned)(((B + 3) / 4) * N);
-    const dim3 grid(pass_grid(vgrid, capped, kCapStage0)), block(256);
+    const unsigned cap = cap_stage0();
+    const dim3 grid(pass_grid(vgrid, capped, cap)), block(256);
     auto with_k = [&](auto kk) {
         constexpr int KK = kk;
         return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
             constexpr int NN = nn;
             if constexpr ((KK == 16 && NN >= 4) || KK * NN > kMaxRows) return MCQ_EUNSUPPORTED;
-            else return pick_bool(capped, [&](auto strided) {
+            else return pick_bool(pass_strided(vgrid, capped, cap), [&](auto strided) {
                 constexpr bool STRIDED = strided;
                 hipLaunchKernelGGL((k_tf_stage0<KK, NN, STRIDED>), grid, block, 0, st, G, XC, idx, R, Q, B, keep, ent, S, fin, nact, map, vgrid);
                 return counted_launch_rc();
@@ -565,13 +579,14 @@ int launch_tf_comb(int kh, int kc, const float *E, const TfLists &L, long B, int
                    CT *fin, const int *nact, hipStream_t st, bool capped) {
     // (capped: the last combine only; the others of more than 8 codebooks keep their full grid)
     if (fin == nullptr) capped = false;
-    const dim3 grid(pass_grid((unsigned)(B * (N >> (v + 1))), capped, kCapWave)), block(64);
+    const unsigned full = (unsigned)(B * (N >> (v + 1))), cap = cap_wave();
+    const dim3 grid(pass_grid(full, capped, cap)), block(64);
     return pick_pair<kTfCombLists>(kh, kc, [&](auto a, auto c) {
         return pick_bool(fin != nullptr, [&](auto last) {
             constexpr int KH = decltype(a)::value, KC = decltype(c)::value;
             constexpr bool LAST = last;
             if constexpr (!tf_comb_reached<CT>(KH, KC, LAST)) return MCQ_EUNSUPPORTED;
-            else return pick_bool(capped, [&](auto strided) {
+            else return pick_bool(pass_strided(full, capped, cap), [&](auto strided) {
                 constexpr bool STRIDED = strided;
                 if constexpr (STRIDED && !LAST) return MCQ_EUNSUPPORTED;      // (not reached: capped only with fin)
                 else {
@@ -669,6 +684,7 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
     const bool small = (K == 16);
     const int nlev = tf_levels(N);
     const dim3 wave(64);
+    const unsigned cap = cap_wave();
     {   // level 0: single codebooks
         const int keep = (N == 2) ? 1 : L.kc[1];
         CT *fin = (N == 2) ? idx_new : nullptr;
@@ -679,9 +695,9 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
             if constexpr (sizeof(CT) == 1 && KC == 16) {
                 // lists of 16 one-byte entries: the slot-major kernel (a 16-lane group of a gather = one table row: a fifth faster than
                 // the lane-major one, profiles/r06_ab_pair0_slot_major.txt)
-                return pick_bool(capped, [&](auto strided) {
+                return pick_bool(pass_strided(grid.x, capped, cap), [&](auto strided) {
                     constexpr bool STRIDED = strided;
-                    hipLaunchKernelGGL(k_tf_pair0s<STRIDED>, dim3(pass_grid(grid.x, capped, kCapWave)), wave, 0, st, G, idx_cur, w.E, L, B, N,
+                    hipLaunchKernelGGL(k_tf_pair0s<STRIDED>, dim3(pass_grid(grid.x, capped, cap)), wave, 0, st, G, idx_cur, w.E, L, B, N,
                                        K, keep, fin, nact);
                     return counted_launch_rc();
                 });
@@ -708,16 +724,20 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
             const int ntab1 = (N >> 3) * 4, ntab3 = (N == 16) ? 16 : 1, per3 = (N == 16) ? 4 : 1;
             const unsigned pair_blocks = (unsigned)(B * (N / 4)), tab_blocks = (unsigned)(B * ntab1);
             const unsigned vgrid = tab_blocks + (N == 16 ? (unsigned)(B * ntab3) : 0u);
-            const int rc = pick_bool(capped, [&](auto strided) {
+            // (each launch takes the looping form by its own grid: at 32,768 vectors of 8 codebooks the level-1 combines fit the cap
+            // and the tables do not)
+            int rc = pick_bool(pass_strided(pair_blocks, capped, cap), [&](auto strided) {
                 constexpr bool STRIDED = strided;
-                {
-                    Timed t(prof, CAT_LEVEL1);
-                    hipLaunchKernelGGL((k_tf_pair1<16, 16, CT, STRIDED>), dim3(pass_grid(pair_blocks, capped, kCapWave)), wave, 0, st, G, idx_cur,
-                                       w.E, L, B, N, K, L.kc[2], static_cast<CT *>(nullptr), nact);
-                    if (const int rc1 = counted_launch_rc()) return rc1;
-                }
+                Timed t(prof, CAT_LEVEL1);
+                hipLaunchKernelGGL((k_tf_pair1<16, 16, CT, STRIDED>), dim3(pass_grid(pair_blocks, capped, cap)), wave, 0, st, G, idx_cur,
+                                   w.E, L, B, N, K, L.kc[2], static_cast<CT *>(nullptr), nact);
+                return counted_launch_rc();
+            });
+            if (rc) return rc;
+            rc = pick_bool(pass_strided(vgrid, capped, cap), [&](auto strided) {
+                constexpr bool STRIDED = strided;
                 Timed t(prof, N == 16 ? CAT_TABLES_UP : CAT_TABLES);      // (16 codebooks: the category of their level-3 launch)
-                hipLaunchKernelGGL((k_tf_table1<16, 16, CT, true, STRIDED>), dim3(pass_grid(vgrid, capped, kCapWave)), wave, 0, st, G, idx_cur,
+                hipLaunchKernelGGL((k_tf_table1<16, 16, CT, true, STRIDED>), dim3(pass_grid(vgrid, capped, cap)), wave, 0, st, G, idx_cur,
                                    L, B, N, K, ntab1, 2, w.tabs[0], nact, tab_blocks, ntab3, per3, w.tabs[1], vgrid);
                 return counted_launch_rc();
             });
@@ -729,10 +749,10 @@ int run_tf_combines(const float *G, const CT *idx_cur, CT *idx_new, const Worksp
         const unsigned pair_blocks = (unsigned)(B * (N / 4)), tab_blocks = (unsigned)(B * ntab1);
         const int ntab3 = fuse_l3 ? 16 : 1, per3 = fuse_l3 ? 4 : 1;
         const unsigned vgrid = pair_blocks + tab_blocks + (fuse_l3 ? (unsigned)(B * ntab3) : 0u);
-        const dim3 grid(pass_grid(vgrid, capped, kCapWave));
+        const dim3 grid(pass_grid(vgrid, capped, cap));
         Timed t(prof, CAT_LEVEL1_FUSED);
         const int rc = pick_leaf_lists<CT>(K, [&](auto kc0) {
-            return pick_bool(capped, [&](auto strided) {
+            return pick_bool(pass_strided(vgrid, capped, cap), [&](auto strided) {
                 constexpr int KC = decltype(kc0)::value;
                 constexpr bool STRIDED = strided;
                 hipLaunchKernelGGL((k_tf_level1<KC, KC, CT, STRIDED>), grid, wave, 0, st, G, idx_cur, w.E, L, B, N, K, keep, ntab1, per1,

@@ -27,6 +27,14 @@ constexpr int kWave = 64;
 constexpr int kBigPos = 0x7fffffff;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+// Where a function's lane number comes from: OWN (the default of a last template argument) reads lane_id() where the function
+// always read it and ignores the trailing parameter `lane_given`, so such a function is the code it was without the two; !OWN
+// takes the number a caller hands down (mcq_tf_kernels.h, tf_fresh_lane: the STRIDED pass kernels)
+template <bool OWN>
+__device__ __forceinline__ int lane_of(int lane_given) {
+    if constexpr (OWN) return lane_id();
+    else return lane_given;
+}
 
 // ---------------------------------------------------------------- reductions
 __device__ __forceinline__ float wave_sum_butterfly(float p) {
@@ -281,10 +289,11 @@ __device__ __forceinline__ u64 wave_select_mask(uint32_t ko, u64 valid, int cnt,
 // gathers of the level-0 combine); kAnyOrder -- anything (the merge of a chunked selection).  Either way the list is handed
 // over in ascending position.
 enum { kLaneMajor = 0, kSlotMajor = 1, kAnyOrder = 2 };
-template <int VPL, int LAYOUT = kLaneMajor>
+template <int VPL, int LAYOUT = kLaneMajor, bool OWN = true>
 __device__ __forceinline__ int wave_select_set(const float (&v)[VPL], const int (&p)[VPL], int cnt, int M,
-                                               u64 *lds /* kSelectLdsU64 per wave */, bool &has, int &dst, float &out_v, int &out_p) {
-    const int lane = lane_id();
+                                               u64 *lds /* kSelectLdsU64 per wave */, bool &has, int &dst, float &out_v, int &out_p,
+                                               int lane_given = 0) {
+    const int lane = lane_of<OWN>(lane_given);
     if (cnt == 1) {  // plain arg-min
         wave_select<VPL>(v, p, 1, M, out_v, out_p);
         has = lane == 0;

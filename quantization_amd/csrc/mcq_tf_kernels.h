@@ -49,6 +49,36 @@ struct TfLists {
     int erK;
 };
 
+// The arguments of the running kernel, read again from its argument block through a pointer the optimiser cannot see through.
+// `A` mirrors the kernel's parameter list member by member (the block holds every parameter at its natural alignment, in order,
+// structs by value among them, so A's layout is the block's).  The STRIDED loops of k_tf_pair0s, k_tf_pair1 and k_tf_comb call
+// this once per iteration: the body then sees freshly loaded arguments -- one batch of scalar loads that hit the constant cache
+// -- and nothing but the loop's own state is live from one iteration to the next.  Held across the loop, the arguments (the
+// whole TfLists among them) overflowed the scalar file: 35-40 SGPR spills in k_tf_pair0s and k_tf_pair1.  The loops of
+// k_tf_stage0, k_tf_table1 and k_tf_level1 hold their arguments as before: the first two ran at 8 waves per SIMD already, and
+// with fresh arguments every iteration starts behind a scalar round trip (k_tf_stage0 <256, 8>: 211 -> 230 us at 79 % active,
+// profiles/r28_ab_capped_forms.txt); k_tf_level1 shares its table body with its dense form (below).
+template <typename A>
+__device__ __forceinline__ const A &tf_fresh_args() {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();        // (constant address space: the reads stay scalar loads)
+    asm volatile("" : "+s"(p));
+    return *(const A *)p;
+}
+// The lane number, opaque to the optimiser likewise: what a body derives from it -- positions, LDS addresses: 10 to 35 registers
+// per kernel -- is loop-invariant, and the compiler hoists it out of a STRIDED loop and holds it across the iterations: THAT is
+// what took k_tf_pair1 <16, 16> from the dense form's 49 VGPRs to 83 (5 waves per SIMD) and the last k_tf_comb <16, 32> from 53
+// to 79 (6 waves); with the lane handed down they take 58 and 57.  (A body that is inlined into a dense kernel more than once --
+// tf_table1_body -- keeps its own lane in the looping forms too: an instantiation that only the dense kernel calls has that
+// kernel's LDS address folded in before inlining, and the dense kernel's text moves.)
+// The bodies and the helpers that derive most from the lane take it as a last parameter `lane_given`, read only by their !OWN
+// instantiations (mcq_kernels.h, lane_of: OWN, the default, reads lane_id() where the function always read it, so the dense kernels
+// are the code they were)
+__device__ __forceinline__ int tf_fresh_lane() {
+    int l = lane_id();
+    asm volatile("" : "+v"(l));
+    return l & 63;
+}
+
 __device__ __forceinline__ float shfl_f(float v, int src) {
     return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v)));
 }
@@ -429,16 +459,16 @@ k_tf_stage0(const float *__restrict__ G, const float *__restrict__ XC, const tf_
             const int *__restrict__ nact, const int *__restrict__ map, unsigned vgrid) {
     if constexpr (!STRIDED) {
         tf_stage0_body<K, N>(blockIdx.x, gridDim.x, G, XC, idx, R, Q, B, keep, ent_out, S_out, idx_final, nact, map);
-        return;
-    }
-    // (N > 8: the virtual launch is phase-major, ph * per_phase + r; the active part of every phase is its first `nr` ids)
-    const unsigned per = (N > 8) ? vgrid / (N / 8) : vgrid;
-    const unsigned nr = nact ? (unsigned)((*nact + 3) / 4) * (N > 8 ? 8u : (unsigned)N) : per;
-    const unsigned need = (N > 8) ? nr * (N / 8) : nr;
-    for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
-        const unsigned vb = (N > 8) ? (c / nr) * per + c % nr : c;
-        tf_stage0_body<K, N>(vb, vgrid, G, XC, idx, R, Q, B, keep, ent_out, S_out, idx_final, nact, map);
-        wave_lds_fence();
+    } else {
+        // (N > 8: the virtual launch is phase-major, ph * per_phase + r; the active part of every phase is its first `nr` ids)
+        const unsigned per = (N > 8) ? vgrid / (N / 8) : vgrid;
+        const unsigned nr = nact ? (unsigned)((*nact + 3) / 4) * (N > 8 ? 8u : (unsigned)N) : per;
+        const unsigned need = (N > 8) ? nr * (N / 8) : nr;
+        for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
+            const unsigned vb = (N > 8) ? (c / nr) * per + c % nr : c;
+            tf_stage0_body<K, N>(vb, vgrid, G, XC, idx, R, Q, B, keep, ent_out, S_out, idx_final, nact, map);
+            wave_lds_fence();
+        }
     }
 }
 
@@ -582,9 +612,10 @@ __device__ __attribute__((noinline)) void tf_er_next(const float *G, const float
 
 // The winner's leaves, codebook by codebook (:468-469): lane n walks down the position tree.
 // `win` = position a*kc + b of the winner among the pairs of the two top-level lists.
-template <typename CT>
-__device__ __forceinline__ void tf_emit(const TfLists &L, long b, int N, int nlev, int win, CT *__restrict__ idx_out) {
-    const int n = lane_id();
+template <typename CT, bool OWN = true>
+__device__ __forceinline__ void tf_emit(const TfLists &L, long b, int N, int nlev, int win, CT *__restrict__ idx_out,
+                                        int lane_given = 0) {
+    const int n = lane_of<OWN>(lane_given);
     int e = 0;
     if (n < N) {
         int v = nlev - 1;
@@ -614,10 +645,10 @@ __device__ __forceinline__ void tf_emit(const TfLists &L, long b, int N, int nle
 }
 
 // select `keep` of the wave's scores and write the next level's list (or, for the last combine, the result)
-template <int VPL, typename CT = uint8_t, int LAYOUT = kLaneMajor>
+template <int VPL, typename CT = uint8_t, int LAYOUT = kLaneMajor, bool OWN = true>
 __device__ __forceinline__ void tf_finish(const float (&sv)[VPL], const int (&sp)[VPL], int keep, int KCin, u64 *scratch,
                                           const TfLists &L, int vout /* level of the list written */, long b, int N,
-                                          int gout, CT *__restrict__ idx_final) {
+                                          int gout, CT *__restrict__ idx_final, int lane_given = 0) {
     if (idx_final != nullptr) {     // one group left, keep == 1: the smallest (score, position) is the result
         // (wave_select's rule for one winner -- smallest (score, position), NaN never taken -- without its general
         // bookkeeping of the previous winner: ten instructions per candidate there)
@@ -628,13 +659,13 @@ __device__ __forceinline__ void tf_finish(const float (&sv)[VPL], const int (&sp
         wave_lexmin(bv, bp);
         int win = __builtin_amdgcn_readfirstlane(bp);
         if (win > KCin * KCin - 1) win = KCin * KCin - 1;          // only reachable with NaN keys
-        tf_emit(L, b, N, vout, win, idx_final);
+        tf_emit<CT, OWN>(L, b, N, vout, win, idx_final, lane_given);
         return;
     }
     float ov;
     int op, dst;
     bool has;
-    wave_select_set<VPL, LAYOUT>(sv, sp, keep, KCin * KCin, scratch, has, dst, ov, op);
+    wave_select_set<VPL, LAYOUT, OWN>(sv, sp, keep, KCin * KCin, scratch, has, dst, ov, op, lane_given);
     if (has) {
         const long o = (b * (N >> vout) + gout) * keep + dst;
         L.pos[vout][2 * o] = (uint8_t)(op / KCin);
@@ -691,9 +722,11 @@ k_tf_pair0(const float *__restrict__ G, const CT *__restrict__ idx, const float 
 // load, the lane takes byte l / 16), the scores of a list reach the lanes as one coalesced load and four ds_bpermute, the border
 // lanes reuse the column entry they hold.  Same expressions, same values; the list leaves in ascending position as ever
 // (wave_select_set<kSlotMajor>).
+template <bool OWN = true>
 __device__ __forceinline__ void
 tf_pair0s_body(unsigned bid, const float *__restrict__ G, const uint8_t *__restrict__ idx, const float *__restrict__ E, const TfLists &L,
-               long B, int N, int K, int keep, uint8_t *__restrict__ idx_final, const int *__restrict__ nact) {
+               long B, int N, int K, int keep, uint8_t *__restrict__ idx_final, const int *__restrict__ nact,
+               int lane_given = 0) {
     constexpr int KC = 16, VPL = 4;
     __shared__ u64 scratch[kSelectLdsU64];
     Stamps stp;
@@ -702,7 +735,7 @@ tf_pair0s_body(unsigned bid, const float *__restrict__ G, const uint8_t *__restr
     const int g = (int)(bid & (unsigned)(Gout - 1));
     const long b = (long)(bid >> __builtin_ctz((unsigned)Gout));
     if (b >= B) return;
-    const int lane = lane_id();
+    const int lane = lane_of<OWN>(lane_given);
     const int n = 2 * g, m = n + 1;
     const int q4 = lane >> 4, c = lane & 15;
     const uint8_t *en = L.ent + (b * N + n) * KC, *em = en + KC;
@@ -743,10 +776,22 @@ tf_pair0s_body(unsigned bid, const float *__restrict__ G, const uint8_t *__restr
         sp[v] = 64 * v + lane;
     }
     stp.at(2);                                  // leaf table gathered, scores formed
-    tf_finish<VPL, uint8_t, kSlotMajor>(sv, sp, keep, KC, scratch, L, 1, b, N, g, idx_final);
+    tf_finish<VPL, uint8_t, kSlotMajor, OWN>(sv, sp, keep, KC, scratch, L, 1, b, N, g, idx_final, lane_given);
     stp.at(3);                                  // selection done, list written
     stp.flush(1, bid, 64);
 }
+
+template <typename CT>
+struct TfPairArgs {         // the parameters of k_tf_pair0s and k_tf_pair1
+    const float *G;
+    const CT *idx;
+    const float *E;
+    TfLists L;
+    long B;
+    int N, K, keep;
+    CT *idx_final;
+    const int *nact;
+};
 
 template <bool STRIDED = false>
 __global__ void __launch_bounds__(64)
@@ -754,13 +799,17 @@ k_tf_pair0s(const float *__restrict__ G, const uint8_t *__restrict__ idx, const 
             int N, int K, int keep, uint8_t *__restrict__ idx_final, const int *__restrict__ nact) {
     if constexpr (!STRIDED) {
         tf_pair0s_body(blockIdx.x, G, idx, E, L, B, N, K, keep, idx_final, nact);
-        return;
-    }
-    // (capped grid: see k_tf_stage0)
-    const unsigned need = nact ? (unsigned)*nact * (unsigned)(N >> 1) : gridDim.x;
-    for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
-        tf_pair0s_body(c, G, idx, E, L, B, N, K, keep, idx_final, nact);
-        wave_lds_fence();
+    } else {
+        // (capped grid: see k_tf_stage0)
+        // (the active count is read once, here: an iteration that began with the argument block AND, behind it, *nact had two
+        // scalar round trips ahead of its first vector load; the body gets the count as its B and no nact)
+        const long nb = nact ? (long)*nact : B;
+        const unsigned need = (unsigned)nb * (unsigned)(N >> 1);
+        for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
+            const auto &a = tf_fresh_args<TfPairArgs<uint8_t>>();
+            tf_pair0s_body<false>(c, a.G, a.idx, a.E, a.L, nb, a.N, a.K, a.keep, a.idx_final, nullptr, tf_fresh_lane());
+            wave_lds_fence();
+        }
     }
 }
 
@@ -783,13 +832,14 @@ k_tf_pair0s(const float *__restrict__ G, const uint8_t *__restrict__ idx, const 
 // a lane forms the entries of used rows and columns only.  *stmask: bit v set = t[v] is such an entry (the others are 0); the
 // caller stores a lane's four entries only if one of them is, so the rows no list names and the four-column groups without a
 // named column are NOT written -- no reader looks at them.  Every entry that is formed is formed as without the flag.
-template <int KCH, int KC, typename CT = uint8_t, bool USED2 = false>
+template <int KCH, int KC, typename CT = uint8_t, bool USED2 = false, bool OWN = true>
 __device__ __forceinline__ void tf_table1(const float *__restrict__ G, const CT *__restrict__ idx, const TfLists &L,
                                           long b, int N, int K, int X, int Y, float *leaf /* LDS [4][KCH*KCH + 64] */,
-                                          float (&t)[KC * KC / 64], Stamps &stp, uint32_t *stmask = nullptr) {
+                                          float (&t)[KC * KC / 64], Stamps &stp, uint32_t *stmask = nullptr,
+                                          int lane_given = 0) {
     static_assert(!USED2 || (KCH == 16 && KC == 16 && sizeof(CT) == 1), "the mask exists for lists of 16 one-byte entries");
     constexpr int VPLH = KCH * KCH / 64, VPL = KC * KC / 64, MH = KCH * KCH;
-    const int lane = lane_id();
+    const int lane = lane_of<OWN>(lane_given);
     const CT *id = idx + b * N;
     const CT *ent = reinterpret_cast<const CT *>(L.ent);
     const int G1 = N >> 1;
@@ -1016,10 +1066,11 @@ __device__ __forceinline__ void tf_table1(const float *__restrict__ G, const CT 
 constexpr int tf_leaf_lds_floats(int KCH, int code_bytes = 1) { return 4 * (KCH * (KCH + 1) + 36) + 16 + 16 * code_bytes; }
 
 // combine of level 1: siblings X = 2g, Y = 2g + 1 (pairs of codebooks).  One wave per (b, g).
-template <int KCH, int KC, typename CT = uint8_t>
+template <int KCH, int KC, typename CT = uint8_t, bool OWN = true>
 __device__ __forceinline__ void tf_pair1_body(unsigned bid, float *leaf, const float *__restrict__ G, const CT *__restrict__ idx,
                                               const float *__restrict__ E, const TfLists &L, long B, int N, int K, int keep,
-                                              CT *__restrict__ idx_final, const int *__restrict__ nact) {
+                                              CT *__restrict__ idx_final, const int *__restrict__ nact,
+                                              int lane_given = 0) {
     constexpr int VPL = KC * KC / 64;
     // the selection's scratch reuses the leaf tables' LDS (dead once the level-1 table sits in registers): 5.6 instead of
     // 7.3 KB per single-wave workgroup, i.e. 29 instead of 22 waves per CU
@@ -1031,7 +1082,7 @@ __device__ __forceinline__ void tf_pair1_body(unsigned bid, float *leaf, const f
     const int g = (int)(bid & (unsigned)(Gout - 1));
     const long b = (long)(bid >> __builtin_ctz((unsigned)Gout));
     if (b >= B) return;
-    const int lane = lane_id();
+    const int lane = lane_of<OWN>(lane_given);
     const int X = 2 * g, Y = X + 1, G1 = N >> 1;
     const int i = (VPL * lane) / KC, j0 = (VPL * lane) % KC;
     const float Eb = E[b];
@@ -1040,7 +1091,7 @@ __device__ __forceinline__ void tf_pair1_body(unsigned bid, float *leaf, const f
 #pragma unroll
     for (int v = 0; v < VPL; ++v) so[v] = L.S[1][(b * G1 + Y) * KC + j0 + v];
     float t[VPL];
-    tf_table1<KCH, KC, CT>(G, idx, L, b, N, K, X, Y, leaf, t, stp);
+    tf_table1<KCH, KC, CT, false, OWN>(G, idx, L, b, N, K, X, Y, leaf, t, stp, nullptr, lane_given);
     float sv[VPL];
     int sp[VPL];
 #pragma unroll
@@ -1049,7 +1100,7 @@ __device__ __forceinline__ void tf_pair1_body(unsigned bid, float *leaf, const f
         sp[v] = VPL * lane + v;
     }
     wave_lds_fence();                                   // the table reads are done before the selection writes there
-    tf_finish<VPL, CT>(sv, sp, keep, KC, scratch, L, 2, b, N, g, idx_final);
+    tf_finish<VPL, CT, kLaneMajor, OWN>(sv, sp, keep, KC, scratch, L, 2, b, N, g, idx_final, lane_given);
     stp.at(4);                                          // selection done, list written
     stp.flush(2, bid, 64);
 }
@@ -1061,13 +1112,15 @@ k_tf_pair1(const float *__restrict__ G, const CT *__restrict__ idx, const float 
     __shared__ __attribute__((aligned(16))) float leaf[tf_leaf_lds_floats(KCH, sizeof(CT))];
     if constexpr (!STRIDED) {
         tf_pair1_body<KCH, KC, CT>(blockIdx.x, leaf, G, idx, E, L, B, N, K, keep, idx_final, nact);
-        return;
-    }
-    // (capped grid: see k_tf_stage0; the grid is a multiple of 8, so a workgroup stays on its XCD)
-    const unsigned need = nact ? (unsigned)*nact * (unsigned)(N >> 2) : gridDim.x;
-    for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
-        tf_pair1_body<KCH, KC, CT>(c, leaf, G, idx, E, L, B, N, K, keep, idx_final, nact);
-        wave_lds_fence();
+    } else {
+        // (capped grid: see k_tf_stage0; the grid is a multiple of 8, so a workgroup stays on its XCD)
+        const long nb = nact ? (long)*nact : B;       // (read once: see k_tf_pair0s)
+        const unsigned need = (unsigned)nb * (unsigned)(N >> 2);
+        for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
+            const auto &a = tf_fresh_args<TfPairArgs<CT>>();
+            tf_pair1_body<KCH, KC, CT, false>(c, leaf, a.G, a.idx, a.E, a.L, nb, a.N, a.K, a.keep, a.idx_final, nullptr, tf_fresh_lane());
+            wave_lds_fence();
+        }
     }
 }
 
@@ -1120,19 +1173,19 @@ k_tf_table1(const float *__restrict__ G, const CT *__restrict__ idx, TfLists L, 
     if constexpr (!STRIDED) {
         if (blockIdx.x < tab_blocks) tf_table1_body<KCH, KC, CT, USED2>(blockIdx.x, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
         else tf_table1_body<KCH, KC, CT, USED2>(blockIdx.x - tab_blocks, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);
-        return;
-    }
-    // (the active ids of the first range rounded up to a multiple of 8, so that an id of the second keeps its XCD)
-    unsigned r1 = tab_blocks, r2 = vgrid - tab_blocks;
-    if (nact) {
-        const unsigned na = (unsigned)*nact;
-        r1 = (na * (unsigned)ntab + 7u) & ~7u;
-        r2 = r2 ? na * (unsigned)ntab2 : 0u;
-    }
-    for (unsigned c = blockIdx.x; c < r1 + r2; c += gridDim.x) {
-        if (c < r1) tf_table1_body<KCH, KC, CT, USED2>(c, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
-        else tf_table1_body<KCH, KC, CT, USED2>(c - r1, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);
-        wave_lds_fence();
+    } else {
+        // (the active ids of the first range rounded up to a multiple of 8, so that an id of the second keeps its XCD)
+        unsigned r1 = tab_blocks, r2 = vgrid - tab_blocks;
+        if (nact) {
+            const unsigned na = (unsigned)*nact;
+            r1 = (na * (unsigned)ntab + 7u) & ~7u;
+            r2 = r2 ? na * (unsigned)ntab2 : 0u;
+        }
+        for (unsigned c = blockIdx.x; c < r1 + r2; c += gridDim.x) {
+            if (c < r1) tf_table1_body<KCH, KC, CT, USED2>(c, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
+            else tf_table1_body<KCH, KC, CT, USED2>(c - r1, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);
+            wave_lds_fence();
+        }
     }
 }
 
@@ -1149,23 +1202,23 @@ k_tf_level1(const float *__restrict__ G, const CT *__restrict__ idx, const float
         if (blockIdx.x < pair_blocks) tf_pair1_body<KCH, KC, CT>(blockIdx.x, leaf, G, idx, E, L, B, N, K, keep, nullptr, nact);
         else if (blockIdx.x < pair_blocks + tab_blocks) tf_table1_body<KCH, KC, CT>(blockIdx.x - pair_blocks, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
         else tf_table1_body<KCH, KC, CT>(blockIdx.x - pair_blocks - tab_blocks, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);   // (16 codebooks: the tables of level 3 as well)
-        return;
-    }
-    // (capped grid: see k_tf_stage0.  The active ids of each of the three ranges, rounded up to a multiple of 8: a range's
-    // virtual id mod 8 stays that of the compact id as long as the full ranges are multiples of 8, as they are at the bench
-    // shape; the ids past the active vectors return at once)
-    unsigned r0 = pair_blocks, r1 = tab_blocks, r2 = vgrid - pair_blocks - tab_blocks;
-    if (nact) {
-        const unsigned na = (unsigned)*nact;
-        r0 = (na * (unsigned)(N / 4) + 7u) & ~7u;
-        r1 = (na * (unsigned)ntab + 7u) & ~7u;
-        r2 = r2 ? na * (unsigned)ntab2 : 0u;
-    }
-    for (unsigned c = blockIdx.x; c < r0 + r1 + r2; c += gridDim.x) {
-        if (c < r0) tf_pair1_body<KCH, KC, CT>(c, leaf, G, idx, E, L, B, N, K, keep, nullptr, nact);
-        else if (c < r0 + r1) tf_table1_body<KCH, KC, CT>(c - r0, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
-        else tf_table1_body<KCH, KC, CT>(c - r0 - r1, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);   // (16 codebooks: the tables of level 3 as well)
-        wave_lds_fence();
+    } else {
+        // (capped grid: see k_tf_stage0.  The active ids of each of the three ranges, rounded up to a multiple of 8: a range's
+        // virtual id mod 8 stays that of the compact id as long as the full ranges are multiples of 8, as they are at the bench
+        // shape; the ids past the active vectors return at once)
+        unsigned r0 = pair_blocks, r1 = tab_blocks, r2 = vgrid - pair_blocks - tab_blocks;
+        if (nact) {
+            const unsigned na = (unsigned)*nact;
+            r0 = (na * (unsigned)(N / 4) + 7u) & ~7u;
+            r1 = (na * (unsigned)ntab + 7u) & ~7u;
+            r2 = r2 ? na * (unsigned)ntab2 : 0u;
+        }
+        for (unsigned c = blockIdx.x; c < r0 + r1 + r2; c += gridDim.x) {
+            if (c < r0) tf_pair1_body<KCH, KC, CT>(c, leaf, G, idx, E, L, B, N, K, keep, nullptr, nact);
+            else if (c < r0 + r1) tf_table1_body<KCH, KC, CT>(c - r0, leaf, G, idx, L, B, N, K, ntab, per, tabs, nact);
+            else tf_table1_body<KCH, KC, CT>(c - r0 - r1, leaf, G, idx, L, B, N, K, ntab2, per2, tabs2, nact);   // (16 codebooks: the tables of level 3 as well)
+            wave_lds_fence();
+        }
     }
 }
 
@@ -1176,10 +1229,10 @@ k_tf_level1(const float *__restrict__ G, const CT *__restrict__ idx, const float
 template <int KH>
 constexpr int tf_tab_stride() { return KH * (KH + 1); }      // floats per table in LDS
 
-template <int KH, int COUNT>
-__device__ __forceinline__ void tf_load_tables(const float *__restrict__ src, float *dst) {
+template <int KH, int COUNT, bool OWN = true>
+__device__ __forceinline__ void tf_load_tables(const float *__restrict__ src, float *dst, int lane_given = 0) {
     constexpr int M = KH * KH, RS = KH + 1, TS = tf_tab_stride<KH>();
-    const int lane = lane_id();
+    const int lane = lane_of<OWN>(lane_given);
     if constexpr ((COUNT * M) % 256 == 0 && KH % 4 == 0) {
         constexpr int IT = COUNT * M / 256;               // float4 per lane
         constexpr int BATCH = IT < 8 ? IT : 8;
@@ -1269,10 +1322,10 @@ k_tf_up(TfLists L, long B, int N, int u, int ntab, int per, const float *__restr
 // LAST: the combine that leaves one group (idx_final != nullptr, keep == 1) as an instantiation of its own -- the winner is a
 // running arg-min over the scores, no score array and no selection: 86 registers -> the 8 waves per SIMD of the other pass kernels
 // (k_tf_comb<16,32> is the last launch of every pass of 8 codebooks).
-template <int KH, int KC, bool LAST, typename CT = uint8_t>
+template <int KH, int KC, bool LAST, typename CT = uint8_t, bool OWN = true>
 __device__ __forceinline__ void
 tf_comb_body(unsigned bid, const float *__restrict__ E, const TfLists &L, long B, int N, int v, int keep, const float *__restrict__ tabs,
-             CT *__restrict__ idx_final, const int *__restrict__ nact) {
+             CT *__restrict__ idx_final, const int *__restrict__ nact, int lane_given = 0) {
     constexpr int MH = KH * KH, RS = KH + 1, TS = tf_tab_stride<KH>();
     constexpr int VPL = (KC * KC / 64 <= 16) ? KC * KC / 64 : 16;
     constexpr int CHUNKS = KC * KC / (64 * VPL);
@@ -1288,9 +1341,9 @@ tf_comb_body(unsigned bid, const float *__restrict__ E, const TfLists &L, long B
     const int h = (int)(bid & (unsigned)(Gout - 1));
     const long b = (long)(bid >> __builtin_ctz((unsigned)Gout));
     if (b >= B) return;
-    const int lane = lane_id();
+    const int lane = lane_of<OWN>(lane_given);
     const int P = 2 * h, Q = P + 1, Gv = N >> v;
-    tf_load_tables<KH, 4>(tabs + ((size_t)b * Gout + h) * 4 * MH, th);
+    tf_load_tables<KH, 4, OWN>(tabs + ((size_t)b * Gout + h) * 4 * MH, th, lane_given);
     const float Eb = E[b];
     const uint8_t *px = L.pos[v] + ((b * Gv + P) * KC) * 2, *py = L.pos[v] + ((b * Gv + Q) * KC) * 2;
     const float *Sx = L.S[v] + (b * Gv + P) * KC, *Sy = L.S[v] + (b * Gv + Q) * KC;
@@ -1308,7 +1361,7 @@ tf_comb_body(unsigned bid, const float *__restrict__ E, const TfLists &L, long B
             sp[u] = VPL * lane + u;
         }
         wave_lds_fence();
-        tf_finish<VPL, CT>(sv, sp, keep, KC, scratch, L, v + 1, b, N, h, idx_final);
+        tf_finish<VPL, CT, kLaneMajor, OWN>(sv, sp, keep, KC, scratch, L, v + 1, b, N, h, idx_final, lane_given);
     } else if (!LAST) {
         // 4,096 pairs that are NOT the last combine (64 codebooks of more than 16 entries: 64 of them go on): the 64 smallest
         // of every chunk of 1,024, then the 64 smallest of those 4 x 64 -- the same set and order as one selection over
@@ -1359,9 +1412,20 @@ tf_comb_body(unsigned bid, const float *__restrict__ E, const TfLists &L, long B
         }
         wave_lexmin(bv, bp);
         if (bp > KC * KC - 1) bp = KC * KC - 1;                  // only reachable with NaN keys
-        tf_emit(L, b, N, v + 1, bp, idx_final);                   // keep == 1, last combine
+        tf_emit<CT, OWN>(L, b, N, v + 1, bp, idx_final, lane_given);      // keep == 1, last combine
     }
 }
+
+template <typename CT>
+struct TfCombArgs {         // k_tf_comb's parameters
+    const float *E;
+    TfLists L;
+    long B;
+    int N, v, keep;
+    const float *tabs;
+    CT *idx_final;
+    const int *nact;
+};
 
 template <int KH, int KC, bool LAST, typename CT = uint8_t, bool STRIDED = false>
 __global__ void __launch_bounds__(64)
@@ -1369,13 +1433,15 @@ k_tf_comb(const float *__restrict__ E, TfLists L, long B, int N, int v, int keep
           CT *__restrict__ idx_final, const int *__restrict__ nact) {
     if constexpr (!STRIDED) {
         tf_comb_body<KH, KC, LAST, CT>(blockIdx.x, E, L, B, N, v, keep, tabs, idx_final, nact);
-        return;
-    }
-    // (capped grid: see k_tf_stage0)
-    const unsigned need = nact ? (unsigned)*nact * (unsigned)(N >> (v + 1)) : gridDim.x;
-    for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
-        tf_comb_body<KH, KC, LAST, CT>(c, E, L, B, N, v, keep, tabs, idx_final, nact);
-        wave_lds_fence();
+    } else {
+        // (capped grid: see k_tf_stage0)
+        const long nb = nact ? (long)*nact : B;       // (read once: see k_tf_pair0s)
+        const unsigned need = (unsigned)nb * (unsigned)(N >> (v + 1));
+        for (unsigned c = blockIdx.x; c < need; c += gridDim.x) {
+            const auto &a = tf_fresh_args<TfCombArgs<CT>>();
+            tf_comb_body<KH, KC, LAST, CT, false>(c, a.E, a.L, nb, a.N, a.v, a.keep, a.tabs, a.idx_final, nullptr, tf_fresh_lane());
+            wave_lds_fence();
+        }
     }
 }
 
