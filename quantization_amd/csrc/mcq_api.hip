@@ -1201,6 +1201,26 @@ struct ListsIn {
     int P;
     const float *bias = nullptr;              // rule 21: float[Q][P], one value per (query, probe slot); NULL: none
 };
+// the whole store as one list: probes == NULL to k_search_wide and k_range_lists
+constexpr ListsIn kWholeStore{nullptr, 0, nullptr, 1};
+
+// the table rows a list kernel over codes of type T is allowed LDS for: 64 codebooks of 256 entries under one-byte codes, the
+// library's cap under two-byte ones (N = 64 is reachable at K <= 256 only, rule 33)
+template <typename T>
+constexpr int kTableRowsOf = sizeof(T) == 2 ? kMaxRows : 64 * 256;
+
+// checks that several entry points make, each where its own order has it (the test_*_host.py files pin the orders)
+bool metric_ok(int metric) { return metric == MCQ_SEARCH_L2 || metric == MCQ_SEARCH_IP || metric == MCQ_SEARCH_COS; }
+bool w_ok(const float *w, int metric) { return w || metric == MCQ_SEARCH_IP; }          // (the inner product never reads w)
+bool codes_aligned(const void *codes, int N, int code_bytes) {           // a candidate's codes are loaded as one vector
+    return reinterpret_cast<uintptr_t>(codes) % (N * code_bytes >= 16 ? 16 : N * code_bytes) == 0;
+}
+// what the mcq_*_workspace_bytes entries of the scans, sweeps and lists size; outside it they answer 256.  n: B up to
+// 2^31 - 1, or P up to kListMaxProbes; an entry without k passes 1 of 1
+bool sized(long Q, long n, long n_max, int N, int K, int k, int k_max, int code_bytes = 1) {
+    return Q >= 1 && Q <= 0x7fffffffL && n >= 1 && n <= n_max && k >= 1 && k <= k_max &&
+           (code_bytes == 2 ? code16_domain(N, K, 1) : search_domain(N, K, 1)) == 0;
+}
 
 // What every scan, sweep and list-by-list entry point rejects, in this order (tests/test_search_host.py, test_search_metric_host.py,
 // test_search_mask_host.py, test_search_range_host.py, test_search_lists_host.py and test_search_range_lists_host.py pin it);
@@ -1216,7 +1236,7 @@ int search_check(const float *tables, long Q, const void *codes, const float *w,
     if (const int rc = code_bytes == 2 ? code16_domain(N, K, 1) : search_domain(N, K, 1)) return rc;
     if (k > 64) return MCQ_EUNSUPPORTED;
     if (k < 1 || Q < 0 || B < 0 || Q > 0x7fffffffL) return MCQ_EINVAL;
-    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
+    if (!metric_ok(metric)) return MCQ_EINVAL;
     if (B > 0x7fffffffL) return MCQ_EUNSUPPORTED;
     if (li && (li->P < 0 || li->L < 0)) return MCQ_EINVAL;
     if (li && li->P > kListMaxProbes) return MCQ_EUNSUPPORTED;
@@ -1226,9 +1246,7 @@ int search_check(const float *tables, long Q, const void *codes, const float *w,
         return 0;
     }
     if (!tables || !codes || !workspace || (li && (!li->list_offsets || !li->probes))) return MCQ_EINVAL;
-    if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;                  // (the inner product never reads w)
-    const int need = N * code_bytes >= 16 ? 16 : N * code_bytes;          // a candidate's codes are loaded as one vector
-    if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
+    if (!w_ok(w, metric) || !codes_aligned(codes, N, code_bytes)) return MCQ_EINVAL;
     if (reinterpret_cast<uintptr_t>(mask) % 8 != 0) return MCQ_EINVAL;
     if (li && (reinterpret_cast<uintptr_t>(li->list_offsets) % 8 != 0 || reinterpret_cast<uintptr_t>(li->probes) % 4 != 0)) return MCQ_EINVAL;
     if (li && reinterpret_cast<uintptr_t>(li->bias) % 4 != 0) return MCQ_EINVAL;
@@ -1285,16 +1303,19 @@ TilePlan tile_plan(long Q, long B, int N, int K, int waves) {
     return p;
 }
 
-// the scan: LDS holds the tables, then the waves' lists; the workspace k (score, position) pairs per (query, slice)
+// the workspace of a top-k call: k scores per (query, list), then as many positions, each array 256-aligned
+size_t topk_ws_bytes(long Q, int lists, int k) { return 2 * align256((size_t)Q * lists * k * 4); }
+
+// the scan: LDS holds the tables, then the waves' lists; a list per (query, slice)
 struct ScanPlan : TilePlan {
-    size_t lds, ws_half;
+    size_t lds, ws_bytes;
 };
 
 ScanPlan scan_plan(long Q, long B, int N, int K, int k) {
     ScanPlan p{tile_plan(Q, B, N, K, kScanWaves), 0, 0};
     const size_t tab = (size_t)p.qt * N * K * 4, lists = (size_t)p.qt * kScanWaves * 64 * 8;
     p.lds = tab > lists ? tab : lists;
-    p.ws_half = align256((size_t)Q * p.slices * k * 4);                  // scores, then positions
+    p.ws_bytes = topk_ws_bytes(Q, p.slices, k);
     return p;
 }
 
@@ -1323,26 +1344,35 @@ int launch_scan(const ScanPlan &p, hipStream_t st, const float *tables, int Q, c
     });
 }
 
-// the search list by list (rules 13-16; mirrored by lists_plan of tests/search_lists_grid.py): one query per workgroup and
-// `parts` parts of each query's candidates -- as many as fill the chip once at small Q, capped as the slice count is.  A
-// function of the call's shape alone: the lists' lengths are known to the device only (nothing is read back).
-struct ListsPlan {
+// The plan of every kernel that gives a workgroup one query and one of `parts` parts of that query's candidates: the search
+// list by list, past 64 neighbours and over a shortlist, the re-ranking, the range search list by list.  A function of the
+// call's shape alone: what a list or a shortlist row holds is known to the device only (nothing is read back).
+// parts == 0 (PartPlan{}): the call has no candidate anywhere.
+struct PartPlan {
     int parts;
-    size_t lds, ws_half;
+    size_t lds, ws_bytes;
 };
 
-int lists_parts(long Q) {
-    const long parts = kListTargetBlocks / (Q > 0 ? Q : 1);
-    return (int)(parts < 1 ? 1 : (parts > kScanMaxSlices ? kScanMaxSlices : parts));
+// as many parts as fill the chip once at small Q (`target` workgroups), no more than `cap`, no more than the `steps` a
+// query's candidates make where that is known on the host, at least one
+int part_count(long Q, long target, long cap, long steps = 0x7fffffffL) {
+    long parts = target / (Q > 0 ? Q : 1);
+    parts = parts > cap ? cap : parts;
+    parts = parts > steps ? steps : parts;
+    return (int)(parts < 1 ? 1 : parts);
 }
+// the cap that keeps the merge of a query to kWideMergeEntries streamed entries per entry of its sorted half: 128 parts up to
+// k = 512 and 64 beyond
+long wide_merge_cap(int k) { return kWideMergeEntries / wide_half(k); }
 
-ListsPlan lists_plan(long Q, int P, int N, int K, int k) {
-    const int parts = lists_parts(Q);
-    return {parts, (size_t)lists_lds_bytes(N * K, P), align256((size_t)Q * parts * k * 4)};   // scores, then positions
+// the search list by list (rules 13-16; mirrored by lists_plan of tests/search_lists_grid.py): capped as the slice count is
+PartPlan lists_plan(long Q, int P, int N, int K, int k) {
+    const int parts = part_count(Q, kListTargetBlocks, kScanMaxSlices);
+    return {parts, (size_t)lists_lds_bytes(N * K, P), topk_ws_bytes(Q, parts, k)};
 }
 
 // a bias (li.bias != NULL; rules 21 and 23) is one more flag of the same kernel: a call moves between the two by its bias alone
-int launch_lists(const ListsPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
+int launch_lists(const PartPlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
                  int N, int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
     return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
         return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
@@ -1364,6 +1394,29 @@ int launch_lists(const ListsPlan &p, hipStream_t st, const float *tables, int Q,
     });
 }
 
+// The tail of every top-k call, once its arguments have passed: the size of the workspace against the plan's, its split
+// into scores, then positions, launch(ws_s, ws_i) -- a list of k entries per (query, part) --, and the merge of a query's
+// lists into its result (wide: k_search_wide_merge of mcq_wide_kernels.h).  A plan without parts (no candidate anywhere)
+// launches the merge alone, on no list: the fill of rule 4.
+template <typename Launch>
+int topk_tail(const PartPlan &p, void *workspace, size_t workspace_bytes, hipStream_t st, long Q, int k, float *out_score,
+              int64_t *out_index, bool wide, Launch &&launch) {
+    float *ws_s = nullptr;
+    int *ws_i = nullptr;
+    if (p.parts > 0) {
+        if (workspace_bytes < p.ws_bytes) return MCQ_EWORKSPACE;
+        ws_s = static_cast<float *>(workspace);
+        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_bytes / 2);
+        if (const int rc = launch(ws_s, ws_i)) return rc;
+    }
+    if (wide)
+        hipLaunchKernelGGL(k_search_wide_merge, dim3((unsigned)Q), dim3(64 * kWideWaves), 0, st, ws_s, ws_i, p.parts, k, out_score,
+                           out_index);
+    else
+        hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, p.parts, k, out_score, out_index);
+    return launch_rc();
+}
+
 // every top-k entry point: the scan over the whole store (rules 1-6 and 10-12), or list by list (li; rules 13-16)
 int search_topk(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
                 const uint64_t *mask, const ListsIn *li, float *out_score, int64_t *out_index, void *workspace,
@@ -1373,44 +1426,22 @@ int search_topk(const float *tables, long Q, const uint8_t *codes, const float *
         return rc;
     if (Q == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws_s = nullptr;
-    int *ws_i = nullptr;
-    const auto split = [&](size_t half) {                                 // the workspace: scores, then positions
-        if (workspace_bytes < 2 * half) return false;
-        ws_s = static_cast<float *>(workspace);
-        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + half);
-        return true;
-    };
-    int S = 0;                                                            // lists per query; 0 (no candidate anywhere): the fill of rule 4
-    if (!empty && li) {
-        const ListsPlan p = lists_plan(Q, li->P, N, K, k);
-        if (!split(p.ws_half)) return MCQ_EWORKSPACE;
-        if (const int rc = launch_lists(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, *li, ws_s, ws_i)) return rc;
-        S = p.parts;
-    } else if (!empty) {
-        const ScanPlan p = scan_plan(Q, B, N, K, k);
-        if (!split(p.ws_half)) return MCQ_EWORKSPACE;
-        if (const int rc = launch_scan(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, ws_s, ws_i, mask)) return rc;
-        S = p.slices;
-    }
-    hipLaunchKernelGGL(k_search_merge, dim3((unsigned)Q), dim3(64), 0, st, ws_s, ws_i, S, k, out_score, out_index);
-    return launch_rc();
+    const ScanPlan sp = (empty || li) ? ScanPlan{} : scan_plan(Q, B, N, K, k);
+    const PartPlan p = empty ? PartPlan{} : li ? lists_plan(Q, li->P, N, K, k) : PartPlan{sp.slices, sp.lds, sp.ws_bytes};
+    return topk_tail(p, workspace, workspace_bytes, st, Q, k, out_score, out_index, false, [&](float *ws_s, int *ws_i) {
+        return li ? launch_lists(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, *li, ws_s, ws_i)
+                  : launch_scan(sp, st, tables, (int)Q, codes, w, B, N, K, k, metric, ws_s, ws_i, mask);
+    });
 }
 
 // ---- the search past 64 neighbours (mcq_wide_kernels.h; rules 24-27 of include/mcq_wide.h; mirrored by wide_plan of
 // tests/search_wide_grid.py): the parts of lists_plan, capped so that the merge of a query streams at most kWideMergeEntries
-// entries per entry of its sorted half -- 64 parts up to k = 512 and 32 beyond, where lists_parts alone would hand the merge
-// of a single query 256 lists.  A function of the call's shape alone.  P is 1 for a call over the whole store.
-struct WidePlan {
-    int parts;
-    size_t lds, ws_half;
-};
-
-WidePlan wide_plan(long Q, int P, int N, int K, int k) {
-    const int cap = kWideMergeEntries / wide_half(k);
-    int parts = lists_parts(Q);
-    parts = parts > cap ? cap : parts;
-    return {parts, (size_t)wide_lds_bytes(N * K, P, k), align256((size_t)Q * parts * k * 4)};   // scores, then positions
+// entries per entry of its sorted half -- 128 parts up to k = 512 and 64 beyond (wide_merge_cap), where lists_plan alone
+// would hand the merge of a single query 256 lists.  P is 1 for a call over the whole store.
+PartPlan wide_plan(long Q, int P, int N, int K, int k) {
+    const long cap = wide_merge_cap(k) < kScanMaxSlices ? wide_merge_cap(k) : kScanMaxSlices;
+    const int parts = part_count(Q, kListTargetBlocks, cap);
+    return {parts, (size_t)wide_lds_bytes(N * K, P, k), topk_ws_bytes(Q, parts, k)};
 }
 
 // search_check with the cap of this feature: k in 65 .. 1,024 passes where search_check tests k > 64, a larger one fails there
@@ -1420,43 +1451,23 @@ int wide_check(const float *tables, long Q, const void *codes, const float *w, l
     return search_check(tables, Q, codes, w, B, N, K, as, metric, mask, li, outs_ok, workspace, empty, code_bytes);
 }
 
-// li.probes == NULL: the whole store as one list; a bias is a null test inside the kernel, not a flag
-int launch_wide(const WidePlan &p, hipStream_t st, const float *tables, int Q, const uint8_t *codes, const float *w, long B,
-                int N, int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
+// li.probes == NULL: the whole store as one list; a bias is a null test inside the kernel, not a flag.  T = uint16_t
+// (mcq_search_topk_u16): the same plan, the two-byte instantiations
+template <typename T>
+int launch_wide(const PartPlan &p, hipStream_t st, const float *tables, int Q, const T *codes, const float *w, long B, int N,
+                int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
     return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
         return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
             return pick_bool(mask != nullptr, [&](auto masked) {
                 constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
                 constexpr bool MASKED = masked;
                 static bool allowed[64] = {};
-                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_wide<NN, M, MASKED>),
-                                                     wide_lds_bytes(64 * 256, kListMaxProbes, kWideMaxK)))
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_wide<NN, M, MASKED, T>),
+                                                     wide_lds_bytes(kTableRowsOf<T>, kListMaxProbes, kWideMaxK)))
                     return rc;
-                hipLaunchKernelGGL((k_search_wide<NN, M, MASKED>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kWideWaves),
+                hipLaunchKernelGGL((k_search_wide<NN, M, MASKED, T>), dim3((unsigned)Q * (unsigned)p.parts), dim3(64 * kWideWaves),
                                    p.lds, st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts, li.list_offsets, li.L,
                                    li.probes, li.P, ws_s, ws_i, reinterpret_cast<const u64 *>(mask), li.bias);
-                return launch_rc();
-            });
-        });
-    });
-}
-
-// launch_wide over two-byte codes (mcq_search_topk_u16): the same plan, the uint16_t instantiations.  N = 64 is reachable at
-// K <= 256 only (rule 33), and then with the largest table the one-byte kernels carry.
-int launch_wide16(const WidePlan &p, hipStream_t st, const float *tables, int Q, const uint16_t *codes, const float *w, long B,
-                  int N, int K, int k, int metric, const uint64_t *mask, const ListsIn &li, float *ws_s, int *ws_i) {
-    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
-        return pick<1, 2, 4, 8, 16, 32, 64>(N, [&](auto nn) {
-            return pick_bool(mask != nullptr, [&](auto masked) {
-                constexpr int M = decltype(m)::value, NN = decltype(nn)::value;
-                constexpr bool MASKED = masked;
-                static bool allowed[64] = {};
-                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_search_wide<NN, M, MASKED, uint16_t>),
-                                                     wide_lds_bytes(kMaxRows, kListMaxProbes, kWideMaxK)))
-                    return rc;
-                hipLaunchKernelGGL((k_search_wide<NN, M, MASKED, uint16_t>), dim3((unsigned)Q * (unsigned)p.parts),
-                                   dim3(64 * kWideWaves), p.lds, st, tables, Q, codes, M == kMetricIP ? nullptr : w, B, K, k, p.parts,
-                                   li.list_offsets, li.L, li.probes, li.P, ws_s, ws_i, reinterpret_cast<const u64 *>(mask), li.bias);
                 return launch_rc();
             });
         });
@@ -1474,57 +1485,41 @@ int search_wide(const float *tables, long Q, const T *codes, const float *w, lon
         return rc;
     if (Q == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws_s = nullptr;
-    int *ws_i = nullptr;
-    int S = 0;                                                            // lists per query; 0 (no candidate anywhere): the fill of rule 4
-    if (!empty) {
-        const ListsIn whole{nullptr, 0, nullptr, 1};
-        const ListsIn &in = li ? *li : whole;
-        const WidePlan p = wide_plan(Q, in.P, N, K, k);
-        if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
-        ws_s = static_cast<float *>(workspace);                            // the workspace: scores, then positions
-        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
-        if constexpr (sizeof(T) == 2) {
-            if (const int rc = launch_wide16(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, in, ws_s, ws_i)) return rc;
-        } else {
-            if (const int rc = launch_wide(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, in, ws_s, ws_i)) return rc;
-        }
-        S = p.parts;
-    }
-    hipLaunchKernelGGL(k_search_wide_merge, dim3((unsigned)Q), dim3(64 * kWideWaves), 0, st, ws_s, ws_i, S, k, out_score, out_index);
-    return launch_rc();
+    const ListsIn &in = li ? *li : kWholeStore;
+    const PartPlan p = empty ? PartPlan{} : wide_plan(Q, in.P, N, K, k);
+    return topk_tail(p, workspace, workspace_bytes, st, Q, k, out_score, out_index, true, [&](float *ws_s, int *ws_i) {
+        return launch_wide<T>(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, mask, in, ws_s, ws_i);
+    });
 }
 
 // ---- the exact re-ranking of a shortlist (mcq_rerank_kernels.h; rules 28-31 of include/mcq_rerank.h; mirrored by rerank_plan
 // of tests/rerank_grid.py): one query per workgroup and `parts` parts of its shortlist row, cut by count of its steps of
 // kRerankGroup entries -- as many as fill the chip once at small Q, no more than the row has steps, capped as wide_plan caps
-// them for the merge.  A function of the call's shape alone.
-struct RerankPlan {
-    int parts;
-    size_t lds, ws_half;
-};
-
-RerankPlan rerank_plan(long Q, long S, int D, int k) {
-    const long steps = (S + kRerankGroup - 1) / kRerankGroup;
-    const long cap = kWideMergeEntries / wide_half(k);
-    long parts = kRerankTargetBlocks / (Q > 0 ? Q : 1);
-    parts = parts > cap ? cap : parts;
-    parts = parts > steps ? steps : parts;
-    parts = parts < 1 ? 1 : parts;
-    return {(int)parts, (size_t)rerank_lds_bytes(D, k), align256((size_t)Q * parts * k * 4)};   // scores, then positions
+// them for the merge.
+PartPlan rerank_plan(long Q, long S, int D, int k) {
+    const int parts = part_count(Q, kRerankTargetBlocks, wide_merge_cap(k), (S + kRerankGroup - 1) / kRerankGroup);
+    return {parts, (size_t)rerank_lds_bytes(D, k), topk_ws_bytes(Q, parts, k)};
 }
 
-// rule 28's limits, in its order; 0 inside the domain
-int rerank_domain(long Q, long S, long B, long Bs, int D, int k, int metric) {
+// the limits the calls over a shortlist share (rules 28 and 36), in their order, behind what the call says of its rows (D,
+// or N and K); 0 inside the domain
+int shortlist_limits(long Q, long S, long B, long Bs, int k, int metric) {
     constexpr long kLimit = 0x7fffffffL;                                   // sizes stay below 2^31 - 1
-    if (D > kRerankMaxD || k > kWideMaxK) return MCQ_EUNSUPPORTED;
-    if (D < 1 || k < 1 || Q < 0 || S < 0 || B < 0 || Bs < 0) return MCQ_EINVAL;
-    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
+    if (k > kWideMaxK) return MCQ_EUNSUPPORTED;
+    if (k < 1 || Q < 0 || S < 0 || B < 0 || Bs < 0) return MCQ_EINVAL;
+    if (!metric_ok(metric)) return MCQ_EINVAL;
     if (Q >= kLimit || S >= kLimit || B >= kLimit || Bs >= kLimit) return MCQ_EUNSUPPORTED;
     return 0;
 }
 
-int launch_rerank(const RerankPlan &p, hipStream_t st, const void *queries, bool qhalf, int Q, const void *vectors, bool xhalf,
+// rule 28's limits, in its order; 0 inside the domain.  A k past the cap is reported before a D below 1
+int rerank_domain(long Q, long S, long B, long Bs, int D, int k, int metric) {
+    if (D > kRerankMaxD) return MCQ_EUNSUPPORTED;
+    if (D < 1 && k <= kWideMaxK) return MCQ_EINVAL;
+    return shortlist_limits(Q, S, B, Bs, k, metric);
+}
+
+int launch_rerank(const PartPlan &p, hipStream_t st, const void *queries, bool qhalf, int Q, const void *vectors, bool xhalf,
                   long B, int D, const int64_t *shortlist, int S, const int64_t *row_of, long Bs, int k, int metric, int vec,
                   float *ws_s, int *ws_i) {
     return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
@@ -1552,62 +1547,39 @@ int rerank(const void *queries, bool qhalf, long Q, const void *vectors, bool xh
     if (Q > 0 && (!out_score || !out_index)) return MCQ_EINVAL;
     if (Q == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws_s = nullptr;
-    int *ws_i = nullptr;
-    int parts = 0;                                                        // lists per query; 0 (no candidate anywhere): the fill
+    const size_t qel = qhalf ? 2 : 4, xel = xhalf ? 2 : 4;
+    PartPlan p{};                                                         // (no row can hold a candidate: the fill)
     if (S > 0 && B > 0 && Bs > 0) {
         if (!queries || !vectors || !shortlist || !workspace) return MCQ_EINVAL;
-        const size_t qel = qhalf ? 2 : 4, xel = xhalf ? 2 : 4;
         if (reinterpret_cast<uintptr_t>(queries) % qel != 0 || reinterpret_cast<uintptr_t>(vectors) % xel != 0) return MCQ_EINVAL;
         if (reinterpret_cast<uintptr_t>(shortlist) % 8 != 0 || reinterpret_cast<uintptr_t>(row_of) % 8 != 0) return MCQ_EINVAL;
-        const RerankPlan p = rerank_plan(Q, S, D, k);
-        if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
-        ws_s = static_cast<float *>(workspace);                            // the workspace: scores, then positions
-        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
-        // one vector load per lane and trip where every row starts on its boundary: 16 bytes of fp32, 8 of fp16
-        const int vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(vectors) % (4 * xel) == 0;
-        if (const int rc = launch_rerank(p, st, queries, qhalf, (int)Q, vectors, xhalf, B, D, shortlist, (int)S, row_of, Bs, k,
-                                         metric, vec, ws_s, ws_i))
-            return rc;
-        parts = p.parts;
+        p = rerank_plan(Q, S, D, k);
     }
-    hipLaunchKernelGGL(k_search_wide_merge, dim3((unsigned)Q), dim3(64 * kWideWaves), 0, st, ws_s, ws_i, parts, k, out_score,
-                       out_index);
-    return launch_rc();
+    // one vector load per lane and trip where every row starts on its boundary: 16 bytes of fp32, 8 of fp16
+    const int vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(vectors) % (4 * xel) == 0;
+    return topk_tail(p, workspace, workspace_bytes, st, Q, k, out_score, out_index, true, [&](float *ws_s, int *ws_i) {
+        return launch_rerank(p, st, queries, qhalf, (int)Q, vectors, xhalf, B, D, shortlist, (int)S, row_of, Bs, k, metric, vec,
+                             ws_s, ws_i);
+    });
 }
 
 // ---- the search over a shortlist (mcq_shortlist_kernels.h; rules 36-39 of include/mcq_shortlist.h; mirrored by short_plan of
 // tests/search_shortlist_grid.py): one query per workgroup and `parts` parts of its shortlist row, cut by count of its steps
 // of kShortStep entries -- as many as fill the chip once at small Q, no more than the row has steps, capped as wide_plan caps
-// them for the merge.  A function of the call's shape alone.
-struct ShortPlan {
-    int parts;
-    size_t lds, ws_half;
-};
-
-ShortPlan short_plan(long Q, long S, int N, int K, int k) {
-    const long steps = (S + kShortStep - 1) / kShortStep;
-    const long cap = kWideMergeEntries / wide_half(k);
-    long parts = kShortTargetBlocks / (Q > 0 ? Q : 1);
-    parts = parts > cap ? cap : parts;
-    parts = parts > steps ? steps : parts;
-    parts = parts < 1 ? 1 : parts;
-    return {(int)parts, (size_t)short_lds_bytes(N * K, k), align256((size_t)Q * parts * k * 4)};   // scores, then positions
+// them for the merge.
+PartPlan short_plan(long Q, long S, int N, int K, int k) {
+    const int parts = part_count(Q, kShortTargetBlocks, wide_merge_cap(k), (S + kShortStep - 1) / kShortStep);
+    return {parts, (size_t)short_lds_bytes(N * K, k), topk_ws_bytes(Q, parts, k)};
 }
 
 // rule 36's limits, in its order; 0 inside the domain.  code_bytes: 1, or 2 for mcq_search_shortlist_u16
 int short_domain(long Q, long S, long B, long Bs, int N, int K, int k, int metric, int code_bytes) {
-    constexpr long kLimit = 0x7fffffffL;                                   // sizes stay below 2^31 - 1
     if (const int rc = code_bytes == 2 ? code16_domain(N, K, 1) : search_domain(N, K, 1)) return rc;
-    if (k > kWideMaxK) return MCQ_EUNSUPPORTED;
-    if (k < 1 || Q < 0 || S < 0 || B < 0 || Bs < 0) return MCQ_EINVAL;
-    if (metric != MCQ_SEARCH_L2 && metric != MCQ_SEARCH_IP && metric != MCQ_SEARCH_COS) return MCQ_EINVAL;
-    if (Q >= kLimit || S >= kLimit || B >= kLimit || Bs >= kLimit) return MCQ_EUNSUPPORTED;
-    return 0;
+    return shortlist_limits(Q, S, B, Bs, k, metric);
 }
 
 template <typename T>
-int launch_short(const ShortPlan &p, hipStream_t st, const float *tables, int Q, const T *codes, const float *w, long B, int N,
+int launch_short(const PartPlan &p, hipStream_t st, const float *tables, int Q, const T *codes, const float *w, long B, int N,
                  int K, int k, int metric, const int64_t *shortlist, int S, const int64_t *row_of, long Bs, const float *bias,
                  float *ws_s, int *ws_i) {
     return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
@@ -1635,28 +1607,17 @@ int search_shortlist(const float *tables, long Q, const T *codes, const float *w
     if (Q > 0 && (!out_score || !out_index)) return MCQ_EINVAL;
     if (Q == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *ws_s = nullptr;
-    int *ws_i = nullptr;
-    int parts = 0;                                                        // lists per query; 0 (no candidate anywhere): the fill
+    PartPlan p{};                                                         // (no row can hold a candidate: the fill)
     if (S > 0 && B > 0 && Bs > 0) {
         if (!tables || !codes || !shortlist || !workspace) return MCQ_EINVAL;
-        if (!w && metric != MCQ_SEARCH_IP) return MCQ_EINVAL;              // (the inner product never reads w)
-        const int need = N * (int)sizeof(T) >= 16 ? 16 : N * (int)sizeof(T);   // a candidate's codes are loaded as one vector
-        if (reinterpret_cast<uintptr_t>(codes) % need != 0) return MCQ_EINVAL;
+        if (!w_ok(w, metric) || !codes_aligned(codes, N, sizeof(T))) return MCQ_EINVAL;
         if (reinterpret_cast<uintptr_t>(shortlist) % 8 != 0 || reinterpret_cast<uintptr_t>(row_of) % 8 != 0) return MCQ_EINVAL;
         if (reinterpret_cast<uintptr_t>(bias) % 4 != 0) return MCQ_EINVAL;
-        const ShortPlan p = short_plan(Q, S, N, K, k);
-        if (workspace_bytes < 2 * p.ws_half) return MCQ_EWORKSPACE;
-        ws_s = static_cast<float *>(workspace);                            // the workspace: scores, then positions
-        ws_i = reinterpret_cast<int *>(static_cast<char *>(workspace) + p.ws_half);
-        if (const int rc = launch_short<T>(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, shortlist, (int)S, row_of, Bs, bias,
-                                           ws_s, ws_i))
-            return rc;
-        parts = p.parts;
+        p = short_plan(Q, S, N, K, k);
     }
-    hipLaunchKernelGGL(k_search_wide_merge, dim3((unsigned)Q), dim3(64 * kWideWaves), 0, st, ws_s, ws_i, parts, k, out_score,
-                       out_index);
-    return launch_rc();
+    return topk_tail(p, workspace, workspace_bytes, st, Q, k, out_score, out_index, true, [&](float *ws_s, int *ws_i) {
+        return launch_short<T>(p, st, tables, (int)Q, codes, w, B, N, K, k, metric, shortlist, (int)S, row_of, Bs, bias, ws_s, ws_i);
+    });
 }
 
 }  // namespace
@@ -1693,8 +1654,7 @@ struct RangeArgsT {
     long capacity;
     const uint64_t *mask;                                                 // NULL: none (rule 12)
 };
-using RangeArgs = RangeArgsT<uint8_t>;
-using RangeArgs16 = RangeArgsT<uint16_t>;                                 // two-byte codes (include/mcq_code16.h)
+using RangeArgs = RangeArgsT<uint8_t>;                                    // (uint16_t: the entries of include/mcq_code16.h)
 
 // a sweep: FILL == false counts, FILL == true stores; a candidate's digits arrive in chunks of CH = min(N, 8)
 template <bool FILL>
@@ -1718,53 +1678,26 @@ int launch_range(const RangePlan &p, hipStream_t st, const RangeArgs &a) {
 }
 
 // the range search list by list (rules 17-20; mirrored by range_lists_plan of tests/search_range_lists_grid.py): the parts of
-// lists_plan, the LDS of k_search_lists, one int64 per (query, part, wave) of workspace.  A function of the call's shape alone.
-struct RangeListsPlan {
-    int parts;
-    size_t lds, ws_bytes;
-};
-
-RangeListsPlan range_lists_plan(long Q, int P, int N, int K) {
-    const int parts = lists_parts(Q);
+// lists_plan, the LDS of k_search_lists, one int64 per (query, part, wave) of workspace
+PartPlan range_lists_plan(long Q, int P, int N, int K) {
+    const int parts = part_count(Q, kListTargetBlocks, kScanMaxSlices);
     return {parts, (size_t)lists_lds_bytes(N * K, P), align256((size_t)Q * parts * kRangeListWaves * 8)};
 }
 
-// (a bias, li.bias != NULL, is a flag here as in launch_lists)
-template <bool FILL>
-int launch_range_lists(const RangeListsPlan &p, hipStream_t st, const RangeArgs &a, const ListsIn &li) {
+// (a bias, li.bias != NULL, is a flag here as in launch_lists.)  T = uint16_t (mcq_search_range_u16_count / _fill): the same
+// plan, the two-byte instantiations, and li.probes == NULL for the whole store as one list
+template <bool FILL, typename T>
+int launch_range_lists(const PartPlan &p, hipStream_t st, const RangeArgsT<T> &a, const ListsIn &li) {
     return pick<1, 2, 4, 8>(a.N < 8 ? a.N : 8, [&](auto ch) {
         return pick_bool(a.mask != nullptr, [&](auto masked) {
             return pick_bool(li.bias != nullptr, [&](auto biased) {
                 constexpr int CH = decltype(ch)::value;
                 constexpr bool MASKED = masked, BIAS = biased;
                 static bool allowed[64] = {};
-                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_lists<CH, FILL, MASKED, BIAS>),
-                                                     lists_lds_bytes(64 * 256, kListMaxProbes)))
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_lists<CH, FILL, MASKED, BIAS, T>),
+                                                     lists_lds_bytes(kTableRowsOf<T>, kListMaxProbes)))
                     return rc;
-                hipLaunchKernelGGL((k_range_lists<CH, FILL, MASKED, BIAS>), dim3((unsigned)a.Q * (unsigned)p.parts),
-                                   dim3(64 * kRangeListWaves), p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts,
-                                   li.list_offsets, li.L, li.probes, li.P, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity,
-                                   reinterpret_cast<const u64 *>(a.mask), li.bias);
-                return launch_rc();
-            });
-        });
-    });
-}
-
-// launch_range_lists over two-byte codes (mcq_search_range_u16_count / _fill): the same plan, the uint16_t instantiations.
-// li.probes == NULL: the whole store as one list.
-template <bool FILL>
-int launch_range_lists16(const RangeListsPlan &p, hipStream_t st, const RangeArgs16 &a, const ListsIn &li) {
-    return pick<1, 2, 4, 8>(a.N < 8 ? a.N : 8, [&](auto ch) {
-        return pick_bool(a.mask != nullptr, [&](auto masked) {
-            return pick_bool(li.bias != nullptr, [&](auto biased) {
-                constexpr int CH = decltype(ch)::value;
-                constexpr bool MASKED = masked, BIAS = biased;
-                static bool allowed[64] = {};
-                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_range_lists<CH, FILL, MASKED, BIAS, uint16_t>),
-                                                     lists_lds_bytes(kMaxRows, kListMaxProbes)))
-                    return rc;
-                hipLaunchKernelGGL((k_range_lists<CH, FILL, MASKED, BIAS, uint16_t>), dim3((unsigned)a.Q * (unsigned)p.parts),
+                hipLaunchKernelGGL((k_range_lists<CH, FILL, MASKED, BIAS, T>), dim3((unsigned)a.Q * (unsigned)p.parts),
                                    dim3(64 * kRangeListWaves), p.lds, st, a.tables, a.codes, a.w, a.B, a.N, a.K, a.metric, p.parts,
                                    li.list_offsets, li.L, li.probes, li.P, a.thr, a.ws, a.lims, a.out_s, a.out_i, a.capacity,
                                    reinterpret_cast<const u64 *>(a.mask), li.bias);
@@ -1789,27 +1722,21 @@ int range_check(const float *tables, long Q, const void *codes, const float *w, 
     return 0;
 }
 
-// the launch of one sweep, over the whole store or list by list (li).  *per: the workspace entries of a query.
-template <bool FILL>
-int launch_range_any(hipStream_t st, const RangeArgs &a, const ListsIn *li, int *per = nullptr) {
-    if (li) {
-        const RangeListsPlan p = range_lists_plan(a.Q, li->P, a.N, a.K);
-        if (per) *per = p.parts * kRangeListWaves;
-        return launch_range_lists<FILL>(p, st, a, *li);
+// the launch of one sweep, over the whole store or list by list (li).  *per: the workspace entries of a query.  Two-byte
+// codes go list by list always, the whole store as one list.
+template <bool FILL, typename T>
+int launch_range_any(hipStream_t st, const RangeArgsT<T> &a, const ListsIn *li, int *per = nullptr) {
+    if constexpr (sizeof(T) == 1) {
+        if (!li) {
+            const RangePlan p = range_plan(a.Q, a.B, a.N, a.K);
+            if (per) *per = p.slices * kRangeWaves;
+            return launch_range<FILL>(p, st, a);
+        }
     }
-    const RangePlan p = range_plan(a.Q, a.B, a.N, a.K);
-    if (per) *per = p.slices * kRangeWaves;
-    return launch_range<FILL>(p, st, a);
-}
-
-// two-byte codes: always list by list, the whole store as the one list of k_range_lists' probes == NULL
-template <bool FILL>
-int launch_range_any(hipStream_t st, const RangeArgs16 &a, const ListsIn *li, int *per = nullptr) {
-    const ListsIn whole{nullptr, 0, nullptr, 1};
-    const ListsIn &in = li ? *li : whole;
-    const RangeListsPlan p = range_lists_plan(a.Q, in.P, a.N, a.K);
+    const ListsIn &in = li ? *li : kWholeStore;
+    const PartPlan p = range_lists_plan(a.Q, in.P, a.N, a.K);
     if (per) *per = p.parts * kRangeListWaves;
-    return launch_range_lists16<FILL>(p, st, a, in);
+    return launch_range_lists<FILL, T>(p, st, a, in);
 }
 
 // every count entry point: the COUNT sweep, the counts -> offsets per query, the totals -> lims
@@ -2600,8 +2527,7 @@ int mcq_code_norms(const uint8_t *codes, long B, const void *prepared, int N, in
 }
 
 size_t mcq_search_workspace_bytes(long Q, long B, int N, int K, int k) {
-    if (Q <= 0 || B <= 0 || k < 1 || k > 64 || B > 0x7fffffffL || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
-    return 2 * scan_plan(Q, B, N, K, k).ws_half;
+    return sized(Q, B, 0x7fffffffL, N, K, k, 64) ? scan_plan(Q, B, N, K, k).ws_bytes : 256;
 }
 
 int mcq_code_rnorms(const uint8_t *codes, long B, const void *prepared, int N, int K, int D, float *rnorms_out, void *stream) {
@@ -2641,8 +2567,7 @@ int mcq_search_scan_masked(const float *tables, long Q, const uint8_t *codes, co
 
 // rules 13-16: the search list by list.  The size depends on neither B nor L: the parts of a query are cut on the device.
 size_t mcq_search_lists_workspace_bytes(long Q, int P, int N, int K, int k) {
-    if (Q <= 0 || P <= 0 || P > kListMaxProbes || k < 1 || k > 64 || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
-    return 2 * lists_plan(Q, P, N, K, k).ws_half;
+    return sized(Q, P, kListMaxProbes, N, K, k, 64) ? lists_plan(Q, P, N, K, k).ws_bytes : 256;
 }
 
 int mcq_search_scan_lists(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
@@ -2654,8 +2579,7 @@ int mcq_search_scan_lists(const float *tables, long Q, const uint8_t *codes, con
 
 // ---- range search over stored codes: mcq_range_kernels.h (rules 7-9 of include/mcq.h)
 size_t mcq_search_range_workspace_bytes(long Q, long B, int N, int K) {
-    if (Q <= 0 || B <= 0 || B > 0x7fffffffL || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
-    return range_plan(Q, B, N, K).ws_bytes;
+    return sized(Q, B, 0x7fffffffL, N, K, 1, 1) ? range_plan(Q, B, N, K).ws_bytes : 256;
 }
 
 int mcq_search_range_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int metric,
@@ -2686,8 +2610,7 @@ int mcq_search_range_fill_masked(const float *tables, long Q, const uint8_t *cod
 
 // ---- rules 17-20: the range search list by list.  The size depends on neither B nor L: the parts of a query are cut on the device.
 size_t mcq_search_range_lists_workspace_bytes(long Q, int P, int N, int K) {
-    if (Q <= 0 || P <= 0 || P > kListMaxProbes || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
-    return range_lists_plan(Q, P, N, K).ws_bytes;
+    return sized(Q, P, kListMaxProbes, N, K, 1, 1) ? range_lists_plan(Q, P, N, K).ws_bytes : 256;
 }
 
 int mcq_search_range_lists_count(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K,
@@ -2744,8 +2667,7 @@ int mcq_code_rnorms_based(const uint8_t *codes, long B, const void *prepared, in
 
 // ---- rules 24-27 (include/mcq_wide.h): the search past 64 neighbours, 1 <= k <= 1,024
 size_t mcq_search_wide_workspace_bytes(long Q, long B, int N, int K, int k) {
-    if (Q <= 0 || B <= 0 || k < 1 || k > kWideMaxK || B > 0x7fffffffL || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
-    return 2 * wide_plan(Q, 1, N, K, k).ws_half;
+    return sized(Q, B, 0x7fffffffL, N, K, k, kWideMaxK) ? wide_plan(Q, 1, N, K, k).ws_bytes : 256;
 }
 
 int mcq_search_wide(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k, int metric,
@@ -2756,8 +2678,7 @@ int mcq_search_wide(const float *tables, long Q, const uint8_t *codes, const flo
 }
 
 size_t mcq_search_wide_lists_workspace_bytes(long Q, int P, int N, int K, int k) {
-    if (Q <= 0 || P <= 0 || P > kListMaxProbes || k < 1 || k > kWideMaxK || Q > 0x7fffffffL || search_domain(N, K, 1) != 0) return 256;
-    return 2 * wide_plan(Q, P, N, K, k).ws_half;
+    return sized(Q, P, kListMaxProbes, N, K, k, kWideMaxK) ? wide_plan(Q, P, N, K, k).ws_bytes : 256;
 }
 
 int mcq_search_wide_lists(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,
@@ -2771,7 +2692,7 @@ int mcq_search_wide_lists(const float *tables, long Q, const uint8_t *codes, con
 // ---- rules 28-31 (include/mcq_rerank.h): the exact re-ranking of a shortlist
 size_t mcq_rerank_workspace_bytes(long Q, long S, int D, int k) {
     if (Q <= 0 || S <= 0 || rerank_domain(Q, S, 0, 0, D, k, MCQ_SEARCH_L2) != 0) return 256;
-    return 2 * rerank_plan(Q, S, D, k).ws_half;
+    return rerank_plan(Q, S, D, k).ws_bytes;
 }
 
 int mcq_rerank(const void *queries, int queries_half, long Q, const void *vectors, int vectors_half, long B, int D,
@@ -2797,8 +2718,7 @@ int mcq_code_norms_u16(const uint16_t *codes, long B, const void *prepared, int 
 }
 
 size_t mcq_search_topk_u16_workspace_bytes(long Q, int P, int N, int K, int k) {
-    if (Q <= 0 || P <= 0 || P > kListMaxProbes || k < 1 || k > kWideMaxK || Q > 0x7fffffffL || code16_domain(N, K, 1) != 0) return 256;
-    return 2 * wide_plan(Q, P, N, K, k).ws_half;
+    return sized(Q, P, kListMaxProbes, N, K, k, kWideMaxK, 2) ? wide_plan(Q, P, N, K, k).ws_bytes : 256;
 }
 
 int mcq_search_topk_u16(const float *tables, long Q, const uint16_t *codes, const float *w, long B, int N, int K, int k, int metric,
@@ -2811,8 +2731,7 @@ int mcq_search_topk_u16(const float *tables, long Q, const uint16_t *codes, cons
 }
 
 size_t mcq_search_range_u16_workspace_bytes(long Q, int P, int N, int K) {
-    if (Q <= 0 || P <= 0 || P > kListMaxProbes || Q > 0x7fffffffL || code16_domain(N, K, 1) != 0) return 256;
-    return range_lists_plan(Q, P, N, K).ws_bytes;
+    return sized(Q, P, kListMaxProbes, N, K, 1, 1, 2) ? range_lists_plan(Q, P, N, K).ws_bytes : 256;
 }
 
 int mcq_search_range_u16_count(const float *tables, long Q, const uint16_t *codes, const float *w, long B, int N, int K, int metric,
@@ -2836,7 +2755,7 @@ int mcq_search_range_u16_fill(const float *tables, long Q, const uint16_t *codes
 // ---- rules 36-39 (include/mcq_shortlist.h): the search over a shortlist
 size_t mcq_search_shortlist_workspace_bytes(long Q, long S, int N, int K, int k) {
     if (Q <= 0 || S <= 0 || short_domain(Q, S, 0, 0, N, K, k, MCQ_SEARCH_L2, 2) != 0) return 256;
-    return 2 * short_plan(Q, S, N, K, k).ws_half;
+    return short_plan(Q, S, N, K, k).ws_bytes;
 }
 
 int mcq_search_shortlist(const float *tables, long Q, const uint8_t *codes, const float *w, long B, int N, int K, int k,

@@ -334,30 +334,40 @@ class SearchMixin:
         q2d = queries.detach().reshape(-1, self.dim).to(torch.float32)
         return tables, flat, w, (q2d * q2d).sum(dim=1, keepdim=True), lists
 
-    def _run(self, tables: Tensor, codes: Tensor, w: Tensor, metric: str, mask, lists, k: int = None, thr: Tensor = None,
-             max_results: int = None, wide: bool = False):
-        """The one call path into the library, behind _search_scan (k given), _search_range (thr given) and
-        _search_wide_scan (k given, wide), whose docstrings say what comes back.  metric, mask and lists have passed
-        _checked, and `lists` is what it returned."""
+    def _store_operands(self, tables: Tensor, codes: Tensor, w: Tensor, metric: str, *others):
+        """What _run and _search_shortlist_scan hand the library alike: tables fp32 (Q, N, K), the codes (B, N) contiguous on a
+        16-byte boundary, the per-candidate array fp32 (B,) -- None under "ip", required under the other metrics -- and
+        whether the store holds two-byte codes.  `others`: what else the call reads, for the device check.
+        -> (tables, codes, w, two)"""
         N, K = self.num_codebooks, self.codebook_size
         if metric == "ip":
             w = None
         elif w is None:
             raise ValueError(f"metric {metric!r} needs the per-candidate array")
-        _on_device(tables, codes, w, thr, mask, *(lists or ()))
+        _on_device(tables, codes, w, *others)
         tables = tables.detach().to(torch.float32).contiguous()
         if w is not None:
             w = w.detach().to(torch.float32).contiguous()
         codes = codes.contiguous()
         if codes.data_ptr() % 16:
             codes = codes.clone()
-        Q, B, dev = tables.shape[0], codes.shape[0], tables.device
+        Q, B = tables.shape[0], codes.shape[0]
         # a store of two-byte codes (include/mcq_code16.h): the public calls make one iff codebook_size > 256 (_unpacked_codes);
         # here the dtype decides, so that _search_scan and _search_range can hold the two kinds against each other at K <= 256
         two = codes.dtype == torch.int16
         assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N)
         assert two or (codes.dtype == torch.uint8 and K <= 256)
         assert w is None or tuple(w.shape) == (B,)
+        return tables, codes, w, two
+
+    def _run(self, tables: Tensor, codes: Tensor, w: Tensor, metric: str, mask, lists, k: int = None, thr: Tensor = None,
+             max_results: int = None, wide: bool = False):
+        """The one call path into the library, behind _search_scan (k given), _search_range (thr given) and
+        _search_wide_scan (k given, wide), whose docstrings say what comes back.  metric, mask and lists have passed
+        _checked, and `lists` is what it returned."""
+        N, K = self.num_codebooks, self.codebook_size
+        tables, codes, w, two = self._store_operands(tables, codes, w, metric, thr, mask, *(lists or ()))
+        Q, B, dev = tables.shape[0], codes.shape[0], tables.device
         has = {"bias": lists is not None and len(lists) == 3, "lists": lists is not None, "mask": mask is not None,
                "metric": metric != "l2", None: True}
         first, scan, scan_bytes, count, fill, range_bytes = next(row for row in _ENTRIES if has[row[0]])
@@ -511,23 +521,10 @@ class SearchMixin:
         The dtype of `codes` decides the entry, as in _run."""
         N, K = self.num_codebooks, self.codebook_size
         check_metric(metric)
-        if metric == "ip":
-            w = None
-        elif w is None:
-            raise ValueError(f"metric {metric!r} needs the per-candidate array")
-        _on_device(tables, codes, w, shortlist, row_of, bias)
-        tables = tables.detach().to(torch.float32).contiguous()
-        if w is not None:
-            w = w.detach().to(torch.float32).contiguous()
-        codes = codes.contiguous()
-        if codes.data_ptr() % 16:
-            codes = codes.clone()
+        tables, codes, w, two = self._store_operands(tables, codes, w, metric, shortlist, row_of, bias)
         shortlist = shortlist.detach().contiguous()
         Q, B, S, dev = tables.shape[0], codes.shape[0], shortlist.shape[1], tables.device
-        two = codes.dtype == torch.int16
-        assert tuple(tables.shape) == (Q, N, K) and tuple(codes.shape) == (B, N) and tuple(shortlist.shape) == (Q, S)
-        assert two or (codes.dtype == torch.uint8 and K <= 256)
-        assert shortlist.dtype == torch.int64 and (w is None or tuple(w.shape) == (B,))
+        assert tuple(shortlist.shape) == (Q, S) and shortlist.dtype == torch.int64
         if row_of is not None:
             row_of = row_of.detach().contiguous()
             assert row_of.dtype == torch.int64 and row_of.ndim == 1

@@ -251,7 +251,8 @@ def test_launch_wide_selects_exactly_the_cells_the_gpu_test_launches():
         src = f.read()
     body = src[src.index("int launch_wide("):]
     body = body[:body.index("\n}\n")]
-    assert "li.bias != nullptr" not in body and "k_search_wide<NN, M, MASKED>" in body      # the bias is no template axis
+    # the bias is no template axis: the codebook count, the metric, the mask, and the code type of launch_wide<T>
+    assert "li.bias != nullptr" not in body and "k_search_wide<NN, M, MASKED, T>" in body and "k_search_wide<NN, M, MASKED, T," not in body
     # the parsed launchers and the cap of the older entries stand as they stood
     assert src.count("    if (k > 64) return MCQ_EUNSUPPORTED;\n") == 1
 
