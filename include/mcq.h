@@ -24,6 +24,24 @@
  *    cannot be made, gets the one-stream sequence (include/mcq_lanes.h);
  *  - return value: 0 = ok; MCQ_E* < 0 = rejected argument; > 0 = hipError_t of a
  *    failed launch.  Nothing is thrown across the boundary.
+ *  - WORKSPACES.  Every entry of this header and of its companions (mcq_residual.h, mcq_wide.h, mcq_code16.h,
+ *    mcq_shortlist.h, mcq_rerank.h, mcq_probe.h) that takes `void *workspace, size_t workspace_bytes` keeps these four
+ *    promises (tests/test_gpu_workspace_contract.py holds each entry to them between guard bands):
+ *      a. the bytes its size query returns for the call's arguments are enough, exactly: no byte in front of `workspace`
+ *         or from workspace + workspace_bytes on is read or written, and no byte outside an output's documented extent is
+ *         written.  Size queries return at least 256, and 256 for arguments outside the entry's domain; those of the search
+ *         entries are multiples of 256, mcq_encode_workspace_bytes, mcq_loss_workspace_bytes and
+ *         mcq_weight_grad_workspace_bytes are not rounded;
+ *      b. a workspace is SCRATCH: what it holds on entry -- zeros, NaN patterns, another call's or another shape's leftovers --
+ *         changes no result, bit for bit.  Whatever a call reads from it, it wrote before (counters included).  The one
+ *         exception is by design: the fill call of a range search reads what the count call with the same arguments left;
+ *      c. every `const` pointer is read only (`prepared`, tables, codes, w, masks, offsets, probes, biases, thresholds,
+ *         shortlists, frames, logits, indexes);
+ *      d. a call that returns an MCQ_E* code -- MCQ_EWORKSPACE for a workspace one byte short included -- has touched
+ *         neither the workspace nor an output nor an input: every check precedes the first launch.  An empty call
+ *         (B == 0, or Q == 0 where the entry defines it) returns 0 and leaves the workspace as it was; what it writes to
+ *         its outputs is said at the entry.
+ *    One workspace serves one call at a time: calls that share it must be ordered on one stream.
  *  - supported domain: codebook_size K a power of two in [16, 1024], num_codebooks N
  *    a power of two, N <= 64, N*K <= 16384 (the reference's trainer produces at most 64 x 16 and 32 x 256:
  *    bytes_per_frame <= 32, quantization/quantization.py:614; `prepared` holds the N*K x N*K Gram matrix).
@@ -122,7 +140,10 @@ int mcq_prepare_params(const float *centers, const float *centers_scale, const f
  *   out_u8 : uint8 [B][N / pack]     -- encode(as_bytes=True) (:266-272), where
  *            pack = 2 when K == 16 (low nibble = even codebook), else 1.
  * workspace: device scratch of at least mcq_encode_workspace_bytes(B, N, K, D)
- * bytes (the batch is processed in chunks that fit; any B >= 0 is accepted).   */
+ * bytes (the batch is processed in chunks that fit; any B >= 0 is accepted), under the WORKSPACES promises above: a
+ * smaller one serves as long as it holds one chunk of 128 vectors (or the whole batch); below that the call returns
+ * MCQ_EWORKSPACE and has touched nothing.  B == 0 returns 0 and writes nothing.  The same holds for mcq_encode_ex,
+ * mcq_refine_indexes, mcq_logits_refine and mcq_logits_refine_codes, which take the same workspace.                 */
 size_t mcq_encode_workspace_bytes(long B, int N, int K, int D);
 int mcq_encode(const float *x, long B, const void *prepared, float lscale_exp, int N, int K, int D,
                int refine_iters, uint8_t *out_u8, int64_t *out_i64, void *workspace,
@@ -202,7 +223,9 @@ int mcq_logits_refine_codes(const float *x, long B, const void *prepared, float 
 
 /* Log-softmax statistics of logits [B][N*K] against indexes int64 [B][N] (:221-240):
  *   lse[b][n] = logsumexp_k;  chosen_sum[n] = sum_b (logit[b][n][idx] - lse);
- *   prob_sum[n][k] = sum_b softmax;  count[n][k] = #{b: idx[b][n] == k}.                       */
+ *   prob_sum[n][k] = sum_b softmax;  count[n][k] = #{b: idx[b][n] == k}.
+ * workspace >= mcq_loss_workspace_bytes(B, N, K): per-chunk partial sums of the batch, added in a fixed order (WORKSPACES above:
+ * scratch, exact size, MCQ_EWORKSPACE before anything is written).  B <= 0 is MCQ_EINVAL: there is no empty call.       */
 size_t mcq_loss_workspace_bytes(long B, int N, int K);
 int mcq_loss_fwd(const float *logits, const int64_t *idx, long B, int N, int K, float *lse, float *chosen_sum,
                  float *prob_sum, float *count, void *workspace, size_t workspace_bytes, void *stream);
@@ -237,7 +260,9 @@ int mcq_recon_fwd(const float *x, const int64_t *idx, long B, const void *prepar
  *   s = exp(10*logits_scale) read from DEVICE memory (scale_dev).  Splits of the batch whose partial tiles (workspace) are
  *   added in a fixed order; fp32 MFMA, or -- M and D multiples of 128, M >= 1024, B >= 2048 -- six bf16 piece products per
  *   multiply-add (each operand as three bf16 pieces: fp32-grade, 1e-6 of the largest entry against the fp64 product).
- *   Deterministic; not part of the bit-exact contract of the index search.
+ *   Deterministic; not part of the bit-exact contract of the index search.  workspace >= mcq_weight_grad_workspace_bytes(B, M, D),
+ *   sized for the split count of the fp32 kernel; the bf16-piece kernel takes no more splits than that.  Every plane a
+ *   call adds up it wrote itself (WORKSPACES above).  B, M or D <= 0 is MCQ_EINVAL: there is no empty call.
  * mcq_adam_step: torch.optim.Adam's update (weight decay as L2 term, no amsgrad) on one flat bucket of n floats:
  *   parameters p, gradients g, moments m / v; bias_correction1 = 1 - beta1^t and sqrt(1 - beta2^t) formed by the caller.
  * mcq_loss_head: head[4] = {sum num_part, sum den_part, sum chosen_n, batch}: mcq_loss_tail's `sums` from the
@@ -508,7 +533,8 @@ int mcq_search_range_lists_fill(const float *tables, long Q, const uint8_t *code
 
 /* ---- test / profiling hooks -------------------------------------------------
  * Logits of Quantizer._logits (:277-279) for a batch, fp32 [B][N*K]; used by the
- * parity tests to localise a divergence.                                       */
+ * parity tests to localise a divergence.  workspace: the limb planes of the frames
+ * (WORKSPACES above); B == 0 returns 0 and writes nothing, as for mcq_logits_argmax.   */
 size_t mcq_logits_workspace_bytes(long B, int N, int D);   /* also what mcq_logits_argmax needs */
 int mcq_logits(const float *x, long B, const void *prepared, float lscale_exp, int N, int K, int D,
                float *out, void *workspace, size_t workspace_bytes, void *stream);

@@ -30,7 +30,9 @@
  *      and a range call lists the hits of a query in ascending position (rule 8).  There is one top-k entry for every k: at
  *      k <= 64 its result has the bits the narrow one-byte entries give on the same digits (rule 26).  The workspace queries
  *      take P, the probes per query, 1 for a call over the whole store; they are functions of the call's shape alone and
- *      answer 256 outside the domain.   */
+ *      answer 256 outside the domain.
+ * Workspaces: the four promises of include/mcq.h, "WORKSPACES" (exact size, scratch contents, const inputs, a refused call
+ * touches nothing), hold for every entry declared here. */
 #ifndef MCQ_CODE16_H
 #define MCQ_CODE16_H
 

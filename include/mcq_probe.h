@@ -3,7 +3,9 @@
  * A companion of include/mcq.h (which it includes): the same library, the same conventions -- borrowed device pointers, calls
  * that enqueue on the given stream and return, 0 / MCQ_E* / hipError_t as the return value --, and the same ABI version.  The
  * entries here run one step of the encode through the launcher the encode itself uses, on inputs the caller supplies; no product
- * code needs them.  quantization_amd/_lib.py binds them in PROBE_SIGNATURES, beside the SIGNATURES of mcq.h.                  */
+ * code needs them.  quantization_amd/_lib.py binds them in PROBE_SIGNATURES, beside the SIGNATURES of mcq.h.
+ * Workspaces: the four promises of include/mcq.h, "WORKSPACES" (exact size, scratch contents, const inputs, a refused call
+ * touches nothing), hold for every entry declared here. */
 #ifndef MCQ_PROBE_H
 #define MCQ_PROBE_H
 

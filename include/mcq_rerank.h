@@ -40,7 +40,9 @@
  *      position have one score, so which of them is listed first cannot be told).
  *  31. the workspace: mcq_rerank_workspace_bytes(Q, S, D, k), a function of those four alone, 256 outside the domain of
  *      rule 28 or where Q or S is 0; a workspace smaller than that is MCQ_EWORKSPACE.  It holds k (score, position) pairs
- *      per query and part.   */
+ *      per query and part.
+ * Workspaces: the four promises of include/mcq.h, "WORKSPACES" (exact size, scratch contents, const inputs, a refused call
+ * touches nothing), hold for every entry declared here. */
 #ifndef MCQ_RERANK_H
 #define MCQ_RERANK_H
 

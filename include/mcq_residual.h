@@ -4,7 +4,9 @@
  * that enqueue on the given stream and return, 0 / MCQ_E* / hipError_t as the return value --, and the same ABI version.  It
  * holds the entry points an inverted file over residual codes needs beside those of mcq.h's sections "search list by list"
  * and "range search list by list", and rules 21-23 of the contract that mcq.h numbers 1-20.
- * quantization_amd/_lib.py binds these entries in RESIDUAL_SIGNATURES, beside the SIGNATURES of mcq.h.                      */
+ * quantization_amd/_lib.py binds these entries in RESIDUAL_SIGNATURES, beside the SIGNATURES of mcq.h.
+ * Workspaces: the four promises of include/mcq.h, "WORKSPACES" (exact size, scratch contents, const inputs, a refused call
+ * touches nothing), hold for every entry declared here. */
 #ifndef MCQ_RESIDUAL_H
 #define MCQ_RESIDUAL_H
 

@@ -43,7 +43,9 @@
  *      the candidates stand in the row (given equal biases).
  *  39. the workspace: mcq_search_shortlist_workspace_bytes(Q, S, N, K, k), a function of those five alone and the same for
  *      both entries; 256 outside the domain of rule 36 (that of the two-byte entry, which contains the other) or where Q or
- *      S is 0; a workspace smaller than that is MCQ_EWORKSPACE.  It holds k (score, position) pairs per query and part.   */
+ *      S is 0; a workspace smaller than that is MCQ_EWORKSPACE.  It holds k (score, position) pairs per query and part.
+ * Workspaces: the four promises of include/mcq.h, "WORKSPACES" (exact size, scratch contents, const inputs, a refused call
+ * touches nothing), hold for every entry declared here. */
 #ifndef MCQ_SHORTLIST_H
 #define MCQ_SHORTLIST_H
 

@@ -25,7 +25,9 @@
  *      the bits of the older entries' result.
  *  27. the workspace: mcq_search_wide_workspace_bytes(Q, B, N, K, k) and mcq_search_wide_lists_workspace_bytes(Q, P, N, K, k),
  *      functions of the call's shape alone, 256 outside the domain (as rules 5 and 16 have it, with k up to 1,024); a
- *      workspace smaller than that is MCQ_EWORKSPACE, checked last.  It holds k (score, position) pairs per query and part.   */
+ *      workspace smaller than that is MCQ_EWORKSPACE, checked last.  It holds k (score, position) pairs per query and part.
+ * Workspaces: the four promises of include/mcq.h, "WORKSPACES" (exact size, scratch contents, const inputs, a refused call
+ * touches nothing), hold for every entry declared here. */
 #ifndef MCQ_WIDE_H
 #define MCQ_WIDE_H
 

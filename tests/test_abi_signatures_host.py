@@ -28,8 +28,9 @@ def _c_class(decl, is_return=False):
     return SCALARS[words[0]]
 
 
-def header_signatures(path=HEADER):
-    """{name: (return class, (parameter classes))} of every mcq_* function the header declares, in its order"""
+def header_declarations(path=HEADER):
+    """{name: (return text, [parameter texts])} of every mcq_* function the header declares, in its order: the text of the
+    header with the comments stripped, each parameter with its blanks collapsed"""
     text = open(path).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
@@ -37,9 +38,14 @@ def header_signatures(path=HEADER):
     out = {}
     for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(mcq_\w+)\s*\(([^()]*)\)\s*;", text):
         assert name not in out, name
-        params = [] if params.strip() == "void" else params.split(",")
-        out[name] = (_c_class(ret, is_return=True), tuple(_c_class(p) for p in params))
+        out[name] = (ret, [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")])
     return out
+
+
+def header_signatures(path=HEADER):
+    """{name: (return class, (parameter classes))} of every mcq_* function the header declares, in its order"""
+    return {name: (_c_class(ret, is_return=True), tuple(_c_class(p) for p in params))
+            for name, (ret, params) in header_declarations(path).items()}
 
 
 def _agree(want, got):

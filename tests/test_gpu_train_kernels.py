@@ -132,7 +132,13 @@ def test_loss_fwd_matches_float64(K, N, B, regime):
 
     a = run()
     _same(a, run(), "mcq_loss_fwd")
-    lse, ch, ps, cnt = a
+    hold_loss_fwd(z, idx, *a)
+
+
+def hold_loss_fwd(z, idx, lse, ch, ps, cnt):
+    """the four outputs of mcq_loss_fwd on logits z [B][N][K] and targets idx against fp64, within the bounds of
+    test_loss_fwd_matches_float64 (also what tests/test_gpu_workspace_contract.py holds the entry to)"""
+    (B, N, K), dev = z.shape, z.device
     lse_r, lp, p, e_lp, shift = _softmax_ref(z, K)
     valid = (idx >= 0).unsqueeze(-1)
     _check("mcq_loss_fwd", "lse", lse, lse_r.squeeze(-1),
@@ -441,7 +447,13 @@ def test_weight_grad_matches_float64(B, M, D):
 
     a = run()
     _same(a, run(), "mcq_weight_grad")
-    gW, gb = a
+    hold_weight_grad(G, x, s, *a)
+
+
+def hold_weight_grad(G, x, s, gW, gb):
+    """gW and gb of mcq_weight_grad against fp64, within the bounds of test_weight_grad_matches_float64 (also what
+    tests/test_gpu_workspace_contract.py holds the entry to)"""
+    (B, M), D = G.shape, x.shape[1]
     G64, x64, sv = G.double(), x.double(), float(s.double())
     Lw = tg.wgrad_chain(B, M, D)
     entry = "mcq_weight_grad" + ("[bf3]" if tg.wgrad_use_bf3(B, M, D) else "[f32]")
