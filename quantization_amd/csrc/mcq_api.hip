@@ -8,6 +8,7 @@
 #include "../../include/mcq_rerank.h"
 #include "../../include/mcq_code16.h"
 #include "../../include/mcq_shortlist.h"
+#include "../../include/mcq_coarse.h"
 #include "../../include/mcq_lanes.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
@@ -20,6 +21,7 @@
 #include "mcq_wide_kernels.h"
 #include "mcq_rerank_kernels.h"
 #include "mcq_shortlist_kernels.h"
+#include "mcq_coarse_kernels.h"
 #include "mcq_lanes.h"
 
 #include <cstdlib>
@@ -2770,6 +2772,98 @@ int mcq_search_shortlist_u16(const float *tables, long Q, const uint16_t *codes,
                              float *out_score, int64_t *out_index, void *workspace, size_t workspace_bytes, void *stream) {
     return search_shortlist(tables, Q, codes, w, B, N, K, k, metric, shortlist, S, row_of, Bs, bias, out_score, out_index, workspace,
                             workspace_bytes, stream);
+}
+
+// ---- rules 40-43 (include/mcq_coarse.h): the coarse probes.  (mcq_coarse_kernels.h; the part buffers are typed arguments of
+// the entry, so there is neither a workspace nor a plan the caller has to follow: mcq_coarse_parts only recommends)
+namespace {
+
+long coarse_tiles(long L) { return (L + kCoarseCT - 1) / kCoarseCT; }
+
+// rule 40's limits, in its order; 0 inside the domain
+int coarse_domain(long Q, long L, int D, int P, int metric) {
+    constexpr long kLimit = 0x7fffffffL;                                   // sizes stay below 2^31 - 1
+    if (D > kCoarseMaxD || P > kCoarseMaxP) return MCQ_EUNSUPPORTED;
+    if (D < 1 || P < 1 || Q < 0 || L < 0) return MCQ_EINVAL;
+    if (!metric_ok(metric)) return MCQ_EINVAL;
+    if (Q >= kLimit || L >= kLimit) return MCQ_EUNSUPPORTED;
+    return 0;
+}
+
+bool aligned4(const void *p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
+
+// parts == 0: L == 0, the tail alone
+int launch_coarse_finish(hipStream_t st, const float *part_score, const int32_t *part_list, int parts, int P, const float *queries,
+                         int Q, const float *centroids, int L, int D, int vec, int32_t *out_list, float *out_score,
+                         float *out_bias) {
+    return pick_bool(out_bias != nullptr, [&](auto bias) {
+        constexpr bool BIAS = bias;
+        static bool allowed[64] = {};
+        if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_coarse_finish<BIAS>),
+                                             coarse_finish_lds(BIAS, kCoarseMaxD, kCoarseMaxP)))
+            return rc;
+        hipLaunchKernelGGL((k_coarse_finish<BIAS>), dim3((unsigned)Q), dim3(64 * kWideWaves),
+                           coarse_finish_lds(BIAS && parts > 0, D, P), st, part_score, part_list, parts, P, queries, centroids, L, D,
+                           vec, out_list, out_score, out_bias);
+        return launch_rc();
+    });
+}
+
+}  // namespace
+
+int mcq_coarse_terms(const float *centroids, long L, int D, int metric, float *terms, void *stream) {
+    if (D > kCoarseMaxD) return MCQ_EUNSUPPORTED;
+    if (D < 1 || L < 0) return MCQ_EINVAL;
+    if (!metric_ok(metric)) return MCQ_EINVAL;
+    if (L >= 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (metric == MCQ_SEARCH_IP || L == 0) return 0;
+    if (!centroids || !terms || !aligned4(centroids) || !aligned4(terms)) return MCQ_EINVAL;
+    const dim3 grid((unsigned)((L + kCoarseWaves - 1) / kCoarseWaves)), block(64 * kCoarseWaves);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (metric == MCQ_SEARCH_L2) hipLaunchKernelGGL((k_coarse_terms<kMetricL2>), grid, block, 0, st, centroids, (int)L, D, terms);
+    else hipLaunchKernelGGL((k_coarse_terms<kMetricCos>), grid, block, 0, st, centroids, (int)L, D, terms);
+    return launch_rc();
+}
+
+long mcq_coarse_parts(long Q, long L, int D, int P) {
+    if (Q <= 0 || L <= 0 || coarse_domain(Q, L, D, P, MCQ_SEARCH_L2) != 0) return 1;
+    const long qt = (Q + kCoarseQT - 1) / kCoarseQT, ct = coarse_tiles(L);
+    if (qt >= kCoarseFullBlocks) return 1;
+    const long parts = (kCoarseTargetBlocks + qt - 1) / qt;
+    return parts < ct ? parts : ct;
+}
+
+int mcq_coarse_probe(const float *queries, long Q, const float *centroids, long L, int D, const float *terms, int P, int metric,
+                     long parts, int32_t *out_list, float *out_score, float *out_bias, float *part_score, int32_t *part_list,
+                     void *stream) {
+    if (const int rc = coarse_domain(Q, L, D, P, metric)) return rc;
+    if (Q > 0 && (!out_list || !out_score)) return MCQ_EINVAL;
+    if (Q == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (L == 0) {                                                          // no input is looked at: the tail
+        if (!aligned4(out_list) || !aligned4(out_score) || !aligned4(out_bias)) return MCQ_EINVAL;
+        return launch_coarse_finish(st, nullptr, nullptr, 0, P, nullptr, (int)Q, nullptr, 0, D, 0, out_list, out_score, out_bias);
+    }
+    const long qt = (Q + kCoarseQT - 1) / kCoarseQT;
+    if (parts < 1 || parts > coarse_tiles(L)) return MCQ_EINVAL;
+    if (qt * parts >= 0x7fffffffL) return MCQ_EUNSUPPORTED;                // (the grid of k_coarse_scores)
+    if (!queries || !centroids || !part_score || !part_list || (metric != MCQ_SEARCH_IP && !terms)) return MCQ_EINVAL;
+    if (!aligned4(out_list) || !aligned4(out_score) || !aligned4(out_bias) || !aligned4(queries) || !aligned4(centroids) ||
+        (metric != MCQ_SEARCH_IP && !aligned4(terms)) || !aligned4(part_score) || !aligned4(part_list))
+        return MCQ_EINVAL;
+    // one 16-byte load per staged group where every row of both operands starts on that boundary
+    const int vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(queries) % 16 == 0 && reinterpret_cast<uintptr_t>(centroids) % 16 == 0;
+    const int rc = pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        static bool allowed[64] = {};
+        if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_coarse_scores<M>), kCoarseLds)) return rc;
+        hipLaunchKernelGGL((k_coarse_scores<M>), dim3((unsigned)(qt * parts)), dim3(64 * kCoarseWaves), kCoarseLds, st, queries,
+                           (int)Q, centroids, (int)L, D, M == kMetricIP ? nullptr : terms, P, (int)parts, vec, part_score, part_list);
+        return launch_rc();
+    });
+    if (rc) return rc;
+    return launch_coarse_finish(st, part_score, part_list, (int)parts, P, queries, (int)Q, centroids, (int)L, D, vec, out_list,
+                                out_score, out_bias);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

@@ -44,6 +44,11 @@ all, is raw data touched.  The fine codes stay in the original order, as the raw
 search_shortlist (quantization_amd/search.py, mcq_search_shortlist) reads the fine codes of the named rows and nothing else;
 its values are the bits fine.search reports for the same (query, vector), and its indexes stay positions in list order.
 
+The coarse step in HIP (quantization_amd/coarse.py, mcq_coarse_probe): for fp32 device tensors and nprobe <= 128,
+coarse_probe(queries, centroids, nprobe, with_bias=True) returns the probes and their biases in one call, with ties to the
+lower list, and coarse_assign(x, centroids) is the `assign` of build_lists without a (B, L) matrix; probe_lists and probe_bias
+below are unchanged and remain the path for CPU tensors and larger nprobe.
+
 Where the coarse centroids come from (k-means over a sample, a trained layer) is the caller's business."""
 import torch
 from torch import Tensor
