@@ -11,6 +11,7 @@ from .hdf5_data import read_hdf5_data  # noqa: F401      (the data helper, quant
 from .ivf import build_lists, probe_lists, probe_bias, list_assign  # noqa: F401   (an inverted file over a store of codes: Quantizer.search_lists, range_search_lists)
 from .rerank import rerank  # noqa: F401   (the exact re-ranking of a shortlist: the step after search_wide / search_lists_wide)
 from .coarse import coarse_terms, coarse_probe, coarse_assign  # noqa: F401   (the coarse quantizer in HIP: probes, biases, assignment)
+from .kmeans import kmeans_step, coarse_train  # noqa: F401   (the coarse centroids themselves: a Lloyd step and the trainer, in HIP)
 
 __all__ = ["Quantizer", "QuantizerTrainer", "JointCodebookLoss", "read_hdf5_data", "build_lists", "probe_lists", "probe_bias", "list_assign", "rerank",
-           "coarse_terms", "coarse_probe", "coarse_assign"]
+           "coarse_terms", "coarse_probe", "coarse_assign", "kmeans_step", "coarse_train"]

@@ -49,7 +49,8 @@ coarse_probe(queries, centroids, nprobe, with_bias=True) returns the probes and 
 lower list, and coarse_assign(x, centroids) is the `assign` of build_lists without a (B, L) matrix; probe_lists and probe_bias
 below are unchanged and remain the path for CPU tensors and larger nprobe.
 
-Where the coarse centroids come from (k-means over a sample, a trained layer) is the caller's business."""
+Where the coarse centroids come from: coarse_train(sample, num_lists) (quantization_amd/kmeans.py, mcq_kmeans_assign and
+mcq_kmeans_update) is k-means under "l2" in HIP, the same bits on every run; a trained layer or another k-means serves as well."""
 import torch
 from torch import Tensor
 

@@ -1,0 +1,136 @@
+"""The coarse centroids of an inverted file, trained in HIP (include/mcq_kmeans.h rules 44-47): one Lloyd step is
+mcq_kmeans_assign -- the nearest centroid of every training vector on the fp32 matrix cores, the bits of coarse_assign, with
+nothing of size (B, L) -- then a stable sort by list in torch, then mcq_kmeans_update -- the members' mean per list as a float64
+sum over a fixed tree, gathered through `order` from the vectors where they lie.  No floating-point atomics: the centroids are a
+stated function of the vectors, the start and the number of steps, the same bits on every run.
+
+    centroids = coarse_train(sample, 1024, iters=10, seed=0)          # (1024, D) fp32
+    terms = coarse_terms(centroids)
+    assign = coarse_assign(x, centroids, terms=terms)                 # and on to build_lists, coarse_probe, search_lists
+
+    new, assign, counts, changed = kmeans_step(sample, centroids)     # a single step, for a loop of one's own
+
+"l2" only; there is no CPU path, and nothing is read back to the host."""
+import torch
+from torch import Tensor
+
+from .coarse import MAX_DIM, _checked, coarse_terms
+from .search import _call, _entry, _on_device
+
+__all__ = ["kmeans_step", "coarse_train"]
+SPLIT = 1e-4                # faiss's split of the largest list when another is empty
+
+
+def _checked_step(vectors, centroids, terms, prev_assign):
+    """shape and dtype errors of a step: looks at no data, so it runs before any device work, on CPU tensors too"""
+    L, D = _checked(vectors, centroids, "l2", terms, "vectors")
+    if vectors.ndim != 2:
+        raise ValueError(f"vectors: an fp32 (B, {D}) tensor, not {tuple(vectors.shape)}")
+    if L < 1:
+        raise ValueError("centroids: at least one list to assign to")
+    B = int(vectors.shape[0])
+    if B >= (1 << 31) - 1:
+        raise ValueError("vectors: fewer than 2^31 - 1 rows")
+    if prev_assign is not None and (not isinstance(prev_assign, Tensor) or prev_assign.dtype != torch.int32 or
+                                    tuple(prev_assign.shape) != (B,)):
+        raise ValueError(f"prev_assign: the int32 ({B},) tensor an earlier step returned, not "
+                         f"{getattr(prev_assign, 'dtype', type(prev_assign))} {tuple(getattr(prev_assign, 'shape', ()))}")
+    return B, L, D
+
+
+def _step(x, c, terms, prev, B, L, D):
+    """x (B, D) and c (L, D) contiguous on one device: the two entries and the sort between them"""
+    dev = x.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if terms is None:
+        terms = coarse_terms(c)
+    parts = int(_entry("mcq_kmeans_parts")(B, L, D))
+    assign = torch.empty((B,), dtype=torch.int32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    changed = None if prev is None else torch.empty((1,), dtype=torch.int32, device=dev)
+    part_score = torch.empty((B, parts), dtype=torch.float32, device=dev)
+    part_list = torch.empty((B, parts), dtype=torch.int32, device=dev)
+    _call("mcq_kmeans_assign", x.data_ptr(), B, c.data_ptr(), L, D, terms.data_ptr(), parts,
+          None if prev is None else prev.data_ptr(), assign.data_ptr(), score.data_ptr(),
+          None if changed is None else changed.data_ptr(), part_score.data_ptr(), part_list.data_ptr(), stream)
+    # the stable sort by list: ascending original position inside a list; a row assigned -1 sorts behind list L - 1
+    key = torch.where(assign < 0, torch.full_like(assign, L), assign).to(torch.int64)
+    keys, order = torch.sort(key, stable=True)
+    offsets = torch.searchsorted(keys, torch.arange(L + 1, dtype=torch.int64, device=dev))
+    new = torch.empty_like(c)
+    counts = torch.empty((L,), dtype=torch.int32, device=dev)
+    block_first = torch.empty((L + 1,), dtype=torch.int64, device=dev)
+    block_sums = torch.empty((int(_entry("mcq_kmeans_blocks")(B, L, D)),), dtype=torch.float64, device=dev)
+    _call("mcq_kmeans_update", x.data_ptr(), B, D, order.data_ptr(), offsets.data_ptr(), L, c.data_ptr(), new.data_ptr(),
+          counts.data_ptr(), block_first.data_ptr(), block_sums.data_ptr(), stream)
+    return new, assign, counts, changed
+
+
+def kmeans_step(vectors: Tensor, centroids: Tensor, terms: Tensor = None, prev_assign: Tensor = None):
+    """vectors (B, D) fp32, centroids (L, D) fp32, L >= 1, on the device -> (new_centroids (L, D) fp32, assign int32 (B,),
+    counts int32 (L,), changed): one Lloyd step under "l2".  assign is coarse_assign(vectors, centroids), ties to the lower
+    list, -1 for a row whose every score is NaN (it belongs to no list); new_centroids[l] is the mean of list l's rows, a
+    float64 sum in ascending row order over the fixed tree of include/mcq_kmeans.h rule 47, rounded once; a list without rows
+    keeps its centroid and counts 0.  changed is a device tensor of one int32, the number of rows whose assignment differs from
+    prev_assign (what an earlier step returned), or None without prev_assign.
+    terms: what coarse_terms(centroids) returned (computed here if None).  Not differentiable; no CPU fallback (McqError);
+    shape and dtype errors are ValueErrors raised before any device work; nothing is read back to the host."""
+    B, L, D = _checked_step(vectors, centroids, terms, prev_assign)
+    _on_device(vectors, centroids, terms, prev_assign)
+    with torch.no_grad(), torch.cuda.device(vectors.device):
+        return _step(vectors.detach().contiguous(), centroids.detach().contiguous(), terms,
+                     None if prev_assign is None else prev_assign.detach().contiguous(), B, L, D)
+
+
+def _reseed(centroids, counts):
+    """empty lists take a share of the largest ones: the j-th empty list, by index, becomes the centroid of the j-th largest
+    list (stable descending counts) times 1 + SPLIT, and that donor's own centroid is scaled by 1 - SPLIT.  Over L rows, on
+    the device, without a host read; no list empty: every row keeps its bits"""
+    L = counts.shape[0]
+    empty = counts == 0
+    donors = torch.sort(counts, descending=True, stable=True).indices
+    rank = torch.cumsum(empty, 0) - 1                        # j of an empty list
+    source = torch.where(empty, donors[rank.clamp(min=0)], torch.arange(L, device=counts.device))
+    gives = torch.empty_like(empty)
+    gives[donors] = torch.arange(L, device=counts.device) < empty.sum()
+    one = torch.ones((), dtype=torch.float32, device=counts.device)
+    scale = torch.where(empty, one * (1 + SPLIT), torch.where(gives, one * (1 - SPLIT), one))
+    return centroids[source] * scale[:, None]
+
+
+def coarse_train(vectors: Tensor, num_lists: int, iters: int = 10, seed: int = 0, init: Tensor = None) -> Tensor:
+    """vectors (B, D) fp32 on the device -> centroids (num_lists, D) fp32: `iters` Lloyd steps (kmeans_step) under "l2" from
+    `init` -- (num_lists, D) fp32 rows -- or, without one, from num_lists distinct rows of `vectors` drawn by a
+    torch.Generator seeded with `seed`.  After each step an empty list is reseeded from the largest (faiss's split, _reseed).
+    The same vectors, seed or init, and iters give the same bits on every run.  Argument errors are ValueErrors raised before
+    any device work; no CPU fallback (McqError); nothing is read back to the host."""
+    if isinstance(num_lists, bool) or not isinstance(num_lists, int) or num_lists < 1:
+        raise ValueError(f"num_lists = {num_lists!r}: a positive integer")
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise ValueError(f"iters = {iters!r}: a non-negative integer")
+    if not isinstance(vectors, Tensor) or vectors.ndim != 2 or vectors.dtype != torch.float32 or \
+            not 1 <= vectors.shape[1] <= MAX_DIM:
+        raise ValueError(f"vectors: an fp32 (B, D) tensor, 1 <= D <= {MAX_DIM}, not {getattr(vectors, 'dtype', type(vectors))} "
+                         f"{tuple(getattr(vectors, 'shape', ()))}")
+    B, D = int(vectors.shape[0]), int(vectors.shape[1])
+    if init is None:
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"seed = {seed!r}: an integer")
+        if num_lists > B:
+            raise ValueError(f"num_lists = {num_lists}: {B} vectors have no {num_lists} distinct rows to start from; pass init")
+    elif not isinstance(init, Tensor) or init.dtype != torch.float32 or tuple(init.shape) != (num_lists, D):
+        raise ValueError(f"init: an fp32 ({num_lists}, {D}) tensor, not {getattr(init, 'dtype', type(init))} "
+                         f"{tuple(getattr(init, 'shape', ()))}")
+    _checked_step(vectors, vectors[:1] if init is None else init, None, None)
+    _on_device(vectors, init)
+    with torch.no_grad(), torch.cuda.device(vectors.device):
+        x = vectors.detach().contiguous()
+        if init is None:
+            rows = torch.randperm(B, generator=torch.Generator().manual_seed(seed))[:num_lists]
+            centroids = x[rows.to(x.device)]
+        else:
+            centroids = init.detach().contiguous().clone()
+        for _ in range(iters):
+            centroids, _, counts, _ = _step(x, centroids, None, None, B, num_lists, D)
+            centroids = _reseed(centroids, counts)
+    return centroids
