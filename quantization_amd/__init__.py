@@ -12,6 +12,8 @@ from .ivf import build_lists, probe_lists, probe_bias, list_assign  # noqa: F401
 from .rerank import rerank  # noqa: F401   (the exact re-ranking of a shortlist: the step after search_wide / search_lists_wide)
 from .coarse import coarse_terms, coarse_probe, coarse_assign  # noqa: F401   (the coarse quantizer in HIP: probes, biases, assignment)
 from .kmeans import kmeans_step, coarse_train  # noqa: F401   (the coarse centroids themselves: a Lloyd step and the trainer, in HIP)
+from .half import coarse_assign_half, kmeans_step_half, coarse_train_half  # noqa: F401   (the same over an fp16 raw store, on the f16 matrix cores)
 
 __all__ = ["Quantizer", "QuantizerTrainer", "JointCodebookLoss", "read_hdf5_data", "build_lists", "probe_lists", "probe_bias", "list_assign", "rerank",
-           "coarse_terms", "coarse_probe", "coarse_assign", "kmeans_step", "coarse_train"]
+           "coarse_terms", "coarse_probe", "coarse_assign", "kmeans_step", "coarse_train",
+           "coarse_assign_half", "kmeans_step_half", "coarse_train_half"]

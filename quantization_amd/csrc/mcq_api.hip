@@ -10,6 +10,7 @@
 #include "../../include/mcq_shortlist.h"
 #include "../../include/mcq_coarse.h"
 #include "../../include/mcq_kmeans.h"
+#include "../../include/mcq_half.h"
 #include "../../include/mcq_lanes.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
@@ -24,6 +25,7 @@
 #include "mcq_shortlist_kernels.h"
 #include "mcq_coarse_kernels.h"
 #include "mcq_kmeans_kernels.h"
+#include "mcq_half_kernels.h"
 #include "mcq_lanes.h"
 
 #include <cstdlib>
@@ -2954,6 +2956,99 @@ int mcq_kmeans_update(const float *vectors, long B, int D, const int64_t *order,
         constexpr bool VEC = v;
         hipLaunchKernelGGL((k_kmeans_sums<VEC>), dim3((unsigned)cap, slabs), block, 0, st, vectors, B, D, order, list_offsets, (int)L,
                            block_first, cap, block_sums);
+        return launch_rc();
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_kmeans_mean, dim3((unsigned)L, slabs), block, 0, st, order, B, list_offsets, block_first, cap, block_sums, D,
+                       centroids_in, centroids_out, counts);
+    return launch_rc();
+}
+
+// ---- rules 48-51 (include/mcq_half.h): the Lloyd step over an fp16 raw store.  (mcq_half_kernels.h; the planes are a typed
+// scratch argument beside the part buffers)
+namespace {
+
+bool aligned2(const void *p) { return reinterpret_cast<uintptr_t>(p) % 2 == 0; }
+
+}  // namespace
+
+long mcq_kmeans_half_parts(long B, long L, int D) {
+    if (B <= 0 || kmeans_domain(B, L, D) != 0) return 1;
+    const long vt = (B + kKmVT - 1) / kKmVT, ct = (L + kKmCT - 1) / kKmCT;
+    if (vt >= kHalfFullBlocks) return 1;
+    const long parts = (kHalfFullBlocks + vt - 1) / vt;
+    return parts < ct ? parts : ct;
+}
+
+long mcq_kmeans_half_planes(long L, int D) {
+    if (kmeans_domain(0, L, D) != 0) return 0;
+    return 2 * L * half_padded_dim(D);
+}
+
+int mcq_kmeans_assign_half(const uint16_t *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
+                           const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
+                           int32_t *part_list, uint16_t *planes, void *stream) {
+    if (const int rc = kmeans_domain(B, L, D)) return rc;
+    if ((B > 0 && (!assign || !score)) || (prev_assign && !changed)) return MCQ_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 block(64 * kKmWaves);
+    if (B == 0) {
+        if (!prev_assign) return 0;
+        if (!aligned4(changed)) return MCQ_EINVAL;
+        hipLaunchKernelGGL(k_kmeans_finish, dim3(1), block, 0, st, nullptr, nullptr, 0, 0, prev_assign, nullptr, nullptr, changed);
+        return launch_rc();
+    }
+    const long vt = (B + kKmVT - 1) / kKmVT;
+    if (parts < 1 || parts > (L + kKmCT - 1) / kKmCT) return MCQ_EINVAL;
+    if (vt * parts >= 0x7fffffffL) return MCQ_EUNSUPPORTED;                // (the grid of k_kmeans_assign_half)
+    if (!vectors || !centroids || !terms || !part_score || !part_list || !planes) return MCQ_EINVAL;
+    if (!aligned2(vectors) || !aligned4(centroids) || !aligned4(terms) || !aligned4(prev_assign) || !aligned4(assign) ||
+        !aligned4(score) || (prev_assign && !aligned4(changed)) || !aligned4(part_score) || !aligned4(part_list) ||
+        reinterpret_cast<uintptr_t>(planes) % 16 != 0)
+        return MCQ_EINVAL;
+    // one 16-byte load per staged group of eight halves where every vector row starts on that boundary
+    const bool vec = D % 8 == 0 && reinterpret_cast<uintptr_t>(vectors) % 16 == 0;
+    const long groups = L * (half_padded_dim(D) / 8), want = (groups + 64 * kKmWaves - 1) / (64 * kKmWaves);
+    const int rc = pick_bool(vec, [&](auto v) {
+        constexpr bool VEC = v;
+        static bool allowed[64] = {};
+        if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_kmeans_assign_half<VEC>), kHalfLdsAll)) return rc;
+        hipLaunchKernelGGL(k_half_split, dim3((unsigned)(want < kHalfSplitBlocks ? want : kHalfSplitBlocks)), block, 0, st, centroids,
+                           (int)L, D, planes);
+        if (const int rc = launch_rc()) return rc;
+        hipLaunchKernelGGL((k_kmeans_assign_half<VEC>), dim3((unsigned)(vt * parts)), block, kHalfLdsAll, st, vectors, (int)B, planes,
+                           (int)L, D, terms, (int)parts, part_score, part_list, prev_assign ? changed : nullptr);
+        return launch_rc();
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_kmeans_finish, dim3((unsigned)((B + 64 * kKmWaves - 1) / (64 * kKmWaves))), block, 0, st, part_score,
+                       part_list, (int)B, (int)parts, prev_assign, assign, score, changed);
+    return launch_rc();
+}
+
+int mcq_kmeans_update_half(const uint16_t *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
+                           const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first,
+                           double *block_sums, void *stream) {
+    if (const int rc = kmeans_domain(B, L, D)) return rc;
+    const long cap = kmeans_max_blocks(B, L);
+    if (cap >= 0x7fffffffL) return MCQ_EUNSUPPORTED;                       // (the grid of k_kmeans_sums_half)
+    if (!list_offsets || !centroids_in || !centroids_out || !counts || !block_first || !block_sums ||
+        (B > 0 && (!vectors || !order)))
+        return MCQ_EINVAL;
+    if (!aligned2(vectors) || !aligned4(centroids_in) || !aligned4(centroids_out) || !aligned4(counts) || !aligned8(order) ||
+        !aligned8(list_offsets) || !aligned8(block_first) || !aligned8(block_sums))
+        return MCQ_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 block(64 * kKmWaves);
+    const unsigned slabs = (unsigned)((D + kKmSlab - 1) / kKmSlab);
+    hipLaunchKernelGGL(k_kmeans_scan, dim3(1), block, 0, st, list_offsets, (int)L, B, block_first);
+    if (const int rc = launch_rc()) return rc;
+    // one 8-byte load per group of four elements where every row starts on that boundary
+    const bool vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(vectors) % 8 == 0;
+    const int rc = pick_bool(vec, [&](auto v) {
+        constexpr bool VEC = v;
+        hipLaunchKernelGGL((k_kmeans_sums_half<VEC>), dim3((unsigned)cap, slabs), block, 0, st, vectors, B, D, order, list_offsets,
+                           (int)L, block_first, cap, block_sums);
         return launch_rc();
     });
     if (rc) return rc;

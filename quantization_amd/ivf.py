@@ -50,7 +50,10 @@ lower list, and coarse_assign(x, centroids) is the `assign` of build_lists witho
 below are unchanged and remain the path for CPU tensors and larger nprobe.
 
 Where the coarse centroids come from: coarse_train(sample, num_lists) (quantization_amd/kmeans.py, mcq_kmeans_assign and
-mcq_kmeans_update) is k-means under "l2" in HIP, the same bits on every run; a trained layer or another k-means serves as well."""
+mcq_kmeans_update) is k-means under "l2" in HIP, the same bits on every run; a trained layer or another k-means serves as well.
+A raw store kept in fp16 (what rerank reads) needs no fp32 copy for this: coarse_train_half(store16, num_lists) and
+coarse_assign_half(store16, centroids) (quantization_amd/half.py, mcq_kmeans_assign_half and mcq_kmeans_update_half) take
+torch.float16 rows against fp32 centroids on the f16 matrix cores; kmeans_step_half is the single step."""
 import torch
 from torch import Tensor
 
