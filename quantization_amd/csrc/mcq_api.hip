@@ -2780,21 +2780,24 @@ int mcq_search_shortlist_u16(const float *tables, long Q, const uint16_t *codes,
 
 // ---- rules 40-43 (include/mcq_coarse.h): the coarse probes.  (mcq_coarse_kernels.h; the part buffers are typed arguments of
 // the entry, so there is neither a workspace nor a plan the caller has to follow: mcq_coarse_parts only recommends)
+extern "C++" {                                                             // (a template has C++ linkage)
 namespace {
+
+// what the coarse probes, the Lloyd step and its fp16 form (rules 40-51) share: sizes and grids stay below 2^31 - 1, and a
+// null pointer is aligned
+constexpr long kSizeLimit = 0x7fffffffL;
+template <int N> bool aligned(const void *p) { return reinterpret_cast<uintptr_t>(p) % N == 0; }
 
 long coarse_tiles(long L) { return (L + kCoarseCT - 1) / kCoarseCT; }
 
-// rule 40's limits, in its order; 0 inside the domain
+// rule 40's limits, in its order; 0 inside the domain.  (mcq_coarse_terms has neither queries nor probes: Q = 0 and P = 1 pass)
 int coarse_domain(long Q, long L, int D, int P, int metric) {
-    constexpr long kLimit = 0x7fffffffL;                                   // sizes stay below 2^31 - 1
     if (D > kCoarseMaxD || P > kCoarseMaxP) return MCQ_EUNSUPPORTED;
     if (D < 1 || P < 1 || Q < 0 || L < 0) return MCQ_EINVAL;
     if (!metric_ok(metric)) return MCQ_EINVAL;
-    if (Q >= kLimit || L >= kLimit) return MCQ_EUNSUPPORTED;
+    if (Q >= kSizeLimit || L >= kSizeLimit) return MCQ_EUNSUPPORTED;
     return 0;
 }
-
-bool aligned4(const void *p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
 
 // parts == 0: L == 0, the tail alone
 int launch_coarse_finish(hipStream_t st, const float *part_score, const int32_t *part_list, int parts, int P, const float *queries,
@@ -2814,14 +2817,12 @@ int launch_coarse_finish(hipStream_t st, const float *part_score, const int32_t 
 }
 
 }  // namespace
+}  // extern "C++"
 
 int mcq_coarse_terms(const float *centroids, long L, int D, int metric, float *terms, void *stream) {
-    if (D > kCoarseMaxD) return MCQ_EUNSUPPORTED;
-    if (D < 1 || L < 0) return MCQ_EINVAL;
-    if (!metric_ok(metric)) return MCQ_EINVAL;
-    if (L >= 0x7fffffffL) return MCQ_EUNSUPPORTED;
+    if (const int rc = coarse_domain(0, L, D, 1, metric)) return rc;
     if (metric == MCQ_SEARCH_IP || L == 0) return 0;
-    if (!centroids || !terms || !aligned4(centroids) || !aligned4(terms)) return MCQ_EINVAL;
+    if (!centroids || !terms || !aligned<4>(centroids) || !aligned<4>(terms)) return MCQ_EINVAL;
     const dim3 grid((unsigned)((L + kCoarseWaves - 1) / kCoarseWaves)), block(64 * kCoarseWaves);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (metric == MCQ_SEARCH_L2) hipLaunchKernelGGL((k_coarse_terms<kMetricL2>), grid, block, 0, st, centroids, (int)L, D, terms);
@@ -2845,18 +2846,19 @@ int mcq_coarse_probe(const float *queries, long Q, const float *centroids, long 
     if (Q == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (L == 0) {                                                          // no input is looked at: the tail
-        if (!aligned4(out_list) || !aligned4(out_score) || !aligned4(out_bias)) return MCQ_EINVAL;
+        if (!aligned<4>(out_list) || !aligned<4>(out_score) || !aligned<4>(out_bias)) return MCQ_EINVAL;
         return launch_coarse_finish(st, nullptr, nullptr, 0, P, nullptr, (int)Q, nullptr, 0, D, 0, out_list, out_score, out_bias);
     }
     const long qt = (Q + kCoarseQT - 1) / kCoarseQT;
     if (parts < 1 || parts > coarse_tiles(L)) return MCQ_EINVAL;
-    if (qt * parts >= 0x7fffffffL) return MCQ_EUNSUPPORTED;                // (the grid of k_coarse_scores)
+    if (qt * parts >= kSizeLimit) return MCQ_EUNSUPPORTED;                 // (the grid of k_coarse_scores)
     if (!queries || !centroids || !part_score || !part_list || (metric != MCQ_SEARCH_IP && !terms)) return MCQ_EINVAL;
-    if (!aligned4(out_list) || !aligned4(out_score) || !aligned4(out_bias) || !aligned4(queries) || !aligned4(centroids) ||
-        (metric != MCQ_SEARCH_IP && !aligned4(terms)) || !aligned4(part_score) || !aligned4(part_list))
+    if (!aligned<4>(out_list) || !aligned<4>(out_score) || !aligned<4>(out_bias) || !aligned<4>(queries) ||
+        !aligned<4>(centroids) || (metric != MCQ_SEARCH_IP && !aligned<4>(terms)) || !aligned<4>(part_score) ||
+        !aligned<4>(part_list))
         return MCQ_EINVAL;
     // one 16-byte load per staged group where every row of both operands starts on that boundary
-    const int vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(queries) % 16 == 0 && reinterpret_cast<uintptr_t>(centroids) % 16 == 0;
+    const int vec = D % 4 == 0 && aligned<16>(queries) && aligned<16>(centroids);
     const int rc = pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
         constexpr int M = decltype(m)::value;
         static bool allowed[64] = {};
@@ -2870,26 +2872,24 @@ int mcq_coarse_probe(const float *queries, long Q, const float *centroids, long 
                                 out_score, out_bias);
 }
 
-// ---- rules 44-47 (include/mcq_kmeans.h): one Lloyd step over the coarse centroids.  (mcq_kmeans_kernels.h; the part buffers
-// and the block buffers are typed arguments, as those of the coarse probes)
+// ---- rules 44-51 (include/mcq_kmeans.h, include/mcq_half.h): one Lloyd step over the coarse centroids, from fp32 rows or from
+// an fp16 raw store.  (mcq_kmeans_kernels.h, mcq_half_kernels.h; the part buffers, the block buffers and the fp16 planes are
+// typed arguments, as those of the coarse probes.)  One path per entry pair: T = float or uint16_t is the type of a vector row
+extern "C++" {
 namespace {
 
-// rules 44 and 46, the limits both entries share, in their order; 0 inside the domain
+// rules 44 and 46, the limits every entry shares, in their order; 0 inside the domain
 int kmeans_domain(long B, long L, int D) {
-    constexpr long kLimit = 0x7fffffffL;
     if (D > kCoarseMaxD) return MCQ_EUNSUPPORTED;
     if (D < 1 || B < 0 || L < 1) return MCQ_EINVAL;
-    if (B >= kLimit || L >= kLimit) return MCQ_EUNSUPPORTED;
+    if (B >= kSizeLimit || L >= kSizeLimit) return MCQ_EUNSUPPORTED;
     return 0;
 }
 
 long kmeans_max_blocks(long B, long L) { return (B + kKmBlock - 1) / kKmBlock + L; }
 
-bool aligned8(const void *p) { return reinterpret_cast<uintptr_t>(p) % 8 == 0; }
-
-}  // namespace
-
-long mcq_kmeans_parts(long B, long L, int D) {
+// rule 44's recommendation; rule 48 takes the same formula (both assign kernels fill the chip with kKmFullBlocks vector tiles)
+long kmeans_parts(long B, long L, int D) {
     if (B <= 0 || kmeans_domain(B, L, D) != 0) return 1;
     const long vt = (B + kKmVT - 1) / kKmVT, ct = (L + kKmCT - 1) / kKmCT;
     if (vt >= kKmFullBlocks) return 1;
@@ -2897,157 +2897,87 @@ long mcq_kmeans_parts(long B, long L, int D) {
     return parts < ct ? parts : ct;
 }
 
-int mcq_kmeans_assign(const float *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
-                      const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
-                      int32_t *part_list, void *stream) {
+// rules 45 and 49.  float rows: `planes` is nullptr and not looked at
+template <typename T>
+int kmeans_assign(const T *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
+                  const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
+                  int32_t *part_list, uint16_t *planes, void *stream) {
+    constexpr bool HALF = sizeof(T) == 2;
     if (const int rc = kmeans_domain(B, L, D)) return rc;
     if ((B > 0 && (!assign || !score)) || (prev_assign && !changed)) return MCQ_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 block(64 * kKmWaves);
-    if (B == 0) {
+    if (B == 0) {                                                          // no input is looked at: the zero of `changed`
         if (!prev_assign) return 0;
-        if (!aligned4(changed)) return MCQ_EINVAL;
-        hipLaunchKernelGGL(k_kmeans_finish, dim3(1), block, 0, st, nullptr, nullptr, 0, 0, prev_assign, nullptr, nullptr, changed);
-        return launch_rc();
+        if (!aligned<4>(changed)) return MCQ_EINVAL;
+    } else {
+        const long vt = (B + kKmVT - 1) / kKmVT;
+        if (parts < 1 || parts > (L + kKmCT - 1) / kKmCT) return MCQ_EINVAL;
+        if (vt * parts >= kSizeLimit) return MCQ_EUNSUPPORTED;             // (the grid of the assign kernel)
+        if (!vectors || !centroids || !terms || !part_score || !part_list || (HALF && !planes)) return MCQ_EINVAL;
+        if (!aligned<sizeof(T)>(vectors) || !aligned<4>(centroids) || !aligned<4>(terms) || !aligned<4>(prev_assign) ||
+            !aligned<4>(assign) || !aligned<4>(score) || (prev_assign && !aligned<4>(changed)) || !aligned<4>(part_score) ||
+            !aligned<4>(part_list) || (HALF && !aligned<16>(planes)))
+            return MCQ_EINVAL;
+        const dim3 grid((unsigned)(vt * parts));
+        int32_t *zeroed = prev_assign ? changed : nullptr;
+        if constexpr (HALF) {
+            // one 16-byte load per staged group of eight halves where every vector row starts on that boundary
+            const bool vec = D % 8 == 0 && aligned<16>(vectors);
+            const long groups = L * (half_padded_dim(D) / 8), want = (groups + 64 * kKmWaves - 1) / (64 * kKmWaves);
+            const int rc = pick_bool(vec, [&](auto v) {
+                constexpr bool VEC = v;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_kmeans_assign_half<VEC>), kHalfLdsAll)) return rc;
+                hipLaunchKernelGGL(k_half_split, dim3((unsigned)(want < kHalfSplitBlocks ? want : kHalfSplitBlocks)), block, 0, st,
+                                   centroids, (int)L, D, planes);
+                if (const int rc = launch_rc()) return rc;
+                hipLaunchKernelGGL((k_kmeans_assign_half<VEC>), grid, block, kHalfLdsAll, st, vectors, (int)B, planes, (int)L, D,
+                                   terms, (int)parts, part_score, part_list, zeroed);
+                return launch_rc();
+            });
+            if (rc) return rc;
+        } else {
+            // one 16-byte load per staged group where every row of both operands starts on that boundary
+            const int vec = D % 4 == 0 && aligned<16>(vectors) && aligned<16>(centroids);
+            static bool allowed[64] = {};
+            if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_kmeans_assign), kKmLds)) return rc;
+            hipLaunchKernelGGL(k_kmeans_assign, grid, block, kKmLds, st, vectors, (int)B, centroids, (int)L, D, terms, (int)parts, vec,
+                               part_score, part_list, zeroed);
+            if (const int rc = launch_rc()) return rc;
+        }
     }
-    const long vt = (B + kKmVT - 1) / kKmVT;
-    if (parts < 1 || parts > (L + kKmCT - 1) / kKmCT) return MCQ_EINVAL;
-    if (vt * parts >= 0x7fffffffL) return MCQ_EUNSUPPORTED;                // (the grid of k_kmeans_assign)
-    if (!vectors || !centroids || !terms || !part_score || !part_list) return MCQ_EINVAL;
-    if (!aligned4(vectors) || !aligned4(centroids) || !aligned4(terms) || !aligned4(prev_assign) || !aligned4(assign) ||
-        !aligned4(score) || (prev_assign && !aligned4(changed)) || !aligned4(part_score) || !aligned4(part_list))
-        return MCQ_EINVAL;
-    const int vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(vectors) % 16 == 0 && reinterpret_cast<uintptr_t>(centroids) % 16 == 0;
-    static bool allowed[64] = {};
-    if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_kmeans_assign), kKmLds)) return rc;
-    hipLaunchKernelGGL(k_kmeans_assign, dim3((unsigned)(vt * parts)), block, kKmLds, st, vectors, (int)B, centroids, (int)L, D, terms,
-                       (int)parts, vec, part_score, part_list, prev_assign ? changed : nullptr);
-    if (const int rc = launch_rc()) return rc;
-    hipLaunchKernelGGL(k_kmeans_finish, dim3((unsigned)((B + 64 * kKmWaves - 1) / (64 * kKmWaves))), block, 0, st, part_score,
-                       part_list, (int)B, (int)parts, prev_assign, assign, score, changed);
+    // B == 0: one workgroup that looks at nothing but `changed`
+    hipLaunchKernelGGL(k_kmeans_finish, dim3(B == 0 ? 1u : (unsigned)((B + 64 * kKmWaves - 1) / (64 * kKmWaves))), block, 0, st,
+                       part_score, part_list, (int)B, B == 0 ? 0 : (int)parts, prev_assign, assign, score, changed);
     return launch_rc();
 }
 
-long mcq_kmeans_blocks(long B, long L, int D) {
-    if (kmeans_domain(B, L, D) != 0 || kmeans_max_blocks(B, L) >= 0x7fffffffL) return 0;
-    return kmeans_max_blocks(B, L) * D;
-}
-
-int mcq_kmeans_update(const float *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
-                      const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first, double *block_sums,
-                      void *stream) {
+// rules 47 and 51
+template <typename T>
+int kmeans_update(const T *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
+                  const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first, double *block_sums,
+                  void *stream) {
+    constexpr bool HALF = sizeof(T) == 2;
     if (const int rc = kmeans_domain(B, L, D)) return rc;
     const long cap = kmeans_max_blocks(B, L);
-    if (cap >= 0x7fffffffL) return MCQ_EUNSUPPORTED;                       // (the grid of k_kmeans_sums)
+    if (cap >= kSizeLimit) return MCQ_EUNSUPPORTED;                        // (the grid of k_kmeans_sums)
     if (!list_offsets || !centroids_in || !centroids_out || !counts || !block_first || !block_sums ||
         (B > 0 && (!vectors || !order)))
         return MCQ_EINVAL;
-    if (!aligned4(vectors) || !aligned4(centroids_in) || !aligned4(centroids_out) || !aligned4(counts) || !aligned8(order) ||
-        !aligned8(list_offsets) || !aligned8(block_first) || !aligned8(block_sums))
+    if (!aligned<sizeof(T)>(vectors) || !aligned<4>(centroids_in) || !aligned<4>(centroids_out) || !aligned<4>(counts) ||
+        !aligned<8>(order) || !aligned<8>(list_offsets) || !aligned<8>(block_first) || !aligned<8>(block_sums))
         return MCQ_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 block(64 * kKmWaves);
     const unsigned slabs = (unsigned)((D + kKmSlab - 1) / kKmSlab);
     hipLaunchKernelGGL(k_kmeans_scan, dim3(1), block, 0, st, list_offsets, (int)L, B, block_first);
     if (const int rc = launch_rc()) return rc;
-    // one 16-byte load per group of four elements where every row starts on that boundary
-    const bool vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(vectors) % 16 == 0;
+    // one load (16 bytes of fp32, 8 of fp16) per group of four elements where every row starts on that boundary
+    const bool vec = D % 4 == 0 && aligned<4 * sizeof(T)>(vectors);
     const int rc = pick_bool(vec, [&](auto v) {
         constexpr bool VEC = v;
-        hipLaunchKernelGGL((k_kmeans_sums<VEC>), dim3((unsigned)cap, slabs), block, 0, st, vectors, B, D, order, list_offsets, (int)L,
-                           block_first, cap, block_sums);
-        return launch_rc();
-    });
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_kmeans_mean, dim3((unsigned)L, slabs), block, 0, st, order, B, list_offsets, block_first, cap, block_sums, D,
-                       centroids_in, centroids_out, counts);
-    return launch_rc();
-}
-
-// ---- rules 48-51 (include/mcq_half.h): the Lloyd step over an fp16 raw store.  (mcq_half_kernels.h; the planes are a typed
-// scratch argument beside the part buffers)
-namespace {
-
-bool aligned2(const void *p) { return reinterpret_cast<uintptr_t>(p) % 2 == 0; }
-
-}  // namespace
-
-long mcq_kmeans_half_parts(long B, long L, int D) {
-    if (B <= 0 || kmeans_domain(B, L, D) != 0) return 1;
-    const long vt = (B + kKmVT - 1) / kKmVT, ct = (L + kKmCT - 1) / kKmCT;
-    if (vt >= kHalfFullBlocks) return 1;
-    const long parts = (kHalfFullBlocks + vt - 1) / vt;
-    return parts < ct ? parts : ct;
-}
-
-long mcq_kmeans_half_planes(long L, int D) {
-    if (kmeans_domain(0, L, D) != 0) return 0;
-    return 2 * L * half_padded_dim(D);
-}
-
-int mcq_kmeans_assign_half(const uint16_t *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
-                           const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
-                           int32_t *part_list, uint16_t *planes, void *stream) {
-    if (const int rc = kmeans_domain(B, L, D)) return rc;
-    if ((B > 0 && (!assign || !score)) || (prev_assign && !changed)) return MCQ_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 block(64 * kKmWaves);
-    if (B == 0) {
-        if (!prev_assign) return 0;
-        if (!aligned4(changed)) return MCQ_EINVAL;
-        hipLaunchKernelGGL(k_kmeans_finish, dim3(1), block, 0, st, nullptr, nullptr, 0, 0, prev_assign, nullptr, nullptr, changed);
-        return launch_rc();
-    }
-    const long vt = (B + kKmVT - 1) / kKmVT;
-    if (parts < 1 || parts > (L + kKmCT - 1) / kKmCT) return MCQ_EINVAL;
-    if (vt * parts >= 0x7fffffffL) return MCQ_EUNSUPPORTED;                // (the grid of k_kmeans_assign_half)
-    if (!vectors || !centroids || !terms || !part_score || !part_list || !planes) return MCQ_EINVAL;
-    if (!aligned2(vectors) || !aligned4(centroids) || !aligned4(terms) || !aligned4(prev_assign) || !aligned4(assign) ||
-        !aligned4(score) || (prev_assign && !aligned4(changed)) || !aligned4(part_score) || !aligned4(part_list) ||
-        reinterpret_cast<uintptr_t>(planes) % 16 != 0)
-        return MCQ_EINVAL;
-    // one 16-byte load per staged group of eight halves where every vector row starts on that boundary
-    const bool vec = D % 8 == 0 && reinterpret_cast<uintptr_t>(vectors) % 16 == 0;
-    const long groups = L * (half_padded_dim(D) / 8), want = (groups + 64 * kKmWaves - 1) / (64 * kKmWaves);
-    const int rc = pick_bool(vec, [&](auto v) {
-        constexpr bool VEC = v;
-        static bool allowed[64] = {};
-        if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_kmeans_assign_half<VEC>), kHalfLdsAll)) return rc;
-        hipLaunchKernelGGL(k_half_split, dim3((unsigned)(want < kHalfSplitBlocks ? want : kHalfSplitBlocks)), block, 0, st, centroids,
-                           (int)L, D, planes);
-        if (const int rc = launch_rc()) return rc;
-        hipLaunchKernelGGL((k_kmeans_assign_half<VEC>), dim3((unsigned)(vt * parts)), block, kHalfLdsAll, st, vectors, (int)B, planes,
-                           (int)L, D, terms, (int)parts, part_score, part_list, prev_assign ? changed : nullptr);
-        return launch_rc();
-    });
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_kmeans_finish, dim3((unsigned)((B + 64 * kKmWaves - 1) / (64 * kKmWaves))), block, 0, st, part_score,
-                       part_list, (int)B, (int)parts, prev_assign, assign, score, changed);
-    return launch_rc();
-}
-
-int mcq_kmeans_update_half(const uint16_t *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
-                           const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first,
-                           double *block_sums, void *stream) {
-    if (const int rc = kmeans_domain(B, L, D)) return rc;
-    const long cap = kmeans_max_blocks(B, L);
-    if (cap >= 0x7fffffffL) return MCQ_EUNSUPPORTED;                       // (the grid of k_kmeans_sums_half)
-    if (!list_offsets || !centroids_in || !centroids_out || !counts || !block_first || !block_sums ||
-        (B > 0 && (!vectors || !order)))
-        return MCQ_EINVAL;
-    if (!aligned2(vectors) || !aligned4(centroids_in) || !aligned4(centroids_out) || !aligned4(counts) || !aligned8(order) ||
-        !aligned8(list_offsets) || !aligned8(block_first) || !aligned8(block_sums))
-        return MCQ_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 block(64 * kKmWaves);
-    const unsigned slabs = (unsigned)((D + kKmSlab - 1) / kKmSlab);
-    hipLaunchKernelGGL(k_kmeans_scan, dim3(1), block, 0, st, list_offsets, (int)L, B, block_first);
-    if (const int rc = launch_rc()) return rc;
-    // one 8-byte load per group of four elements where every row starts on that boundary
-    const bool vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(vectors) % 8 == 0;
-    const int rc = pick_bool(vec, [&](auto v) {
-        constexpr bool VEC = v;
-        hipLaunchKernelGGL((k_kmeans_sums_half<VEC>), dim3((unsigned)cap, slabs), block, 0, st, vectors, B, D, order, list_offsets,
+        hipLaunchKernelGGL((k_kmeans_sums<HALF, VEC>), dim3((unsigned)cap, slabs), block, 0, st, vectors, B, D, order, list_offsets,
                            (int)L, block_first, cap, block_sums);
         return launch_rc();
     });
@@ -3055,6 +2985,49 @@ int mcq_kmeans_update_half(const uint16_t *vectors, long B, int D, const int64_t
     hipLaunchKernelGGL(k_kmeans_mean, dim3((unsigned)L, slabs), block, 0, st, order, B, list_offsets, block_first, cap, block_sums, D,
                        centroids_in, centroids_out, counts);
     return launch_rc();
+}
+
+}  // namespace
+}  // extern "C++"
+
+long mcq_kmeans_parts(long B, long L, int D) { return kmeans_parts(B, L, D); }
+
+long mcq_kmeans_half_parts(long B, long L, int D) { return kmeans_parts(B, L, D); }
+
+long mcq_kmeans_blocks(long B, long L, int D) {
+    if (kmeans_domain(B, L, D) != 0 || kmeans_max_blocks(B, L) >= kSizeLimit) return 0;
+    return kmeans_max_blocks(B, L) * D;
+}
+
+long mcq_kmeans_half_planes(long L, int D) {
+    if (kmeans_domain(0, L, D) != 0) return 0;
+    return 2 * L * half_padded_dim(D);
+}
+
+int mcq_kmeans_assign(const float *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
+                      const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
+                      int32_t *part_list, void *stream) {
+    return kmeans_assign(vectors, B, centroids, L, D, terms, parts, prev_assign, assign, score, changed, part_score, part_list,
+                         nullptr, stream);
+}
+
+int mcq_kmeans_assign_half(const uint16_t *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
+                           const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
+                           int32_t *part_list, uint16_t *planes, void *stream) {
+    return kmeans_assign(vectors, B, centroids, L, D, terms, parts, prev_assign, assign, score, changed, part_score, part_list,
+                         planes, stream);
+}
+
+int mcq_kmeans_update(const float *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
+                      const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first, double *block_sums,
+                      void *stream) {
+    return kmeans_update(vectors, B, D, order, list_offsets, L, centroids_in, centroids_out, counts, block_first, block_sums, stream);
+}
+
+int mcq_kmeans_update_half(const uint16_t *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
+                           const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first,
+                           double *block_sums, void *stream) {
+    return kmeans_update(vectors, B, D, order, list_offsets, L, centroids_in, centroids_out, counts, block_first, block_sums, stream);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector

@@ -1,8 +1,7 @@
 // mcq_half_kernels.h -- gfx950 kernels of the Lloyd step over an fp16 raw store (include/mcq_half.h, rules 48-51): the nearest
-// centroid of every fp16 vector on the f16 matrix cores, and the update's gather from fp16 rows.  The order (pair_less), the tile
-// plan, the meeting of the parts (k_kmeans_finish) and the update's scan and mean (k_kmeans_scan, k_kmeans_mean) are those of
-// mcq_kmeans_kernels.h, the row-bounded gather (rerank_row<true>, rerank_load<true, VEC>) that of mcq_rerank_kernels.h; nothing
-// of those files is changed.
+// centroid of every fp16 vector on the f16 matrix cores.  The order (pair_less), the tile plan and its recommended parts
+// (kKmFullBlocks), the meeting of the parts (k_kmeans_finish) and the whole update (k_kmeans_scan, k_kmeans_sums<true, VEC>,
+// k_kmeans_mean) are those of mcq_kmeans_kernels.h.
 //
 // k_half_split: fp32 centroids -> two fp16 planes [hi: L rows][lo: L rows] of Dp = 32 ceil(D / 32) halves each, once per call:
 // hi = f16(c), lo = f16((c - f32(hi)) * 2^11), an element past D is +0.0 in both.  One thread per group of 8 elements (one
@@ -34,23 +33,23 @@
 // for a store that is not 16-byte aligned or has D % 8 != 0.  profiles/kmeans_half_isa.txt has the compiler's report.  A chunk
 // of 64 halves at a pitch of 72 would take 110,592 B and leave every store one workgroup per compute unit with nothing to cover
 // its barriers.
-// At the end of the part the halves of a wave meet through one shuffle and the two waves of a vector through LDS.
+// At the end of the part the halves of a wave meet through one shuffle and the two waves of a vector through LDS: the last 33
+// lines of k_kmeans_assign, kept as a copy here because one shared function gave k_kmeans_assign two scalar registers fewer
+// and every assign kernel another instruction text behind its loops (profiles/lloyd_fold_isa.txt).
 //
-// k_kmeans_sums_half: k_kmeans_sums over fp16 rows, a sibling and not a flag of that template, so that its instantiations keep
-// their instruction text: the same blocks, quarters and member order, each element widened exactly (fp16 -> fp32 -> float64) and
-// added to the same float64 tree of rule 47.  VEC: one 8-byte load per group of four elements.
+// The update's sums over fp16 rows are the HALF flag of k_kmeans_sums (mcq_kmeans_kernels.h), not a kernel of this file.
 #pragma once
 #include "mcq_kmeans_kernels.h"
 
 namespace mcq {
 
-// ---- launch arithmetic (mcq_kmeans_half_parts and mcq_kmeans_half_planes of mcq_api.hip are the plan)
+// ---- launch arithmetic (mcq_kmeans_half_planes of mcq_api.hip is the plan; the parts are rule 44's, kKmFullBlocks: this
+// kernel too runs two workgroups per compute unit)
 constexpr int kHalfDC = 32;                // halves of a D chunk: two steps of 16
 constexpr int kHalfPitch = kHalfDC + 8;    // halves of a staged row
 constexpr int kHalfStageHalves = (kKmVT + 2 * kKmCT) * kHalfPitch;   // one buffer: the vector rows, the hi rows, the lo rows
 constexpr int kHalfLds = 2 * kHalfStageHalves * 2;      // the staging; behind it the terms of two centroid tiles
 constexpr int kHalfLdsAll = kHalfLds + 2 * kKmCT * 4;
-constexpr int kHalfFullBlocks = 512;       // vector tiles that fill the chip alone: two workgroups per CU
 constexpr int kHalfSplitBlocks = 1 << 16;  // the most workgroups of k_half_split
 constexpr float kHalfLoScale = 2048.f;     // 2^11
 static_assert(kHalfPitch * 2 % 16 == 0 && kHalfDC % 16 == 0, "a fragment is one aligned 16-byte read; a chunk is whole steps");
@@ -259,70 +258,6 @@ k_kmeans_assign_half(const unsigned short *__restrict__ vectors, int B, const un
                 part_list[(v0 + at) * parts + part] = bi[vi];
             }
         }
-    }
-}
-
-// cap: the blocks block_sums holds (the grid's x); sums is [cap][D]
-template <bool VEC>
-__global__ void __launch_bounds__(64 * kKmWaves)
-k_kmeans_sums_half(const unsigned short *__restrict__ vectors, long B, int D, const int64_t *__restrict__ order,
-                   const int64_t *__restrict__ off, int L, const int64_t *__restrict__ first, long cap, double *__restrict__ sums) {
-    __shared__ double quarter[kKmWaves * kKmSlab];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long g = blockIdx.x;
-    const int slab = blockIdx.y;
-    if (g >= first[L] || g >= cap) return;                   // (uniform) a surplus workgroup
-    long a = 0, z = L;                                       // first[a] <= g < first[z]: the last such a is the block's list
-    while (z - a > 1) {
-        const long mid = a + (z - a) / 2;
-        if (first[mid] <= g) a = mid;
-        else z = mid;
-    }
-    long lo, hi;
-    kmeans_list(off, a, B, lo, hi);
-    const long p0 = lo + (g - first[a]) * kKmBlock + (long)wave * kKmQuarter;
-    const long p1 = p0 + kKmQuarter < hi ? p0 + kKmQuarter : hi;
-    double acc[4][4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[t][j] = 0.0;
-    const int e0 = slab * kKmSlab + lane * 4;
-#pragma unroll 1
-    for (long p = p0; p < p1; p += 64) {
-        int row = -1;                                        // lane j: the row of member p + j, -1 where it names none
-        if (p + lane < p1) {
-            const int64_t r = order[p + lane];
-            if (r >= 0 && r < B) row = (int)r;
-        }
-        const int n = p1 - p < 64 ? (int)(p1 - p) : 64;
-#pragma unroll 1
-        for (int j0 = 0; j0 < n; j0 += kKmRows) {
-            float x[kKmRows][4][4];
-#pragma unroll
-            for (int r = 0; r < kKmRows; ++r) {
-                const __amdgpu_buffer_rsrc_t rs = rerank_row<true>(vectors, __builtin_amdgcn_readlane(row, j0 + r), D);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) rerank_load<true, VEC>(x[r][t], rs, e0 + 256 * t);
-            }
-#pragma unroll
-            for (int r = 0; r < kKmRows; ++r)
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[t][j] = acc[t][j] + (double)x[r][t][j];
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) quarter[wave * kKmSlab + 256 * t + lane * 4 + j] = acc[t][j];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < kKmSlab / (64 * kKmWaves); ++i) {
-        const int e = tid + 64 * kKmWaves * i;
-        const double sum = ((quarter[e] + quarter[kKmSlab + e]) + quarter[2 * kKmSlab + e]) + quarter[3 * kKmSlab + e];
-        if (slab * kKmSlab + e < D) sums[g * D + slab * kKmSlab + e] = sum;
     }
 }
 

@@ -21,11 +21,26 @@ __all__ = ["kmeans_step", "coarse_train"]
 SPLIT = 1e-4                # faiss's split of the largest list when another is empty
 
 
-def _checked_step(vectors, centroids, terms, prev_assign):
-    """shape and dtype errors of a step: looks at no data, so it runs before any device work, on CPU tensors too"""
-    L, D = _checked(vectors, centroids, "l2", terms, "vectors")
-    if vectors.ndim != 2:
-        raise ValueError(f"vectors: an fp32 (B, {D}) tensor, not {tuple(vectors.shape)}")
+# the dtype of the vector rows picks the entries (the parts query, the assignment, the update); fp16 rows also take the planes
+_ENTRIES = {torch.float32: ("mcq_kmeans_parts", "mcq_kmeans_assign", "mcq_kmeans_update"),
+            torch.float16: ("mcq_kmeans_half_parts", "mcq_kmeans_assign_half", "mcq_kmeans_update_half")}
+_NAME = {torch.float32: "fp32", torch.float16: "fp16"}
+
+
+def _checked_step(vectors, centroids, terms, prev_assign, dtype=torch.float32, fp32_name=None):
+    """shape and dtype errors of a step over rows of `dtype`: looks at no data, so it runs before any device work, on CPU
+    tensors too.  fp32_name: the call that fp32 rows are sent to by a call that takes torch.float16"""
+    if dtype == torch.float32:
+        L, D = _checked(vectors, centroids, "l2", terms, "vectors")
+        if vectors.ndim != 2:
+            raise ValueError(f"vectors: an fp32 (B, {D}) tensor, not {tuple(vectors.shape)}")
+    else:
+        L, D = _checked(None, centroids, "l2", terms, "")
+        if isinstance(vectors, Tensor) and vectors.dtype == torch.float32:
+            raise ValueError(f"vectors: fp32 rows go to {fp32_name}; this call takes torch.float16")
+        if not isinstance(vectors, Tensor) or vectors.dtype != dtype or vectors.ndim != 2 or vectors.shape[1] != D:
+            raise ValueError(f"vectors: an fp16 (B, {D}) tensor, not {getattr(vectors, 'dtype', type(vectors))} "
+                             f"{tuple(getattr(vectors, 'shape', ()))}")
     if L < 1:
         raise ValueError("centroids: at least one list to assign to")
     B = int(vectors.shape[0])
@@ -38,21 +53,33 @@ def _checked_step(vectors, centroids, terms, prev_assign):
     return B, L, D
 
 
-def _step(x, c, terms, prev, B, L, D):
-    """x (B, D) and c (L, D) contiguous on one device: the two entries and the sort between them"""
+def _assign(x, c, terms, prev, B, L, D):
+    """x (B, D) fp32 or fp16 and c (L, D) fp32 contiguous on one device: the assignment entry of x.dtype, its outputs and its
+    scratch -> (assign, changed)"""
     dev = x.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    if terms is None:
-        terms = coarse_terms(c)
-    parts = int(_entry("mcq_kmeans_parts")(B, L, D))
+    parts_query, entry, _ = _ENTRIES[x.dtype]
+    parts = int(_entry(parts_query)(B, L, D))
     assign = torch.empty((B,), dtype=torch.int32, device=dev)
     score = torch.empty((B,), dtype=torch.float32, device=dev)
     changed = None if prev is None else torch.empty((1,), dtype=torch.int32, device=dev)
     part_score = torch.empty((B, parts), dtype=torch.float32, device=dev)
     part_list = torch.empty((B, parts), dtype=torch.int32, device=dev)
-    _call("mcq_kmeans_assign", x.data_ptr(), B, c.data_ptr(), L, D, terms.data_ptr(), parts,
-          None if prev is None else prev.data_ptr(), assign.data_ptr(), score.data_ptr(),
-          None if changed is None else changed.data_ptr(), part_score.data_ptr(), part_list.data_ptr(), stream)
+    scratch = [part_score.data_ptr(), part_list.data_ptr()]
+    if x.dtype == torch.float16:                             # the two fp16 planes of the centroids
+        planes = torch.empty((int(_entry("mcq_kmeans_half_planes")(L, D)),), dtype=torch.int16, device=dev)
+        scratch.append(planes.data_ptr())
+    _call(entry, x.data_ptr(), B, c.data_ptr(), L, D, terms.data_ptr(), parts, None if prev is None else prev.data_ptr(),
+          assign.data_ptr(), score.data_ptr(), None if changed is None else changed.data_ptr(), *scratch,
+          torch.cuda.current_stream(dev).cuda_stream)
+    return assign, changed
+
+
+def _step(x, c, terms, prev, B, L, D):
+    """x (B, D) fp32 or fp16 and c (L, D) fp32 contiguous on one device: the two entries of x.dtype and the sort between them"""
+    dev = x.device
+    if terms is None:
+        terms = coarse_terms(c)
+    assign, changed = _assign(x, c, terms, prev, B, L, D)
     # the stable sort by list: ascending original position inside a list; a row assigned -1 sorts behind list L - 1
     key = torch.where(assign < 0, torch.full_like(assign, L), assign).to(torch.int64)
     keys, order = torch.sort(key, stable=True)
@@ -61,9 +88,18 @@ def _step(x, c, terms, prev, B, L, D):
     counts = torch.empty((L,), dtype=torch.int32, device=dev)
     block_first = torch.empty((L + 1,), dtype=torch.int64, device=dev)
     block_sums = torch.empty((int(_entry("mcq_kmeans_blocks")(B, L, D)),), dtype=torch.float64, device=dev)
-    _call("mcq_kmeans_update", x.data_ptr(), B, D, order.data_ptr(), offsets.data_ptr(), L, c.data_ptr(), new.data_ptr(),
-          counts.data_ptr(), block_first.data_ptr(), block_sums.data_ptr(), stream)
+    _call(_ENTRIES[x.dtype][2], x.data_ptr(), B, D, order.data_ptr(), offsets.data_ptr(), L, c.data_ptr(), new.data_ptr(),
+          counts.data_ptr(), block_first.data_ptr(), block_sums.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     return new, assign, counts, changed
+
+
+def _public_step(vectors, centroids, terms, prev_assign, dtype, fp32_name):
+    """kmeans_step and kmeans_step_half: the checks, then _step on contiguous tensors"""
+    B, L, D = _checked_step(vectors, centroids, terms, prev_assign, dtype, fp32_name)
+    _on_device(vectors, centroids, terms, prev_assign)
+    with torch.no_grad(), torch.cuda.device(vectors.device):
+        return _step(vectors.detach().contiguous(), centroids.detach().contiguous(), terms,
+                     None if prev_assign is None else prev_assign.detach().contiguous(), B, L, D)
 
 
 def kmeans_step(vectors: Tensor, centroids: Tensor, terms: Tensor = None, prev_assign: Tensor = None):
@@ -75,11 +111,7 @@ def kmeans_step(vectors: Tensor, centroids: Tensor, terms: Tensor = None, prev_a
     prev_assign (what an earlier step returned), or None without prev_assign.
     terms: what coarse_terms(centroids) returned (computed here if None).  Not differentiable; no CPU fallback (McqError);
     shape and dtype errors are ValueErrors raised before any device work; nothing is read back to the host."""
-    B, L, D = _checked_step(vectors, centroids, terms, prev_assign)
-    _on_device(vectors, centroids, terms, prev_assign)
-    with torch.no_grad(), torch.cuda.device(vectors.device):
-        return _step(vectors.detach().contiguous(), centroids.detach().contiguous(), terms,
-                     None if prev_assign is None else prev_assign.detach().contiguous(), B, L, D)
+    return _public_step(vectors, centroids, terms, prev_assign, torch.float32, None)
 
 
 def _reseed(centroids, counts):
@@ -98,20 +130,17 @@ def _reseed(centroids, counts):
     return centroids[source] * scale[:, None]
 
 
-def coarse_train(vectors: Tensor, num_lists: int, iters: int = 10, seed: int = 0, init: Tensor = None) -> Tensor:
-    """vectors (B, D) fp32 on the device -> centroids (num_lists, D) fp32: `iters` Lloyd steps (kmeans_step) under "l2" from
-    `init` -- (num_lists, D) fp32 rows -- or, without one, from num_lists distinct rows of `vectors` drawn by a
-    torch.Generator seeded with `seed`.  After each step an empty list is reseeded from the largest (faiss's split, _reseed).
-    The same vectors, seed or init, and iters give the same bits on every run.  Argument errors are ValueErrors raised before
-    any device work; no CPU fallback (McqError); nothing is read back to the host."""
+def _train(vectors, num_lists, iters, seed, init, dtype, fp32_name):
+    """coarse_train and coarse_train_half: the argument errors, the start and `iters` times _step and _reseed"""
     if isinstance(num_lists, bool) or not isinstance(num_lists, int) or num_lists < 1:
         raise ValueError(f"num_lists = {num_lists!r}: a positive integer")
     if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
         raise ValueError(f"iters = {iters!r}: a non-negative integer")
-    if not isinstance(vectors, Tensor) or vectors.ndim != 2 or vectors.dtype != torch.float32 or \
-            not 1 <= vectors.shape[1] <= MAX_DIM:
-        raise ValueError(f"vectors: an fp32 (B, D) tensor, 1 <= D <= {MAX_DIM}, not {getattr(vectors, 'dtype', type(vectors))} "
-                         f"{tuple(getattr(vectors, 'shape', ()))}")
+    if dtype != torch.float32 and isinstance(vectors, Tensor) and vectors.dtype == torch.float32:
+        raise ValueError(f"vectors: fp32 rows go to {fp32_name}; this call takes torch.float16")
+    if not isinstance(vectors, Tensor) or vectors.ndim != 2 or vectors.dtype != dtype or not 1 <= vectors.shape[1] <= MAX_DIM:
+        raise ValueError(f"vectors: an {_NAME[dtype]} (B, D) tensor, 1 <= D <= {MAX_DIM}, not "
+                         f"{getattr(vectors, 'dtype', type(vectors))} {tuple(getattr(vectors, 'shape', ()))}")
     B, D = int(vectors.shape[0]), int(vectors.shape[1])
     if init is None:
         if isinstance(seed, bool) or not isinstance(seed, int):
@@ -121,16 +150,28 @@ def coarse_train(vectors: Tensor, num_lists: int, iters: int = 10, seed: int = 0
     elif not isinstance(init, Tensor) or init.dtype != torch.float32 or tuple(init.shape) != (num_lists, D):
         raise ValueError(f"init: an fp32 ({num_lists}, {D}) tensor, not {getattr(init, 'dtype', type(init))} "
                          f"{tuple(getattr(init, 'shape', ()))}")
-    _checked_step(vectors, vectors[:1] if init is None else init, None, None)
+    if B >= (1 << 31) - 1:
+        raise ValueError("vectors: fewer than 2^31 - 1 rows")
     _on_device(vectors, init)
     with torch.no_grad(), torch.cuda.device(vectors.device):
         x = vectors.detach().contiguous()
         if init is None:
             rows = torch.randperm(B, generator=torch.Generator().manual_seed(seed))[:num_lists]
-            centroids = x[rows.to(x.device)]
+            centroids = x[rows.to(x.device)].float()         # (fp32 rows: the same tensor, no copy)
         else:
             centroids = init.detach().contiguous().clone()
         for _ in range(iters):
             centroids, _, counts, _ = _step(x, centroids, None, None, B, num_lists, D)
             centroids = _reseed(centroids, counts)
     return centroids
+
+
+def coarse_train(vectors: Tensor, num_lists: int, iters: int = 10, seed: int = 0, init: Tensor = None) -> Tensor:
+    """vectors (B, D) fp32 on the device -> centroids (num_lists, D) fp32: `iters` Lloyd steps (kmeans_step) under "l2" from
+    `init` -- (num_lists, D) fp32 rows -- or, without one, from num_lists distinct rows of `vectors` drawn by a
+    torch.Generator seeded with `seed`.  After each step an empty list is reseeded from the largest (faiss's split, _reseed).
+    The same vectors, seed or init, and iters give the same bits on every run.  Argument errors are ValueErrors raised before
+    any device work; no CPU fallback (McqError); nothing is read back to the host."""
+    return _train(vectors, num_lists, iters, seed, init, torch.float32, None)
+
+

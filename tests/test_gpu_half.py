@@ -183,3 +183,39 @@ def test_coarse_train_half_end_to_end():
     assert bool((kmeans_step_half(xd, coarse_train_half(xd, 8, iters=1, init=dup))[2] > 0).all())   # reseeded from the largest
     a, b = coarse_train_half(xd, 8, iters=2, seed=3), coarse_train_half(xd, 8, iters=2, seed=3)
     assert a.shape == (8, D) and a.dtype == torch.float32 and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+@pytest.mark.parametrize("B,L,D,most", ((257, 129, 16, 2), (129, 300, 33, 3)))
+def test_assign_is_the_fp32_assign_on_exact_inputs(B, L, D, most):
+    """_grid inputs: every product and partial sum is exact in fp32 in any order, so mcq_kmeans_assign on the widened rows and
+    mcq_kmeans_assign_half on the fp16 rows give the same assign, the same score bits and the same `changed` against a shifted
+    prev_assign, with one part and with the most.  (257, 129, 16): a last vector tile of one row, two centroid tiles, the
+    16-byte loads of both kernels; (129, 300, 33): the element-wise loads"""
+    from test_gpu_kmeans import _assign as _assign32
+    x, c = _grid(B, L, D)
+    xd, cd = _dev16(x), torch.from_numpy(c).cuda()
+    xf = xd.float()
+    assert xd.data_ptr() % 16 == 0 and xf.data_ptr() % 16 == 0
+    prev = np.asarray(_assign(xd, cd, 1)[0]).copy()
+    prev[[0, 5, 64, 100, B - 1]] += 1
+    pd = torch.from_numpy(prev).cuda()
+    for parts in (1, most):
+        a16, s16, n16 = _assign(xd, cd, parts, prev=pd)
+        a32, s32, n32 = _assign32(xf, cd, parts, prev=pd)
+        assert np.array_equal(a16, a32) and np.array_equal(_bits(s16), _bits(s32)) and n16 == n32 == 5, parts
+
+
+def test_step_is_the_fp32_step_on_exact_inputs():
+    """kmeans_step_half(x16, c, prev_assign=p) and kmeans_step(x16.float(), c, prev_assign=p) on _grid(300, 5, 33), row 4 of c a
+    copy of row 0 (list 4 is empty and keeps its centroid): the same new centroids bit for bit, the same assign, counts and
+    changed -- one _step and one sums kernel behind both"""
+    from quantization_amd import kmeans_step, kmeans_step_half
+    x, c = _grid(300, 5, 33)
+    assert np.array_equal(c[4], c[0])
+    xd, cd = _dev16(x), torch.from_numpy(c).cuda()
+    p = torch.zeros(300, dtype=torch.int32, device="cuda")
+    new16, a16, n16, ch16 = kmeans_step_half(xd, cd, prev_assign=p)
+    new32, a32, n32, ch32 = kmeans_step(xd.float(), cd, prev_assign=p)
+    assert torch.equal(new16.view(torch.int32), new32.view(torch.int32)) and torch.equal(a16, a32) and torch.equal(n16, n32)
+    assert int(ch16) == int(ch32) == int((a32 != 0).sum()) and int(n32[4]) == 0
+    assert torch.equal(new32[4].view(torch.int32), cd[4].view(torch.int32)) and int(n32.sum()) == 300

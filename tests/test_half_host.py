@@ -61,6 +61,70 @@ def test_queries_and_checks_without_launch():
     assert u(x=None) == I and u(order=None) == I and u(x=odd1) == I and u(sums=ctypes.c_void_p((1 << 20) + 4)) == I
 
 
+def test_half_parts_is_the_fp32_recommendation():
+    """rule 48 takes rule 44's formula: one function behind both queries"""
+    L = _lib().lib()
+    for B in (0, 1, 128, 129, 1024, 65536):
+        for lists in (1, 128, 129, 300, 16384):
+            for D in (1, 64, 16384):
+                assert L.mcq_kmeans_half_parts(B, lists, D) == L.mcq_kmeans_parts(B, lists, D), (B, lists, D)
+    for bad in ((300, 300, 0), (300, 300, 16385), (300, 0, 64)):
+        assert L.mcq_kmeans_half_parts(*bad) == L.mcq_kmeans_parts(*bad) == 1
+
+
+def test_fp32_and_fp16_entries_refuse_alike():
+    """one table of bad arguments against both entries of each pair (fake pointers, no launch): the same return code case by
+    case.  The stated exceptions: `planes`, which the fp32 entry does not have, and vectors at a 2-byte boundary, which only
+    the fp32 entries refuse"""
+    m = _lib()
+    L = m.lib()
+    U, I = m.MCQ_EUNSUPPORTED, m.MCQ_EINVAL
+    big = (1 << 31) - 1
+    fake, odd1, odd2, odd4 = (ctypes.c_void_p((1 << 20) + k) for k in (0, 1, 2, 4))
+
+    def assign(half, x=fake, B=300, c=fake, L_=300, D=64, terms=fake, parts=1, prev=None, assign=fake, score=fake, changed=fake,
+               ps=fake, pl=fake, planes=fake):
+        if half:
+            return L.mcq_kmeans_assign_half(x, B, c, L_, D, terms, parts, prev, assign, score, changed, ps, pl, planes, None)
+        return L.mcq_kmeans_assign(x, B, c, L_, D, terms, parts, prev, assign, score, changed, ps, pl, None)
+
+    none = dict(x=None, c=None, terms=None, assign=None, score=None, changed=None, ps=None, pl=None, planes=None)
+    outs = {**none, "assign": fake, "score": fake}
+    cases = [(dict(D=16385, B=-1, L_=0, **none), U), (dict(D=0, L_=big, **none), I), (dict(B=-1, L_=big, **none), I),
+             (dict(L_=0, B=big, **none), I), (dict(B=big, **none), U), (dict(L_=1 << 40, **none), U),       # the domain
+             (dict(assign=None), I), (dict(score=None), I), (dict(prev=fake, changed=None), I),            # outputs; prev without changed
+             (dict(B=0, **none), 0), (dict(B=0, prev=fake, **{**none, "changed": odd2}), I),               # B == 0
+             (dict(B=0, parts=0, **none), 0)]
+    cases += [(dict(parts=p, **outs), I) for p in (0, -1, 4, 1 << 40)]                                      # 300 lists are 3 tiles
+    cases += [(dict(B=big - 1, L_=big - 1, parts=1 << 24, **outs), U)]                                      # the grid
+    cases += [({n: None}, I) for n in ("x", "c", "terms", "ps", "pl")]                                      # null pointers
+    cases += [({n: odd2}, I) for n in ("c", "terms", "assign", "score", "prev", "ps", "pl")] + [(dict(x=odd1), I)]   # odd pointers
+    cases += [(dict(prev=fake, changed=odd2), I)]
+    for kw, want in cases:
+        assert assign(False, **kw) == assign(True, **kw) == want, kw
+    assert assign(True, planes=None) == I and assign(True, planes=ctypes.c_void_p((1 << 20) + 8)) == I     # exception: planes
+    assert assign(False, x=odd2) == I                                                                      # exception: 2-byte vectors
+
+    names = ("x", "order", "off", "cin", "cout", "counts", "first", "sums")
+
+    def update(half, B=300, D=64, L_=7, **kw):
+        p = {n: kw.get(n, fake) for n in names}
+        f = L.mcq_kmeans_update_half if half else L.mcq_kmeans_update
+        return f(p["x"], B, D, p["order"], p["off"], L_, p["cin"], p["cout"], p["counts"], p["first"], p["sums"], None)
+
+    nothing = {n: None for n in names}
+    cases = [(dict(D=16385, B=-1, L_=0, **nothing), U), (dict(D=0, B=big, **nothing), I), (dict(B=-1, L_=big, **nothing), I),
+             (dict(L_=0, B=big, **nothing), I), (dict(B=big, **nothing), U), (dict(L_=big, **nothing), U),
+             (dict(B=big - 1, L_=big - 1, **nothing), U),                                                   # ceil(B / 4096) + L: the grid
+             (dict(B=0, x=None, order=None, off=None), I)]
+    cases += [({n: None}, I) for n in names]
+    cases += [({n: odd4}, I) for n in ("order", "off", "first", "sums")] + [({n: odd2}, I) for n in ("cin", "cout", "counts")]
+    cases += [(dict(x=odd1), I)]
+    for kw, want in cases:
+        assert update(False, **kw) == update(True, **kw) == want, kw
+    assert update(False, x=odd2) == I                                                                      # exception: 2-byte vectors
+
+
 def test_python_argument_errors_precede_device_work():
     import torch
     m = _lib()

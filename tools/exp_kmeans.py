@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kmeans.jsonl"))
+    ap.add_argument("--tag", default=None, help="a label put into every line, such as the library the process loaded")
+    ap.add_argument("--only", nargs="*", default=None, help="the contenders to time (all by default)")
     args = ap.parse_args()
     from exp_rerank import peak_extra
     from exp_search_lists import timed
@@ -43,6 +45,8 @@ def main():
     out = open(args.out, "w")
 
     def emit(line):
+        if args.tag is not None:
+            line = {"tag": args.tag, **line}
         out.write(json.dumps(line) + "\n")
         out.flush()
         print(json.dumps(line), flush=True)
@@ -92,6 +96,8 @@ def main():
             mine, theirs = kmeans_step(x, cen, terms=terms), rocblas()
             cell = {"B": B, "L": L, "parts": parts, "same_assign": round(float((mine[1].long() == theirs).float().mean()), 6),
                     "max_abs_diff_to_torch_mean": float((mine[0] - mean_of(theirs)).abs().max())}
+            if args.only is not None:
+                contenders = {name: contenders[name] for name in args.only}
             for f in contenders.values():
                 f(), f()
             runs = {name: [] for name in contenders}
