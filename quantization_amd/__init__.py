@@ -13,7 +13,8 @@ from .rerank import rerank  # noqa: F401   (the exact re-ranking of a shortlist:
 from .coarse import coarse_terms, coarse_probe, coarse_assign  # noqa: F401   (the coarse quantizer in HIP: probes, biases, assignment)
 from .kmeans import kmeans_step, coarse_train  # noqa: F401   (the coarse centroids themselves: a Lloyd step and the trainer, in HIP)
 from .half import coarse_assign_half, kmeans_step_half, coarse_train_half  # noqa: F401   (the same over an fp16 raw store, on the f16 matrix cores)
+from .half import coarse_planes, coarse_probe_half  # noqa: F401   (the coarse probes for fp16 queries, on the same matrix cores)
 
 __all__ = ["Quantizer", "QuantizerTrainer", "JointCodebookLoss", "read_hdf5_data", "build_lists", "probe_lists", "probe_bias", "list_assign", "rerank",
            "coarse_terms", "coarse_probe", "coarse_assign", "kmeans_step", "coarse_train",
-           "coarse_assign_half", "kmeans_step_half", "coarse_train_half"]
+           "coarse_assign_half", "kmeans_step_half", "coarse_train_half", "coarse_planes", "coarse_probe_half"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h, include/mcq_probe.h, include/mcq_wide.h, include/mcq_rerank.h, include/mcq_code16.h, include/mcq_shortlist.h, include/mcq_coarse.h, include/mcq_kmeans.h and include/mcq_half.h).
+"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h, include/mcq_probe.h, include/mcq_wide.h, include/mcq_rerank.h, include/mcq_code16.h, include/mcq_shortlist.h, include/mcq_coarse.h, include/mcq_kmeans.h, include/mcq_half.h and include/mcq_coarse_half.h).
 
 The library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950).  There
 is no CPU fallback: a missing library or a non-HIP tensor is an error.
@@ -185,6 +185,15 @@ HALF_SIGNATURES = {
 }
 HALF_SYMBOLS = tuple(HALF_SIGNATURES)
 
+# include/mcq_coarse_half.h, the companion header of the coarse probes for fp16 queries, in the same form and in its order
+# (tests/test_coarse_half_host.py parses that header and compares)
+COARSE_HALF_SIGNATURES = {
+    "mcq_coarse_half_parts": _sig("l", "llii"),
+    "mcq_coarse_half_split": _sig("i", "plipp"),
+    "mcq_coarse_probe_half": _sig("i", "plpplipiilpppppp"),
+}
+COARSE_HALF_SYMBOLS = tuple(COARSE_HALF_SIGNATURES)
+
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
 MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
@@ -206,7 +215,8 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES, **PROBE_SIGNATURES, **WIDE_SIGNATURES,
                                       **RERANK_SIGNATURES, **CODE16_SIGNATURES, **SHORTLIST_SIGNATURES,
-                                      **COARSE_SIGNATURES, **KMEANS_SIGNATURES, **HALF_SIGNATURES}.items():
+                                      **COARSE_SIGNATURES, **KMEANS_SIGNATURES, **HALF_SIGNATURES,
+                                      **COARSE_HALF_SIGNATURES}.items():
         # an older build loaded through the A/B hook above may lack a symbol: it stays unbound, and calling it raises.
         # Without the hook a missing symbol fails here, at load
         if _ALT and not hasattr(L, name):

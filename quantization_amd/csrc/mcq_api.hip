@@ -11,6 +11,7 @@
 #include "../../include/mcq_coarse.h"
 #include "../../include/mcq_kmeans.h"
 #include "../../include/mcq_half.h"
+#include "../../include/mcq_coarse_half.h"
 #include "../../include/mcq_lanes.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
@@ -26,6 +27,7 @@
 #include "mcq_coarse_kernels.h"
 #include "mcq_kmeans_kernels.h"
 #include "mcq_half_kernels.h"
+#include "mcq_coarse_half_kernels.h"
 #include "mcq_lanes.h"
 
 #include <cstdlib>
@@ -3028,6 +3030,95 @@ int mcq_kmeans_update_half(const uint16_t *vectors, long B, int D, const int64_t
                            const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first,
                            double *block_sums, void *stream) {
     return kmeans_update(vectors, B, D, order, list_offsets, L, centroids_in, centroids_out, counts, block_first, block_sums, stream);
+}
+
+// ---- rules 52-55 (include/mcq_coarse_half.h): the coarse probes for fp16 queries.  (mcq_coarse_half_kernels.h; the part
+// buffers are typed arguments and the planes a const input the caller made once with mcq_coarse_half_split)
+extern "C++" {
+namespace {
+
+long coarse_half_tiles(long L) { return (L + kChCT - 1) / kChCT; }
+
+// M = 64 / 128 / 256 by the class of P; f(METRIC, VEC, M) for the one that is asked for
+template <typename F>
+int pick_coarse_half(int metric, bool vec, int P, F &&f) {
+    return pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        return pick_bool(vec, [&](auto v) {
+            return pick<64, 128, 256>(coarse_half_list(P), [&](auto len) { return f(m, v, len); });
+        });
+    });
+}
+
+}  // namespace
+}  // extern "C++"
+
+long mcq_coarse_half_parts(long Q, long L, int D, int P) {
+    if (Q <= 0 || L <= 0 || coarse_domain(Q, L, D, P, MCQ_SEARCH_L2) != 0) return 1;
+    const long qt = (Q + kChQT - 1) / kChQT, ct = coarse_half_tiles(L);
+    const long target = coarse_half_list(P) == 64 ? kChTargetBlocks : kChTargetBlocks / 2;   // workgroups a compute unit holds: 2 or 1
+    if (qt >= target) return 1;
+    const long parts = (target + qt - 1) / qt;
+    return parts < ct ? parts : ct;
+}
+
+int mcq_coarse_half_split(const float *centroids, long L, int D, uint16_t *planes, void *stream) {
+    if (const int rc = coarse_domain(0, L, D, 1, MCQ_SEARCH_L2)) return rc;
+    if (L == 0) return 0;
+    if (!centroids || !planes || !aligned<4>(centroids) || !aligned<16>(planes)) return MCQ_EINVAL;
+    const long groups = L * (half_padded_dim(D) / 8), want = (groups + 64 * kKmWaves - 1) / (64 * kKmWaves);
+    hipLaunchKernelGGL(k_half_split, dim3((unsigned)(want < kHalfSplitBlocks ? want : kHalfSplitBlocks)), dim3(64 * kKmWaves), 0,
+                       static_cast<hipStream_t>(stream), centroids, (int)L, D, planes);
+    return launch_rc();
+}
+
+int mcq_coarse_probe_half(const uint16_t *queries, long Q, const float *centroids, const uint16_t *planes, long L, int D,
+                          const float *terms, int P, int metric, long parts, int32_t *out_list, float *out_score, float *out_bias,
+                          float *part_score, int32_t *part_list, void *stream) {
+    if (const int rc = coarse_domain(Q, L, D, P, metric)) return rc;
+    if (Q > 0 && (!out_list || !out_score)) return MCQ_EINVAL;
+    if (Q == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool with_bias = out_bias != nullptr;
+    auto finish = [&](int np, int vec) {
+        return pick_bool(with_bias, [&](auto bias) {
+            constexpr bool BIAS = bias;
+            static bool allowed[64] = {};
+            if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_coarse_finish_half<BIAS>),
+                                                 coarse_finish_lds(BIAS, kCoarseMaxD, kCoarseMaxP)))
+                return rc;
+            hipLaunchKernelGGL((k_coarse_finish_half<BIAS>), dim3((unsigned)Q), dim3(64 * kWideWaves),
+                               coarse_finish_lds(BIAS && np > 0, D, P), st, part_score, part_list, np, P, queries, centroids, (int)L,
+                               D, vec, out_list, out_score, out_bias);
+            return launch_rc();
+        });
+    };
+    if (L == 0) {                                                          // no input is looked at: the tail
+        if (!aligned<4>(out_list) || !aligned<4>(out_score) || !aligned<4>(out_bias)) return MCQ_EINVAL;
+        return finish(0, 0);
+    }
+    const long qt = (Q + kChQT - 1) / kChQT;
+    if (parts < 1 || parts > coarse_half_tiles(L)) return MCQ_EINVAL;
+    if (qt * parts >= kSizeLimit) return MCQ_EUNSUPPORTED;                 // (the grid of k_coarse_probe_half)
+    if (!queries || !centroids || !planes || !part_score || !part_list || (metric != MCQ_SEARCH_IP && !terms)) return MCQ_EINVAL;
+    if (!aligned<4>(out_list) || !aligned<4>(out_score) || !aligned<4>(out_bias) || !aligned<2>(queries) || !aligned<4>(centroids) ||
+        !aligned<16>(planes) || (metric != MCQ_SEARCH_IP && !aligned<4>(terms)) || !aligned<4>(part_score) || !aligned<4>(part_list))
+        return MCQ_EINVAL;
+    // one 16-byte load per staged group of eight halves where every query row starts on that boundary
+    const bool vec = D % 8 == 0 && aligned<16>(queries);
+    const int rc = pick_coarse_half(metric, vec, P, [&](auto m, auto v, auto len) {
+        constexpr int METRIC = decltype(m)::value, M = decltype(len)::value;
+        constexpr bool VEC = decltype(v)::value;
+        static bool allowed[64] = {};
+        if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_coarse_probe_half<METRIC, VEC, M>),
+                                             coarse_half_lds(M)))
+            return rc;
+        hipLaunchKernelGGL((k_coarse_probe_half<METRIC, VEC, M>), dim3((unsigned)(qt * parts)), dim3(64 * kChWaves),
+                           coarse_half_lds(M), st, queries, (int)Q, planes, (int)L, D, METRIC == kMetricIP ? nullptr : terms, P,
+                           (int)parts, part_score, part_list);
+        return launch_rc();
+    });
+    if (rc) return rc;
+    return finish((int)parts, D % 4 == 0 && aligned<16>(centroids));
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector
