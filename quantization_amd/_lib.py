@@ -1,4 +1,4 @@
-"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h, include/mcq_probe.h, include/mcq_wide.h, include/mcq_rerank.h, include/mcq_code16.h, include/mcq_shortlist.h, include/mcq_coarse.h, include/mcq_kmeans.h, include/mcq_half.h and include/mcq_coarse_half.h).
+"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h, include/mcq_probe.h, include/mcq_wide.h, include/mcq_rerank.h, include/mcq_code16.h, include/mcq_shortlist.h, include/mcq_coarse.h, include/mcq_kmeans.h, include/mcq_half.h, include/mcq_coarse_half.h and include/mcq_bf16.h).
 
 The library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950).  There
 is no CPU fallback: a missing library or a non-HIP tensor is an error.
@@ -194,6 +194,16 @@ COARSE_HALF_SIGNATURES = {
 }
 COARSE_HALF_SYMBOLS = tuple(COARSE_HALF_SIGNATURES)
 
+# include/mcq_bf16.h, the companion header of the Lloyd step over a bf16 raw store, in the same form and in its order
+# (tests/test_bf16_host.py parses that header and compares)
+BF16_SIGNATURES = {
+    "mcq_kmeans_bf16_parts": _sig("l", "lli"),
+    "mcq_kmeans_bf16_planes": _sig("l", "li"),
+    "mcq_kmeans_assign_bf16": _sig("i", "plpliplpppppppp"),
+    "mcq_kmeans_update_bf16": _sig("i", "plipplpppppp"),
+}
+BF16_SYMBOLS = tuple(BF16_SIGNATURES)
+
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
 MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
@@ -216,7 +226,7 @@ def lib():
     for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES, **PROBE_SIGNATURES, **WIDE_SIGNATURES,
                                       **RERANK_SIGNATURES, **CODE16_SIGNATURES, **SHORTLIST_SIGNATURES,
                                       **COARSE_SIGNATURES, **KMEANS_SIGNATURES, **HALF_SIGNATURES,
-                                      **COARSE_HALF_SIGNATURES}.items():
+                                      **COARSE_HALF_SIGNATURES, **BF16_SIGNATURES}.items():
         # an older build loaded through the A/B hook above may lack a symbol: it stays unbound, and calling it raises.
         # Without the hook a missing symbol fails here, at load
         if _ALT and not hasattr(L, name):

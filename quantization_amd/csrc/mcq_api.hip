@@ -12,6 +12,7 @@
 #include "../../include/mcq_kmeans.h"
 #include "../../include/mcq_half.h"
 #include "../../include/mcq_coarse_half.h"
+#include "../../include/mcq_bf16.h"
 #include "../../include/mcq_lanes.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
@@ -28,6 +29,7 @@
 #include "mcq_kmeans_kernels.h"
 #include "mcq_half_kernels.h"
 #include "mcq_coarse_half_kernels.h"
+#include "mcq_bf16_kernels.h"
 #include "mcq_lanes.h"
 
 #include <cstdlib>
@@ -2874,9 +2876,10 @@ int mcq_coarse_probe(const float *queries, long Q, const float *centroids, long 
                                 out_score, out_bias);
 }
 
-// ---- rules 44-51 (include/mcq_kmeans.h, include/mcq_half.h): one Lloyd step over the coarse centroids, from fp32 rows or from
-// an fp16 raw store.  (mcq_kmeans_kernels.h, mcq_half_kernels.h; the part buffers, the block buffers and the fp16 planes are
-// typed arguments, as those of the coarse probes.)  One path per entry pair: T = float or uint16_t is the type of a vector row
+// ---- rules 44-51 and 56-59 (include/mcq_kmeans.h, include/mcq_half.h, include/mcq_bf16.h): one Lloyd step over the coarse
+// centroids, from fp32 rows or from an fp16 or a bf16 raw store.  (mcq_kmeans_kernels.h, mcq_half_kernels.h, mcq_bf16_kernels.h;
+// the part buffers, the block buffers and the planes are typed arguments, as those of the coarse probes.)  One path per entry
+// pair: ROW (kRowF32, kRowF16, kRowBf16) names the type of a vector row, T = float or uint16_t carries it
 extern "C++" {
 namespace {
 
@@ -2890,21 +2893,24 @@ int kmeans_domain(long B, long L, int D) {
 
 long kmeans_max_blocks(long B, long L) { return (B + kKmBlock - 1) / kKmBlock + L; }
 
-// rule 44's recommendation; rule 48 takes the same formula (both assign kernels fill the chip with kKmFullBlocks vector tiles)
-long kmeans_parts(long B, long L, int D) {
+// rule 44's recommendation; rule 48 takes the same formula (both assign kernels fill the chip with kKmFullBlocks vector tiles
+// of kKmVT) and rule 56 the same with its kernel's own tile: kBfFullBlocks vector tiles of kBfVT
+long kmeans_parts(long B, long L, int D, int vtile = kKmVT, int full = kKmFullBlocks) {
     if (B <= 0 || kmeans_domain(B, L, D) != 0) return 1;
-    const long vt = (B + kKmVT - 1) / kKmVT, ct = (L + kKmCT - 1) / kKmCT;
-    if (vt >= kKmFullBlocks) return 1;
-    const long parts = (kKmFullBlocks + vt - 1) / vt;
+    const long vt = (B + vtile - 1) / vtile, ct = (L + kKmCT - 1) / kKmCT;
+    if (vt >= full) return 1;
+    const long parts = (full + vt - 1) / vt;
     return parts < ct ? parts : ct;
 }
 
-// rules 45 and 49.  float rows: `planes` is nullptr and not looked at
-template <typename T>
+// rules 45, 49 and 57.  float rows: `planes` is nullptr and not looked at
+template <int ROW, typename T>
 int kmeans_assign(const T *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
                   const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
                   int32_t *part_list, uint16_t *planes, void *stream) {
-    constexpr bool HALF = sizeof(T) == 2;
+    static_assert(sizeof(T) == (ROW == kRowF32 ? 4 : 2), "the row tag and the element type agree");
+    constexpr bool PLANES = ROW != kRowF32;
+    constexpr int VT = ROW == kRowBf16 ? kBfVT : kKmVT;      // vectors of the assign kernel's tile
     if (const int rc = kmeans_domain(B, L, D)) return rc;
     if ((B > 0 && (!assign || !score)) || (prev_assign && !changed)) return MCQ_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2913,17 +2919,33 @@ int kmeans_assign(const T *vectors, long B, const float *centroids, long L, int 
         if (!prev_assign) return 0;
         if (!aligned<4>(changed)) return MCQ_EINVAL;
     } else {
-        const long vt = (B + kKmVT - 1) / kKmVT;
+        const long vt = (B + VT - 1) / VT;
         if (parts < 1 || parts > (L + kKmCT - 1) / kKmCT) return MCQ_EINVAL;
         if (vt * parts >= kSizeLimit) return MCQ_EUNSUPPORTED;             // (the grid of the assign kernel)
-        if (!vectors || !centroids || !terms || !part_score || !part_list || (HALF && !planes)) return MCQ_EINVAL;
+        if (!vectors || !centroids || !terms || !part_score || !part_list || (PLANES && !planes)) return MCQ_EINVAL;
         if (!aligned<sizeof(T)>(vectors) || !aligned<4>(centroids) || !aligned<4>(terms) || !aligned<4>(prev_assign) ||
             !aligned<4>(assign) || !aligned<4>(score) || (prev_assign && !aligned<4>(changed)) || !aligned<4>(part_score) ||
-            !aligned<4>(part_list) || (HALF && !aligned<16>(planes)))
+            !aligned<4>(part_list) || (PLANES && !aligned<16>(planes)))
             return MCQ_EINVAL;
         const dim3 grid((unsigned)(vt * parts));
         int32_t *zeroed = prev_assign ? changed : nullptr;
-        if constexpr (HALF) {
+        if constexpr (ROW == kRowBf16) {
+            // as for fp16 rows below; three planes, and a workgroup of kBfWaves waves per tile of kBfVT vectors
+            const bool vec = D % 8 == 0 && aligned<16>(vectors);
+            const long groups = L * (half_padded_dim(D) / 8), want = (groups + 64 * kKmWaves - 1) / (64 * kKmWaves);
+            const int rc = pick_bool(vec, [&](auto v) {
+                constexpr bool VEC = v;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_kmeans_assign_bf16<VEC>), kBfLdsAll)) return rc;
+                hipLaunchKernelGGL(k_bf16_split, dim3((unsigned)(want < kHalfSplitBlocks ? want : kHalfSplitBlocks)), block, 0, st,
+                                   centroids, (int)L, D, planes);
+                if (const int rc = launch_rc()) return rc;
+                hipLaunchKernelGGL((k_kmeans_assign_bf16<VEC>), grid, dim3(64 * kBfWaves), kBfLdsAll, st, vectors, (int)B, planes, (int)L,
+                                   D, terms, (int)parts, part_score, part_list, zeroed);
+                return launch_rc();
+            });
+            if (rc) return rc;
+        } else if constexpr (ROW == kRowF16) {
             // one 16-byte load per staged group of eight halves where every vector row starts on that boundary
             const bool vec = D % 8 == 0 && aligned<16>(vectors);
             const long groups = L * (half_padded_dim(D) / 8), want = (groups + 64 * kKmWaves - 1) / (64 * kKmWaves);
@@ -2955,12 +2977,12 @@ int kmeans_assign(const T *vectors, long B, const float *centroids, long L, int 
     return launch_rc();
 }
 
-// rules 47 and 51
-template <typename T>
+// rules 47, 51 and 59
+template <int ROW, typename T>
 int kmeans_update(const T *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
                   const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first, double *block_sums,
                   void *stream) {
-    constexpr bool HALF = sizeof(T) == 2;
+    static_assert(sizeof(T) == (ROW == kRowF32 ? 4 : 2), "the row tag and the element type agree");
     if (const int rc = kmeans_domain(B, L, D)) return rc;
     const long cap = kmeans_max_blocks(B, L);
     if (cap >= kSizeLimit) return MCQ_EUNSUPPORTED;                        // (the grid of k_kmeans_sums)
@@ -2975,11 +2997,11 @@ int kmeans_update(const T *vectors, long B, int D, const int64_t *order, const i
     const unsigned slabs = (unsigned)((D + kKmSlab - 1) / kKmSlab);
     hipLaunchKernelGGL(k_kmeans_scan, dim3(1), block, 0, st, list_offsets, (int)L, B, block_first);
     if (const int rc = launch_rc()) return rc;
-    // one load (16 bytes of fp32, 8 of fp16) per group of four elements where every row starts on that boundary
+    // one load (16 bytes of fp32, 8 of fp16 or bf16) per group of four elements where every row starts on that boundary
     const bool vec = D % 4 == 0 && aligned<4 * sizeof(T)>(vectors);
     const int rc = pick_bool(vec, [&](auto v) {
         constexpr bool VEC = v;
-        hipLaunchKernelGGL((k_kmeans_sums<HALF, VEC>), dim3((unsigned)cap, slabs), block, 0, st, vectors, B, D, order, list_offsets,
+        hipLaunchKernelGGL((k_kmeans_sums<ROW, VEC>), dim3((unsigned)cap, slabs), block, 0, st, vectors, B, D, order, list_offsets,
                            (int)L, block_first, cap, block_sums);
         return launch_rc();
     });
@@ -3006,30 +3028,51 @@ long mcq_kmeans_half_planes(long L, int D) {
     return 2 * L * half_padded_dim(D);
 }
 
+long mcq_kmeans_bf16_parts(long B, long L, int D) { return kmeans_parts(B, L, D, kBfVT, kBfFullBlocks); }
+
+long mcq_kmeans_bf16_planes(long L, int D) {
+    if (kmeans_domain(0, L, D) != 0) return 0;
+    return 3 * L * half_padded_dim(D);
+}
+
 int mcq_kmeans_assign(const float *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
                       const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
                       int32_t *part_list, void *stream) {
-    return kmeans_assign(vectors, B, centroids, L, D, terms, parts, prev_assign, assign, score, changed, part_score, part_list,
-                         nullptr, stream);
+    return kmeans_assign<kRowF32>(vectors, B, centroids, L, D, terms, parts, prev_assign, assign, score, changed, part_score,
+                                  part_list, nullptr, stream);
 }
 
 int mcq_kmeans_assign_half(const uint16_t *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
                            const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
                            int32_t *part_list, uint16_t *planes, void *stream) {
-    return kmeans_assign(vectors, B, centroids, L, D, terms, parts, prev_assign, assign, score, changed, part_score, part_list,
-                         planes, stream);
+    return kmeans_assign<kRowF16>(vectors, B, centroids, L, D, terms, parts, prev_assign, assign, score, changed, part_score,
+                                  part_list, planes, stream);
+}
+
+int mcq_kmeans_assign_bf16(const uint16_t *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
+                           const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
+                           int32_t *part_list, uint16_t *planes, void *stream) {
+    return kmeans_assign<kRowBf16>(vectors, B, centroids, L, D, terms, parts, prev_assign, assign, score, changed, part_score,
+                                   part_list, planes, stream);
 }
 
 int mcq_kmeans_update(const float *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
                       const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first, double *block_sums,
                       void *stream) {
-    return kmeans_update(vectors, B, D, order, list_offsets, L, centroids_in, centroids_out, counts, block_first, block_sums, stream);
+    return kmeans_update<kRowF32>(vectors, B, D, order, list_offsets, L, centroids_in, centroids_out, counts, block_first, block_sums, stream);
 }
 
 int mcq_kmeans_update_half(const uint16_t *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
                            const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first,
                            double *block_sums, void *stream) {
-    return kmeans_update(vectors, B, D, order, list_offsets, L, centroids_in, centroids_out, counts, block_first, block_sums, stream);
+    return kmeans_update<kRowF16>(vectors, B, D, order, list_offsets, L, centroids_in, centroids_out, counts, block_first, block_sums, stream);
+}
+
+int mcq_kmeans_update_bf16(const uint16_t *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,
+                           const float *centroids_in, float *centroids_out, int32_t *counts, int64_t *block_first,
+                           double *block_sums, void *stream) {
+    return kmeans_update<kRowBf16>(vectors, B, D, order, list_offsets, L, centroids_in, centroids_out, counts, block_first, block_sums,
+                                   stream);
 }
 
 // ---- rules 52-55 (include/mcq_coarse_half.h): the coarse probes for fp16 queries.  (mcq_coarse_half_kernels.h; the part

@@ -1,6 +1,6 @@
 // mcq_half_kernels.h -- gfx950 kernels of the Lloyd step over an fp16 raw store (include/mcq_half.h, rules 48-51): the nearest
 // centroid of every fp16 vector on the f16 matrix cores.  The order (pair_less), the tile plan and its recommended parts
-// (kKmFullBlocks), the meeting of the parts (k_kmeans_finish) and the whole update (k_kmeans_scan, k_kmeans_sums<true, VEC>,
+// (kKmFullBlocks), the meeting of the parts (k_kmeans_finish) and the whole update (k_kmeans_scan, k_kmeans_sums<kRowF16, VEC>,
 // k_kmeans_mean) are those of mcq_kmeans_kernels.h.
 //
 // k_half_split: fp32 centroids -> two fp16 planes [hi: L rows][lo: L rows] of Dp = 32 ceil(D / 32) halves each, once per call:
@@ -37,7 +37,7 @@
 // lines of k_kmeans_assign, kept as a copy here because one shared function gave k_kmeans_assign two scalar registers fewer
 // and every assign kernel another instruction text behind its loops (profiles/lloyd_fold_isa.txt).
 //
-// The update's sums over fp16 rows are the HALF flag of k_kmeans_sums (mcq_kmeans_kernels.h), not a kernel of this file.
+// The update's sums over fp16 rows are the kRowF16 form of k_kmeans_sums (mcq_kmeans_kernels.h), not a kernel of this file.
 #pragma once
 #include "mcq_kmeans_kernels.h"
 

@@ -2,8 +2,8 @@
 // nearest centroid of every training vector, and the members' mean per list.  The score and the order are those of the coarse
 // probes (rule 41, pair_less), the staging (coarse_load, coarse_store, the pitch of 34) is that of mcq_coarse_kernels.h and the
 // row-bounded gather (rerank_row, rerank_load) that of mcq_rerank_kernels.h; nothing of those files is changed.  The fp16 form of
-// the step (mcq_half_kernels.h, rules 48-51) has an assign kernel of its own and shares the rest: k_kmeans_finish, k_kmeans_scan,
-// k_kmeans_sums (its HALF flag) and k_kmeans_mean.
+// the step (mcq_half_kernels.h, rules 48-51) and the bf16 form (mcq_bf16_kernels.h, rules 56-59) have an assign kernel of their own
+// each and share the rest: k_kmeans_finish, k_kmeans_scan, k_kmeans_sums (its ROW tag) and k_kmeans_mean.
 //
 // k_kmeans_assign: one workgroup of 4 waves per (tile of 128 vectors, part of the centroid tiles of 128).  A wave owns a 64 x 64
 // block as 2 x 2 accumulators of 32 x 32 and runs v_mfma_f32_32x32x2_f32 with the CENTROIDS as the A operand: lane l supplies
@@ -27,8 +27,10 @@
 // + j of the slab; the rows of four members are loaded (16 loads a lane) before the first add and added in member order.  A
 // row is read through a descriptor that covers that row alone; a member that names no row, and an element past D, reads +0.0
 // without a memory access, and an accumulator that starts at +0.0 is never -0.0, so adding it changes no bit.  The quarter sums
-// meet in LDS (32 KiB) as ((q0 + q1) + q2) + q3.  HALF: the rows are fp16 (rerank_row<true>, rerank_load<true, VEC>, one 8-byte
-// load per group of four under VEC), each element widened exactly (fp16 -> fp32 -> float64) into the same tree.
+// meet in LDS (32 KiB) as ((q0 + q1) + q2) + q3.  ROW = kRowF16: the rows are fp16 (rerank_row<true>, rerank_load<true, VEC>, one
+// 8-byte load per group of four under VEC), each element widened exactly (fp16 -> fp32 -> float64) into the same tree.  ROW =
+// kRowBf16: the rows are bf16, read through the same 2-byte descriptor, each element widened exactly as its bits shifted left by
+// 16 (kmeans_row_load).
 // k_kmeans_mean: one workgroup per (list, slab) counts the list's members that name a row, adds its block sums in ascending
 // order, divides in float64 and rounds once; an empty list copies centroids_in.
 #pragma once
@@ -243,8 +245,30 @@ k_kmeans_scan(const int64_t *__restrict__ off, int L, long B, int64_t *__restric
     if (tid == 0) first[L] = carry;
 }
 
+// the type of a vector row: what the host paths and k_kmeans_sums are instantiated by (two of them are two bytes wide)
+constexpr int kRowF32 = 0, kRowF16 = 1, kRowBf16 = 2;
+
+// rerank_load for a row of type ROW: the four elements of one lane and trip as fp32, from element e of the row on
+template <int ROW, bool VEC>
+__device__ __forceinline__ void kmeans_row_load(float (&x)[4], __amdgpu_buffer_rsrc_t rs, int e) {
+    if constexpr (ROW != kRowBf16) {
+        rerank_load<ROW == kRowF16, VEC>(x, rs, e);
+    } else if constexpr (VEC) {
+        const rerank_v2i raw = __builtin_amdgcn_raw_buffer_load_b64(rs, e * 2, 0, 0);
+        const unsigned lo = (unsigned)raw[0], hi = (unsigned)raw[1];             // elements e, e + 1 | e + 2, e + 3
+        x[0] = __uint_as_float(lo << 16);
+        x[1] = __uint_as_float(lo & 0xffff0000u);
+        x[2] = __uint_as_float(hi << 16);
+        x[3] = __uint_as_float(hi & 0xffff0000u);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            x[j] = __uint_as_float((unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs, (e + j) * 2, 0, 0) << 16);
+    }
+}
+
 // cap: the blocks block_sums holds (the grid's x); sums is [cap][D]
-template <bool HALF, bool VEC>
+template <int ROW, bool VEC>
 __global__ void __launch_bounds__(64 * kKmWaves)
 k_kmeans_sums(const void *__restrict__ vectors, long B, int D, const int64_t *__restrict__ order,
               const int64_t *__restrict__ off, int L, const int64_t *__restrict__ first, long cap, double *__restrict__ sums) {
@@ -282,9 +306,9 @@ k_kmeans_sums(const void *__restrict__ vectors, long B, int D, const int64_t *__
             float x[kKmRows][4][4];
 #pragma unroll
             for (int r = 0; r < kKmRows; ++r) {
-                const __amdgpu_buffer_rsrc_t rs = rerank_row<HALF>(vectors, __builtin_amdgcn_readlane(row, j0 + r), D);
+                const __amdgpu_buffer_rsrc_t rs = rerank_row<ROW != kRowF32>(vectors, __builtin_amdgcn_readlane(row, j0 + r), D);
 #pragma unroll
-                for (int t = 0; t < 4; ++t) rerank_load<HALF, VEC>(x[r][t], rs, e0 + 256 * t);
+                for (int t = 0; t < 4; ++t) kmeans_row_load<ROW, VEC>(x[r][t], rs, e0 + 256 * t);
             }
 #pragma unroll
             for (int r = 0; r < kKmRows; ++r)

@@ -53,7 +53,9 @@ Where the coarse centroids come from: coarse_train(sample, num_lists) (quantizat
 mcq_kmeans_update) is k-means under "l2" in HIP, the same bits on every run; a trained layer or another k-means serves as well.
 A raw store kept in fp16 (what rerank reads) needs no fp32 copy for this: coarse_train_half(store16, num_lists) and
 coarse_assign_half(store16, centroids) (quantization_amd/half.py, mcq_kmeans_assign_half and mcq_kmeans_update_half) take
-torch.float16 rows against fp32 centroids on the f16 matrix cores; kmeans_step_half is the single step."""
+torch.float16 rows against fp32 centroids on the f16 matrix cores; kmeans_step_half is the single step.  A store kept in
+bf16 has the same three calls: coarse_train_bf16(store_bf16, num_lists), coarse_assign_bf16(store_bf16, centroids) and
+kmeans_step_bf16 (quantization_amd/bf16.py, mcq_kmeans_assign_bf16 and mcq_kmeans_update_bf16), on the bf16 matrix cores."""
 import torch
 from torch import Tensor
 

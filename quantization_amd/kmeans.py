@@ -21,25 +21,34 @@ __all__ = ["kmeans_step", "coarse_train"]
 SPLIT = 1e-4                # faiss's split of the largest list when another is empty
 
 
-# the dtype of the vector rows picks the entries (the parts query, the assignment, the update); fp16 rows also take the planes
-_ENTRIES = {torch.float32: ("mcq_kmeans_parts", "mcq_kmeans_assign", "mcq_kmeans_update"),
-            torch.float16: ("mcq_kmeans_half_parts", "mcq_kmeans_assign_half", "mcq_kmeans_update_half")}
-_NAME = {torch.float32: "fp32", torch.float16: "fp16"}
+# the dtype of the vector rows picks the entries (the parts query, the assignment, the update, and for 16-bit rows the size
+# query of the planes the centroids are split into)
+_ENTRIES = {torch.float32: ("mcq_kmeans_parts", "mcq_kmeans_assign", "mcq_kmeans_update", None),
+            torch.float16: ("mcq_kmeans_half_parts", "mcq_kmeans_assign_half", "mcq_kmeans_update_half", "mcq_kmeans_half_planes"),
+            torch.bfloat16: ("mcq_kmeans_bf16_parts", "mcq_kmeans_assign_bf16", "mcq_kmeans_update_bf16", "mcq_kmeans_bf16_planes")}
+_NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
+# the rows a call for 16-bit rows sends on by name, and the suffix of the public call that takes them
+_SENT_ON = {torch.float16: {torch.float32: ""}, torch.bfloat16: {torch.float32: "", torch.float16: "_half"}}
+
+
+def _elsewhere(vectors, dtype, name):
+    """rows of a type that another call serves: a ValueError that names that call.  name: the fp32 call's name"""
+    if isinstance(vectors, Tensor) and vectors.dtype in _SENT_ON[dtype]:
+        raise ValueError(f"vectors: {_NAME[vectors.dtype]} rows go to {name}{_SENT_ON[dtype][vectors.dtype]}; this call takes {dtype}")
 
 
 def _checked_step(vectors, centroids, terms, prev_assign, dtype=torch.float32, fp32_name=None):
     """shape and dtype errors of a step over rows of `dtype`: looks at no data, so it runs before any device work, on CPU
-    tensors too.  fp32_name: the call that fp32 rows are sent to by a call that takes torch.float16"""
+    tensors too.  fp32_name: the call that fp32 rows are sent to by a call that takes 16-bit rows"""
     if dtype == torch.float32:
         L, D = _checked(vectors, centroids, "l2", terms, "vectors")
         if vectors.ndim != 2:
             raise ValueError(f"vectors: an fp32 (B, {D}) tensor, not {tuple(vectors.shape)}")
     else:
         L, D = _checked(None, centroids, "l2", terms, "")
-        if isinstance(vectors, Tensor) and vectors.dtype == torch.float32:
-            raise ValueError(f"vectors: fp32 rows go to {fp32_name}; this call takes torch.float16")
+        _elsewhere(vectors, dtype, fp32_name)
         if not isinstance(vectors, Tensor) or vectors.dtype != dtype or vectors.ndim != 2 or vectors.shape[1] != D:
-            raise ValueError(f"vectors: an fp16 (B, {D}) tensor, not {getattr(vectors, 'dtype', type(vectors))} "
+            raise ValueError(f"vectors: an {_NAME[dtype]} (B, {D}) tensor, not {getattr(vectors, 'dtype', type(vectors))} "
                              f"{tuple(getattr(vectors, 'shape', ()))}")
     if L < 1:
         raise ValueError("centroids: at least one list to assign to")
@@ -54,10 +63,10 @@ def _checked_step(vectors, centroids, terms, prev_assign, dtype=torch.float32, f
 
 
 def _assign(x, c, terms, prev, B, L, D):
-    """x (B, D) fp32 or fp16 and c (L, D) fp32 contiguous on one device: the assignment entry of x.dtype, its outputs and its
-    scratch -> (assign, changed)"""
+    """x (B, D) fp32, fp16 or bf16 and c (L, D) fp32 contiguous on one device: the assignment entry of x.dtype, its outputs and
+    its scratch -> (assign, changed)"""
     dev = x.device
-    parts_query, entry, _ = _ENTRIES[x.dtype]
+    parts_query, entry, _, planes_query = _ENTRIES[x.dtype]
     parts = int(_entry(parts_query)(B, L, D))
     assign = torch.empty((B,), dtype=torch.int32, device=dev)
     score = torch.empty((B,), dtype=torch.float32, device=dev)
@@ -65,8 +74,8 @@ def _assign(x, c, terms, prev, B, L, D):
     part_score = torch.empty((B, parts), dtype=torch.float32, device=dev)
     part_list = torch.empty((B, parts), dtype=torch.int32, device=dev)
     scratch = [part_score.data_ptr(), part_list.data_ptr()]
-    if x.dtype == torch.float16:                             # the two fp16 planes of the centroids
-        planes = torch.empty((int(_entry("mcq_kmeans_half_planes")(L, D)),), dtype=torch.int16, device=dev)
+    if planes_query is not None:                             # the 16-bit planes of the centroids: two of fp16, three of bf16
+        planes = torch.empty((int(_entry(planes_query)(L, D)),), dtype=torch.int16, device=dev)
         scratch.append(planes.data_ptr())
     _call(entry, x.data_ptr(), B, c.data_ptr(), L, D, terms.data_ptr(), parts, None if prev is None else prev.data_ptr(),
           assign.data_ptr(), score.data_ptr(), None if changed is None else changed.data_ptr(), *scratch,
@@ -75,7 +84,8 @@ def _assign(x, c, terms, prev, B, L, D):
 
 
 def _step(x, c, terms, prev, B, L, D):
-    """x (B, D) fp32 or fp16 and c (L, D) fp32 contiguous on one device: the two entries of x.dtype and the sort between them"""
+    """x (B, D) fp32, fp16 or bf16 and c (L, D) fp32 contiguous on one device: the two entries of x.dtype and the sort between
+    them"""
     dev = x.device
     if terms is None:
         terms = coarse_terms(c)
@@ -94,7 +104,7 @@ def _step(x, c, terms, prev, B, L, D):
 
 
 def _public_step(vectors, centroids, terms, prev_assign, dtype, fp32_name):
-    """kmeans_step and kmeans_step_half: the checks, then _step on contiguous tensors"""
+    """kmeans_step, kmeans_step_half and kmeans_step_bf16: the checks, then _step on contiguous tensors"""
     B, L, D = _checked_step(vectors, centroids, terms, prev_assign, dtype, fp32_name)
     _on_device(vectors, centroids, terms, prev_assign)
     with torch.no_grad(), torch.cuda.device(vectors.device):
@@ -131,13 +141,13 @@ def _reseed(centroids, counts):
 
 
 def _train(vectors, num_lists, iters, seed, init, dtype, fp32_name):
-    """coarse_train and coarse_train_half: the argument errors, the start and `iters` times _step and _reseed"""
+    """coarse_train, coarse_train_half and coarse_train_bf16: the argument errors, the start and `iters` times _step and _reseed"""
     if isinstance(num_lists, bool) or not isinstance(num_lists, int) or num_lists < 1:
         raise ValueError(f"num_lists = {num_lists!r}: a positive integer")
     if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
         raise ValueError(f"iters = {iters!r}: a non-negative integer")
-    if dtype != torch.float32 and isinstance(vectors, Tensor) and vectors.dtype == torch.float32:
-        raise ValueError(f"vectors: fp32 rows go to {fp32_name}; this call takes torch.float16")
+    if dtype != torch.float32:
+        _elsewhere(vectors, dtype, fp32_name)
     if not isinstance(vectors, Tensor) or vectors.ndim != 2 or vectors.dtype != dtype or not 1 <= vectors.shape[1] <= MAX_DIM:
         raise ValueError(f"vectors: an {_NAME[dtype]} (B, D) tensor, 1 <= D <= {MAX_DIM}, not "
                          f"{getattr(vectors, 'dtype', type(vectors))} {tuple(getattr(vectors, 'shape', ()))}")
