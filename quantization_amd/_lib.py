@@ -1,4 +1,4 @@
-"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h, include/mcq_probe.h, include/mcq_wide.h, include/mcq_rerank.h, include/mcq_code16.h, include/mcq_shortlist.h, include/mcq_coarse.h, include/mcq_kmeans.h, include/mcq_half.h, include/mcq_coarse_half.h and include/mcq_bf16.h).
+"""ctypes binding of libmcq_hip.so (C ABI: include/mcq.h and its companions include/mcq_residual.h, include/mcq_probe.h, include/mcq_wide.h, include/mcq_rerank.h, include/mcq_code16.h, include/mcq_shortlist.h, include/mcq_coarse.h, include/mcq_kmeans.h, include/mcq_half.h, include/mcq_coarse_half.h, include/mcq_bf16.h and include/mcq_split.h).
 
 The library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950).  There
 is no CPU fallback: a missing library or a non-HIP tensor is an error.
@@ -204,6 +204,15 @@ BF16_SIGNATURES = {
 }
 BF16_SYMBOLS = tuple(BF16_SIGNATURES)
 
+# include/mcq_split.h, the companion header of the assignment of fp32 rows by six bf16 plane products, in the same form and in
+# its order (tests/test_split_host.py parses that header and compares)
+SPLIT_SIGNATURES = {
+    "mcq_kmeans_split_parts": _sig("l", "lli"),
+    "mcq_kmeans_split_planes": _sig("l", "li"),
+    "mcq_kmeans_assign_split": _sig("i", "plpliplpppppppp"),
+}
+SPLIT_SYMBOLS = tuple(SPLIT_SIGNATURES)
+
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
 MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
@@ -226,7 +235,7 @@ def lib():
     for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES, **PROBE_SIGNATURES, **WIDE_SIGNATURES,
                                       **RERANK_SIGNATURES, **CODE16_SIGNATURES, **SHORTLIST_SIGNATURES,
                                       **COARSE_SIGNATURES, **KMEANS_SIGNATURES, **HALF_SIGNATURES,
-                                      **COARSE_HALF_SIGNATURES, **BF16_SIGNATURES}.items():
+                                      **COARSE_HALF_SIGNATURES, **BF16_SIGNATURES, **SPLIT_SIGNATURES}.items():
         # an older build loaded through the A/B hook above may lack a symbol: it stays unbound, and calling it raises.
         # Without the hook a missing symbol fails here, at load
         if _ALT and not hasattr(L, name):

@@ -13,6 +13,7 @@
 #include "../../include/mcq_half.h"
 #include "../../include/mcq_coarse_half.h"
 #include "../../include/mcq_bf16.h"
+#include "../../include/mcq_split.h"
 #include "../../include/mcq_lanes.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
@@ -30,6 +31,7 @@
 #include "mcq_half_kernels.h"
 #include "mcq_coarse_half_kernels.h"
 #include "mcq_bf16_kernels.h"
+#include "mcq_split_kernels.h"
 #include "mcq_lanes.h"
 
 #include <cstdlib>
@@ -2876,10 +2878,11 @@ int mcq_coarse_probe(const float *queries, long Q, const float *centroids, long 
                                 out_score, out_bias);
 }
 
-// ---- rules 44-51 and 56-59 (include/mcq_kmeans.h, include/mcq_half.h, include/mcq_bf16.h): one Lloyd step over the coarse
-// centroids, from fp32 rows or from an fp16 or a bf16 raw store.  (mcq_kmeans_kernels.h, mcq_half_kernels.h, mcq_bf16_kernels.h;
-// the part buffers, the block buffers and the planes are typed arguments, as those of the coarse probes.)  One path per entry
-// pair: ROW (kRowF32, kRowF16, kRowBf16) names the type of a vector row, T = float or uint16_t carries it
+// ---- rules 44-51 and 56-63 (include/mcq_kmeans.h, include/mcq_half.h, include/mcq_bf16.h, include/mcq_split.h): one Lloyd
+// step over the coarse centroids, from fp32 rows or from an fp16 or a bf16 raw store.  (mcq_kmeans_kernels.h,
+// mcq_half_kernels.h, mcq_bf16_kernels.h, mcq_split_kernels.h; the part buffers, the block buffers and the planes are typed
+// arguments, as those of the coarse probes.)  One path per entry pair: ROW (kRowF32, kRowF16, kRowBf16) names the type of a
+// vector row, T = float or uint16_t carries it; kRowSplit is fp32 rows again, on the six plane products of rule 61
 extern "C++" {
 namespace {
 
@@ -2903,14 +2906,14 @@ long kmeans_parts(long B, long L, int D, int vtile = kKmVT, int full = kKmFullBl
     return parts < ct ? parts : ct;
 }
 
-// rules 45, 49 and 57.  float rows: `planes` is nullptr and not looked at
+// rules 45, 49, 57 and 61.  kRowF32: `planes` is nullptr and not looked at
 template <int ROW, typename T>
 int kmeans_assign(const T *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
                   const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
                   int32_t *part_list, uint16_t *planes, void *stream) {
-    static_assert(sizeof(T) == (ROW == kRowF32 ? 4 : 2), "the row tag and the element type agree");
+    static_assert(sizeof(T) == (ROW == kRowF32 || ROW == kRowSplit ? 4 : 2), "the row tag and the element type agree");
     constexpr bool PLANES = ROW != kRowF32;
-    constexpr int VT = ROW == kRowBf16 ? kBfVT : kKmVT;      // vectors of the assign kernel's tile
+    constexpr int VT = ROW == kRowBf16 ? kBfVT : ROW == kRowSplit ? kSpVT : kKmVT;   // vectors of the assign kernel's tile
     if (const int rc = kmeans_domain(B, L, D)) return rc;
     if ((B > 0 && (!assign || !score)) || (prev_assign && !changed)) return MCQ_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2929,7 +2932,24 @@ int kmeans_assign(const T *vectors, long B, const float *centroids, long L, int 
             return MCQ_EINVAL;
         const dim3 grid((unsigned)(vt * parts));
         int32_t *zeroed = prev_assign ? changed : nullptr;
-        if constexpr (ROW == kRowBf16) {
+        if constexpr (ROW == kRowSplit) {
+            // the centroids' three planes by the bf16 step's split, then the kernel that splits the vectors as it stages them:
+            // two 16-byte loads per staged group of eight floats where every vector row starts on that boundary
+            const bool vec = D % 4 == 0 && aligned<16>(vectors);
+            const long groups = L * (half_padded_dim(D) / 8), want = (groups + 64 * kKmWaves - 1) / (64 * kKmWaves);
+            const int rc = pick_bool(vec, [&](auto v) {
+                constexpr bool VEC = v;
+                static bool allowed[64] = {};
+                if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_kmeans_assign_split<VEC>), kSpLdsAll)) return rc;
+                hipLaunchKernelGGL(k_bf16_split, dim3((unsigned)(want < kHalfSplitBlocks ? want : kHalfSplitBlocks)), block, 0, st,
+                                   centroids, (int)L, D, planes);
+                if (const int rc = launch_rc()) return rc;
+                hipLaunchKernelGGL((k_kmeans_assign_split<VEC>), grid, block, kSpLdsAll, st, vectors, (int)B, planes, (int)L, D, terms,
+                                   (int)parts, part_score, part_list, zeroed);
+                return launch_rc();
+            });
+            if (rc) return rc;
+        } else if constexpr (ROW == kRowBf16) {
             // as for fp16 rows below; three planes, and a workgroup of kBfWaves waves per tile of kBfVT vectors
             const bool vec = D % 8 == 0 && aligned<16>(vectors);
             const long groups = L * (half_padded_dim(D) / 8), want = (groups + 64 * kKmWaves - 1) / (64 * kKmWaves);
@@ -3035,6 +3055,10 @@ long mcq_kmeans_bf16_planes(long L, int D) {
     return 3 * L * half_padded_dim(D);
 }
 
+long mcq_kmeans_split_parts(long B, long L, int D) { return kmeans_parts(B, L, D, kSpVT, kSpFullBlocks); }
+
+long mcq_kmeans_split_planes(long L, int D) { return mcq_kmeans_bf16_planes(L, D); }
+
 int mcq_kmeans_assign(const float *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
                       const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
                       int32_t *part_list, void *stream) {
@@ -3054,6 +3078,13 @@ int mcq_kmeans_assign_bf16(const uint16_t *vectors, long B, const float *centroi
                            int32_t *part_list, uint16_t *planes, void *stream) {
     return kmeans_assign<kRowBf16>(vectors, B, centroids, L, D, terms, parts, prev_assign, assign, score, changed, part_score,
                                    part_list, planes, stream);
+}
+
+int mcq_kmeans_assign_split(const float *vectors, long B, const float *centroids, long L, int D, const float *terms, long parts,
+                            const int32_t *prev_assign, int32_t *assign, float *score, int32_t *changed, float *part_score,
+                            int32_t *part_list, uint16_t *planes, void *stream) {
+    return kmeans_assign<kRowSplit>(vectors, B, centroids, L, D, terms, parts, prev_assign, assign, score, changed, part_score,
+                                    part_list, planes, stream);
 }
 
 int mcq_kmeans_update(const float *vectors, long B, int D, const int64_t *order, const int64_t *list_offsets, long L,

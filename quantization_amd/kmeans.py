@@ -21,26 +21,33 @@ __all__ = ["kmeans_step", "coarse_train"]
 SPLIT = 1e-4                # faiss's split of the largest list when another is empty
 
 
-# the dtype of the vector rows picks the entries (the parts query, the assignment, the update, and for 16-bit rows the size
-# query of the planes the centroids are split into)
+# the dtype of the vector rows picks the entries (the parts query, the assignment, the update, and the size query of the planes
+# the centroids are split into, where they are); PLANES6 picks those of include/mcq_split.h, which take fp32 rows too
+PLANES6 = "split"
 _ENTRIES = {torch.float32: ("mcq_kmeans_parts", "mcq_kmeans_assign", "mcq_kmeans_update", None),
             torch.float16: ("mcq_kmeans_half_parts", "mcq_kmeans_assign_half", "mcq_kmeans_update_half", "mcq_kmeans_half_planes"),
-            torch.bfloat16: ("mcq_kmeans_bf16_parts", "mcq_kmeans_assign_bf16", "mcq_kmeans_update_bf16", "mcq_kmeans_bf16_planes")}
+            torch.bfloat16: ("mcq_kmeans_bf16_parts", "mcq_kmeans_assign_bf16", "mcq_kmeans_update_bf16", "mcq_kmeans_bf16_planes"),
+            PLANES6: ("mcq_kmeans_split_parts", "mcq_kmeans_assign_split", "mcq_kmeans_update", "mcq_kmeans_split_planes")}
 _NAME = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
-# the rows a call for 16-bit rows sends on by name, and the suffix of the public call that takes them
-_SENT_ON = {torch.float16: {torch.float32: ""}, torch.bfloat16: {torch.float32: "", torch.float16: "_half"}}
+# the rows a call sends on by name, and the suffix of the public call that takes them
+_SENT_ON = {torch.float16: {torch.float32: ""}, torch.bfloat16: {torch.float32: "", torch.float16: "_half"},
+            PLANES6: {torch.float16: "_half", torch.bfloat16: "_bf16"}}
 
 
 def _elsewhere(vectors, dtype, name):
     """rows of a type that another call serves: a ValueError that names that call.  name: the fp32 call's name"""
     if isinstance(vectors, Tensor) and vectors.dtype in _SENT_ON[dtype]:
-        raise ValueError(f"vectors: {_NAME[vectors.dtype]} rows go to {name}{_SENT_ON[dtype][vectors.dtype]}; this call takes {dtype}")
+        raise ValueError(f"vectors: {_NAME[vectors.dtype]} rows go to {name}{_SENT_ON[dtype][vectors.dtype]}; this call takes "
+                         f"{torch.float32 if dtype == PLANES6 else dtype}")
 
 
 def _checked_step(vectors, centroids, terms, prev_assign, dtype=torch.float32, fp32_name=None):
-    """shape and dtype errors of a step over rows of `dtype`: looks at no data, so it runs before any device work, on CPU
-    tensors too.  fp32_name: the call that fp32 rows are sent to by a call that takes 16-bit rows"""
-    if dtype == torch.float32:
+    """shape and dtype errors of a step over rows of `dtype` (PLANES6: fp32 rows for the entries of include/mcq_split.h): looks
+    at no data, so it runs before any device work, on CPU tensors too.  fp32_name: the call that fp32 rows are sent to by a
+    call that takes 16-bit rows, or the one whose suffixed forms take the 16-bit rows that PLANES6 sends on"""
+    if dtype == PLANES6:
+        _elsewhere(vectors, dtype, fp32_name)
+    if dtype in (torch.float32, PLANES6):
         L, D = _checked(vectors, centroids, "l2", terms, "vectors")
         if vectors.ndim != 2:
             raise ValueError(f"vectors: an fp32 (B, {D}) tensor, not {tuple(vectors.shape)}")
@@ -62,11 +69,11 @@ def _checked_step(vectors, centroids, terms, prev_assign, dtype=torch.float32, f
     return B, L, D
 
 
-def _assign(x, c, terms, prev, B, L, D):
-    """x (B, D) fp32, fp16 or bf16 and c (L, D) fp32 contiguous on one device: the assignment entry of x.dtype, its outputs and
-    its scratch -> (assign, changed)"""
+def _assign(x, c, terms, prev, B, L, D, key=None):
+    """x (B, D) fp32, fp16 or bf16 and c (L, D) fp32 contiguous on one device: the assignment entry of x.dtype, or of `key`
+    (PLANES6, fp32 rows) where one is given, its outputs and its scratch -> (assign, changed)"""
     dev = x.device
-    parts_query, entry, _, planes_query = _ENTRIES[x.dtype]
+    parts_query, entry, _, planes_query = _ENTRIES[key or x.dtype]
     parts = int(_entry(parts_query)(B, L, D))
     assign = torch.empty((B,), dtype=torch.int32, device=dev)
     score = torch.empty((B,), dtype=torch.float32, device=dev)
@@ -75,6 +82,7 @@ def _assign(x, c, terms, prev, B, L, D):
     part_list = torch.empty((B, parts), dtype=torch.int32, device=dev)
     scratch = [part_score.data_ptr(), part_list.data_ptr()]
     if planes_query is not None:                             # the 16-bit planes of the centroids: two of fp16, three of bf16
+                                                             # (for bf16 rows and for PLANES6)
         planes = torch.empty((int(_entry(planes_query)(L, D)),), dtype=torch.int16, device=dev)
         scratch.append(planes.data_ptr())
     _call(entry, x.data_ptr(), B, c.data_ptr(), L, D, terms.data_ptr(), parts, None if prev is None else prev.data_ptr(),
@@ -83,13 +91,13 @@ def _assign(x, c, terms, prev, B, L, D):
     return assign, changed
 
 
-def _step(x, c, terms, prev, B, L, D):
-    """x (B, D) fp32, fp16 or bf16 and c (L, D) fp32 contiguous on one device: the two entries of x.dtype and the sort between
-    them"""
+def _step(x, c, terms, prev, B, L, D, entries=None):
+    """x (B, D) fp32, fp16 or bf16 and c (L, D) fp32 contiguous on one device: the two entries of x.dtype, or of `entries`
+    (_assign's `key`), and the sort between them"""
     dev = x.device
     if terms is None:
         terms = coarse_terms(c)
-    assign, changed = _assign(x, c, terms, prev, B, L, D)
+    assign, changed = _assign(x, c, terms, prev, B, L, D, entries)
     # the stable sort by list: ascending original position inside a list; a row assigned -1 sorts behind list L - 1
     key = torch.where(assign < 0, torch.full_like(assign, L), assign).to(torch.int64)
     keys, order = torch.sort(key, stable=True)
@@ -98,18 +106,20 @@ def _step(x, c, terms, prev, B, L, D):
     counts = torch.empty((L,), dtype=torch.int32, device=dev)
     block_first = torch.empty((L + 1,), dtype=torch.int64, device=dev)
     block_sums = torch.empty((int(_entry("mcq_kmeans_blocks")(B, L, D)),), dtype=torch.float64, device=dev)
-    _call(_ENTRIES[x.dtype][2], x.data_ptr(), B, D, order.data_ptr(), offsets.data_ptr(), L, c.data_ptr(), new.data_ptr(),
+    _call(_ENTRIES[entries or x.dtype][2], x.data_ptr(), B, D, order.data_ptr(), offsets.data_ptr(), L, c.data_ptr(), new.data_ptr(),
           counts.data_ptr(), block_first.data_ptr(), block_sums.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     return new, assign, counts, changed
 
 
 def _public_step(vectors, centroids, terms, prev_assign, dtype, fp32_name):
-    """kmeans_step, kmeans_step_half and kmeans_step_bf16: the checks, then _step on contiguous tensors"""
+    """kmeans_step, kmeans_step_half, kmeans_step_bf16 and kmeans_step_split (dtype PLANES6): the checks, then _step on
+    contiguous tensors"""
     B, L, D = _checked_step(vectors, centroids, terms, prev_assign, dtype, fp32_name)
     _on_device(vectors, centroids, terms, prev_assign)
     with torch.no_grad(), torch.cuda.device(vectors.device):
         return _step(vectors.detach().contiguous(), centroids.detach().contiguous(), terms,
-                     None if prev_assign is None else prev_assign.detach().contiguous(), B, L, D)
+                     None if prev_assign is None else prev_assign.detach().contiguous(), B, L, D,
+                     PLANES6 if dtype == PLANES6 else None)
 
 
 def kmeans_step(vectors: Tensor, centroids: Tensor, terms: Tensor = None, prev_assign: Tensor = None):
@@ -141,13 +151,15 @@ def _reseed(centroids, counts):
 
 
 def _train(vectors, num_lists, iters, seed, init, dtype, fp32_name):
-    """coarse_train, coarse_train_half and coarse_train_bf16: the argument errors, the start and `iters` times _step and _reseed"""
+    """coarse_train, coarse_train_half, coarse_train_bf16 and coarse_train_split (dtype PLANES6): the argument errors, the start
+    and `iters` times _step and _reseed"""
+    key, dtype = (PLANES6, torch.float32) if dtype == PLANES6 else (None, dtype)
     if isinstance(num_lists, bool) or not isinstance(num_lists, int) or num_lists < 1:
         raise ValueError(f"num_lists = {num_lists!r}: a positive integer")
     if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
         raise ValueError(f"iters = {iters!r}: a non-negative integer")
-    if dtype != torch.float32:
-        _elsewhere(vectors, dtype, fp32_name)
+    if key or dtype != torch.float32:
+        _elsewhere(vectors, key or dtype, fp32_name)
     if not isinstance(vectors, Tensor) or vectors.ndim != 2 or vectors.dtype != dtype or not 1 <= vectors.shape[1] <= MAX_DIM:
         raise ValueError(f"vectors: an {_NAME[dtype]} (B, D) tensor, 1 <= D <= {MAX_DIM}, not "
                          f"{getattr(vectors, 'dtype', type(vectors))} {tuple(getattr(vectors, 'shape', ()))}")
@@ -171,7 +183,7 @@ def _train(vectors, num_lists, iters, seed, init, dtype, fp32_name):
         else:
             centroids = init.detach().contiguous().clone()
         for _ in range(iters):
-            centroids, _, counts, _ = _step(x, centroids, None, None, B, num_lists, D)
+            centroids, _, counts, _ = _step(x, centroids, None, None, B, num_lists, D, key)
             centroids = _reseed(centroids, counts)
     return centroids
 
