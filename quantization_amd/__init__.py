@@ -16,9 +16,10 @@ from .half import coarse_assign_half, kmeans_step_half, coarse_train_half  # noq
 from .half import coarse_planes, coarse_probe_half  # noqa: F401   (the coarse probes for fp16 queries, on the same matrix cores)
 from .bf16 import coarse_assign_bf16, kmeans_step_bf16, coarse_train_bf16  # noqa: F401   (the Lloyd step and the trainer over a bf16 raw store, on the bf16 matrix cores)
 from .split import coarse_assign_split, kmeans_step_split, coarse_train_split  # noqa: F401   (the same for fp32 rows on the bf16 matrix cores: six products of bf16 planes)
+from .split import coarse_planes_split, coarse_probe_split  # noqa: F401   (the coarse probes for fp32 queries on those six products, a heap per query)
 
 __all__ = ["Quantizer", "QuantizerTrainer", "JointCodebookLoss", "read_hdf5_data", "build_lists", "probe_lists", "probe_bias", "list_assign", "rerank",
            "coarse_terms", "coarse_probe", "coarse_assign", "kmeans_step", "coarse_train",
            "coarse_assign_half", "kmeans_step_half", "coarse_train_half", "coarse_planes", "coarse_probe_half",
            "coarse_assign_bf16", "kmeans_step_bf16", "coarse_train_bf16",
-           "coarse_assign_split", "kmeans_step_split", "coarse_train_split"]
+           "coarse_assign_split", "kmeans_step_split", "coarse_train_split", "coarse_planes_split", "coarse_probe_split"]

@@ -213,6 +213,15 @@ SPLIT_SIGNATURES = {
 }
 SPLIT_SYMBOLS = tuple(SPLIT_SIGNATURES)
 
+# include/mcq_coarse_split.h, the companion header of the coarse probes for fp32 queries by six bf16 plane products, in the
+# same form and in its order (tests/test_coarse_split_host.py parses that header and compares)
+COARSE_SPLIT_SIGNATURES = {
+    "mcq_coarse_split_parts": _sig("l", "llii"),
+    "mcq_coarse_split_planes": _sig("i", "plipp"),
+    "mcq_coarse_probe_split": _sig("i", "plpplipiilppppppp"),
+}
+COARSE_SPLIT_SYMBOLS = tuple(COARSE_SPLIT_SIGNATURES)
+
 MCQ_EINVAL, MCQ_EUNSUPPORTED, MCQ_EWORKSPACE = -1, -2, -3
 MCQ_SEARCH_L2, MCQ_SEARCH_IP, MCQ_SEARCH_COS = 0, 1, 2     # mcq_search_scan_metric
 MCQ_ENCODE_ALL_PASSES = 8       # mcq_encode_ex: every pass on every vector (fixed-point skipping is the default)
@@ -235,7 +244,8 @@ def lib():
     for name, (restype, argtypes) in {**SIGNATURES, **RESIDUAL_SIGNATURES, **PROBE_SIGNATURES, **WIDE_SIGNATURES,
                                       **RERANK_SIGNATURES, **CODE16_SIGNATURES, **SHORTLIST_SIGNATURES,
                                       **COARSE_SIGNATURES, **KMEANS_SIGNATURES, **HALF_SIGNATURES,
-                                      **COARSE_HALF_SIGNATURES, **BF16_SIGNATURES, **SPLIT_SIGNATURES}.items():
+                                      **COARSE_HALF_SIGNATURES, **BF16_SIGNATURES, **SPLIT_SIGNATURES,
+                                      **COARSE_SPLIT_SIGNATURES}.items():
         # an older build loaded through the A/B hook above may lack a symbol: it stays unbound, and calling it raises.
         # Without the hook a missing symbol fails here, at load
         if _ALT and not hasattr(L, name):

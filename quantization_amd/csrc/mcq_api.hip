@@ -14,6 +14,7 @@
 #include "../../include/mcq_coarse_half.h"
 #include "../../include/mcq_bf16.h"
 #include "../../include/mcq_split.h"
+#include "../../include/mcq_coarse_split.h"
 #include "../../include/mcq_lanes.h"
 #include "mcq_kernels.h"
 #include "mcq_fix_kernels.h"
@@ -32,6 +33,7 @@
 #include "mcq_coarse_half_kernels.h"
 #include "mcq_bf16_kernels.h"
 #include "mcq_split_kernels.h"
+#include "mcq_coarse_split_kernels.h"
 #include "mcq_lanes.h"
 
 #include <cstdlib>
@@ -3193,6 +3195,84 @@ int mcq_coarse_probe_half(const uint16_t *queries, long Q, const float *centroid
     });
     if (rc) return rc;
     return finish((int)parts, D % 4 == 0 && aligned<16>(centroids));
+}
+
+// ---- rules 64-67 (include/mcq_coarse_split.h): the coarse probes for fp32 queries on the six bf16 plane products.
+// (mcq_coarse_split_kernels.h; the part buffers and the queries' planes are typed arguments, the centroids' planes a const
+// input the caller made once with mcq_coarse_split_planes; the finish is mcq_coarse_probe's)
+extern "C++" {
+namespace {
+
+long coarse_split_tiles(long L) { return (L + kCsCT - 1) / kCsCT; }
+
+// k_bf16_split over R rows: the launch of the Lloyd steps
+int launch_bf16_split(hipStream_t st, const float *rows, long R, int D, uint16_t *planes) {
+    const long groups = R * (half_padded_dim(D) / 8), want = (groups + 64 * kKmWaves - 1) / (64 * kKmWaves);
+    hipLaunchKernelGGL(k_bf16_split, dim3((unsigned)(want < kHalfSplitBlocks ? want : kHalfSplitBlocks)), dim3(64 * kKmWaves), 0, st,
+                       rows, (int)R, D, planes);
+    return launch_rc();
+}
+
+}  // namespace
+}  // extern "C++"
+
+long mcq_coarse_split_parts(long Q, long L, int D, int P) {
+    if (Q <= 0 || L <= 0 || coarse_domain(Q, L, D, P, MCQ_SEARCH_L2) != 0) return 1;
+    const int tile = coarse_split_queries(coarse_split_class(P));
+    const long qt = (Q + tile - 1) / tile, ct = coarse_split_tiles(L);
+    if (qt >= kCsFullBlocks) return 1;
+    const long parts = (kCsFullBlocks + qt - 1) / qt;
+    return parts < ct ? parts : ct;
+}
+
+int mcq_coarse_split_planes(const float *rows, long R, int D, uint16_t *planes, void *stream) {
+    if (const int rc = coarse_domain(0, R, D, 1, MCQ_SEARCH_L2)) return rc;
+    if (R == 0) return 0;
+    if (!rows || !planes || !aligned<4>(rows) || !aligned<16>(planes)) return MCQ_EINVAL;
+    return launch_bf16_split(static_cast<hipStream_t>(stream), rows, R, D, planes);
+}
+
+int mcq_coarse_probe_split(const float *queries, long Q, const float *centroids, const uint16_t *planes, long L, int D,
+                           const float *terms, int P, int metric, long parts, int32_t *out_list, float *out_score, float *out_bias,
+                           float *part_score, int32_t *part_list, uint16_t *query_planes, void *stream) {
+    if (const int rc = coarse_domain(Q, L, D, P, metric)) return rc;
+    if (Q > 0 && (!out_list || !out_score)) return MCQ_EINVAL;
+    if (Q == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (L == 0) {                                                          // no input is looked at: the tail
+        if (!aligned<4>(out_list) || !aligned<4>(out_score) || !aligned<4>(out_bias)) return MCQ_EINVAL;
+        return launch_coarse_finish(st, nullptr, nullptr, 0, P, nullptr, (int)Q, nullptr, 0, D, 0, out_list, out_score, out_bias);
+    }
+    const int cls = coarse_split_class(P);
+    const long qt = (Q + coarse_split_queries(cls) - 1) / coarse_split_queries(cls);
+    if (parts < 1 || parts > coarse_split_tiles(L)) return MCQ_EINVAL;
+    if (qt * parts >= kSizeLimit) return MCQ_EUNSUPPORTED;                 // (the grid of k_coarse_probe_split)
+    if (!queries || !centroids || !planes || !part_score || !part_list || !query_planes || (metric != MCQ_SEARCH_IP && !terms))
+        return MCQ_EINVAL;
+    if (!aligned<4>(out_list) || !aligned<4>(out_score) || !aligned<4>(out_bias) || !aligned<4>(queries) || !aligned<4>(centroids) ||
+        !aligned<16>(planes) || (metric != MCQ_SEARCH_IP && !aligned<4>(terms)) || !aligned<4>(part_score) ||
+        !aligned<4>(part_list) || !aligned<16>(query_planes))
+        return MCQ_EINVAL;
+    // the queries' three planes, once per call, then the kernel that moves plane rows of both sides
+    if (const int rc = launch_bf16_split(st, queries, Q, D, query_planes)) return rc;
+    const int rc = pick<kMetricL2, kMetricIP, kMetricCos>(metric, [&](auto m) {
+        return pick<0, 1, 2>(cls, [&](auto c) {
+            constexpr int METRIC = decltype(m)::value, CLASS = decltype(c)::value;
+            static bool allowed[64] = {};
+            if (const int rc = allow_dynamic_lds(allowed, reinterpret_cast<const void *>(&k_coarse_probe_split<METRIC, CLASS>),
+                                                 coarse_split_lds(CLASS)))
+                return rc;
+            hipLaunchKernelGGL((k_coarse_probe_split<METRIC, CLASS>), dim3((unsigned)(qt * parts)),
+                               dim3(64 * coarse_split_waves(CLASS)), coarse_split_lds(CLASS), st, query_planes, (int)Q, planes, (int)L,
+                               D, METRIC == kMetricIP ? nullptr : terms, P, (int)parts, part_score, part_list);
+            return launch_rc();
+        });
+    });
+    if (rc) return rc;
+    // mcq_coarse_probe's finish on the fp32 queries: one 16-byte load per group where every row of both operands starts there
+    const int vec = D % 4 == 0 && aligned<16>(queries) && aligned<16>(centroids);
+    return launch_coarse_finish(st, part_score, part_list, (int)parts, P, queries, (int)Q, centroids, (int)L, D, vec, out_list,
+                                out_score, out_bias);
 }
 
 // rule 10: a byte per stored vector -> a bit per stored vector
